@@ -10,10 +10,17 @@ defaults, core/config.py:30,53-57) over one synthetic ZINC-like batch of 128 gra
 first k=16 eigenvectors (BASELINE.json configs[1]), inputs resident in HBM.  Multi-GPU: the batch
 of 128*N graphs is sharded by graph, 128 per rank, no data-path collective (weak scaling).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up (W forwards, then untimed forwards until --clock-ramp-ms of wall time has passed: the GPU reaches its
+sustained clock), times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...).  `--full` adds every
+extra measurement and check of the forward bench to the same line (cold pass, roofline and per-kernel figures, the module's other
+modes, the CPU baseline, ...).  `--dump-outputs DIR` writes the predictions of the last timed step as DIR/y.npy (float32); the inputs
+and weights are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -891,9 +898,10 @@ def recorded_traffic(kernel):
 
 
 def relaunch_under_torchrun(n):
-    """`python bench.py --gpus N` without a launcher: re-exec this command line as
+    """`python bench.py --gpus N` without a launcher: run this command line again as a child process
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...`
-    (one rank per GPU over RCCL, the launch the driver uses).  Replaces the process; does not return."""
+    (one rank per GPU over RCCL, the launch the driver uses) and exit with its status; does not return.  A fresh child rather than
+    an exec: this process has already opened the GPU (device_count)."""
     import socket
     have = torch.cuda.device_count()
     if have < n and os.environ.get("SN_BENCH_SHARE_DEVICE", "0") != "1":
@@ -907,7 +915,27 @@ def relaunch_under_torchrun(n):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
+
+
+def dump_outputs(outdir, arrays, limit_bytes=64 << 20):
+    """--dump-outputs DIR: every array as DIR/<name>.npy in float32 (float64 stays float64), at most `limit_bytes` in all; a larger
+    array is replaced by a fixed sample (seeded, the same entries from run to run) and its shape is recorded in DIR/<name>.shape.json."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = (a.double() if a.dtype == torch.float64 else a.float()).contiguous().numpy()
+        budget = max(0, limit_bytes - total) // a.itemsize
+        if a.size > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=budget, replace=False))
+            with open(os.path.join(outdir, name + ".shape.json"), "w") as f:
+                json.dump({"shape": list(a.shape), "sampled_flat_indices_seed": 0, "sampled": int(budget)}, f)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        total += a.nbytes
 
 
 def main():
@@ -915,6 +943,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="forward bench: also run every extra measurement and check (cold pass, HIP-event roofline, per-kernel table, overlap / "
+                         "strict / layer-path / sustained / pipelined passes, SURVEY 8(d) protocol, all-eigenvector block, device clock probe, "
+                         "CPU baseline, scatter roofline, all-reduce probe).  Off: set up, warm up, time the K steps, print the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="forward bench: after the timed steps write what the last timed step computed (the predictions y a caller of "
+                         "model(data) receives) as DIR/y.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config", type=int, default=1, choices=[0, 1, 2, 4],
                     help="BASELINE.json configs index: 1 = the headline (default); 0 / 2 / 4 = extra measurements of the other "
@@ -944,6 +979,10 @@ def main():
                          "automatic: max(4, steps // 12), i.e. about a dozen brackets over the timed steps and never more than one launch in four — a bracket is two marker packets that idle the stream "
                          "for ~5 us, i.e. 10-15 us per step at stride 1: 0.277-0.284 ms instead of 0.266-0.267 ms without any)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.workload != "forward" or args.config == 4):
+        raise SystemExit("--dump-outputs: only the forward bench (--workload forward, --config 0 / 1 / 2) writes its outputs")
 
     global WORKLOAD
     if args.config == 4:
@@ -1018,6 +1057,8 @@ def main():
             torch.cuda.synchronize()
 
     ramp_steps = 0
+    dt_cold = dt_ovl = dt_strict = dt_layer = dt_pipe = None
+    rec = None
     with torch.no_grad():
         t_ramp = time.perf_counter()
         for i in range(args.warmup):
@@ -1025,20 +1066,21 @@ def main():
             if i == 0:                       # (the first forward packs the weights and loads the code objects: not GPU work)
                 torch.cuda.synchronize()
                 t_ramp = time.perf_counter()
-        # (0) COLD pass (reported as `cold`, not `value`): exactly the K steps a `--warmup W --steps K` command line describes, right
-        #     behind the W warm-up forwards and nothing else — the number a reader gets who takes the two flags at their word.  An idle
-        #     MI355X needs tens of milliseconds of continuous work to reach its sustained clock and W = 5 forwards are 1.4 ms of it.
-        sync_all()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            model(data)
-        model.check_last()
-        sync_all()
-        dt_cold = time.perf_counter() - t0
+        if args.full:
+            # (0) COLD pass (reported as `cold`, not `value`): exactly the K steps a `--warmup W --steps K` command line describes, right
+            #     behind the W warm-up forwards and nothing else — the number a reader gets who takes the two flags at their word.  An idle
+            #     MI355X needs tens of milliseconds of continuous work to reach its sustained clock and W = 5 forwards are 1.4 ms of it.
+            sync_all()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                model(data)
+            model.check_last()
+            sync_all()
+            dt_cold = time.perf_counter() - t0
         # clock ramp (untimed, reported in the line as `clock_ramp`): measured on one box, same command: phi 137-141 us and 0.290 ms per
         # sequential step behind --warmup 5, 120-126 us and 0.266 ms behind --warmup 200 (= a loop that has been running for 50 ms,
         # which is what a training / evaluation epoch is).  So more untimed forwards follow until --clock-ramp-ms of wall time have passed
-        # since the end of the first forward (the cold pass counts); the timed regions are exactly K steps each.
+        # since the end of the first forward (with --full the cold pass counts); the timed region is exactly K steps.
         if args.clock_ramp_ms > 0:
             torch.cuda.synchronize()
             while (time.perf_counter() - t_ramp) * 1e3 < args.clock_ramp_ms:
@@ -1046,148 +1088,146 @@ def main():
                     model(data)
                 ramp_steps += 8
                 torch.cuda.synchronize()
-        # timed region: HIP events only around the dominant kernel, on the launch stream, every --event-stride-th step
-        # (a bracket = two marker packets, each idling the stream for ~5 us: measured 0.277-0.284 / 0.270 / 0.266-0.267 ms per step at
-        #  stride 1 / 4 / no events on the same box.  Default: about a dozen brackets over the timed steps, at least one in eight)
-        if args.event_stride <= 0:
-            args.event_stride = max(4, args.steps // 12)        # never every launch by default: a 20-step driver run is not taxed
-        rec = ops.KernelTimer(only=["__none__"] if args.no_kernel_events else [DOMINANT], stride=args.event_stride)
+        # timed region, --full only: HIP events around the dominant kernel, on the launch stream, every --event-stride-th step (the
+        # `roofline` block; a bracket = two marker packets, each idling the stream for ~5 us: measured 0.277-0.284 / 0.270 / 0.266-0.267
+        # ms per step at stride 1 / 4 / no events on the same box.  Default: about a dozen brackets over the timed steps, at least one in
+        # eight).  A plain run takes no events.
+        if args.full:
+            if args.event_stride <= 0:
+                args.event_stride = max(4, args.steps // 12)        # never every launch by default: a 20-step driver run is not taxed
+            rec = ops.KernelTimer(only=["__none__"] if args.no_kernel_events else [DOMINANT], stride=args.event_stride)
         # (1) `value`: a plain `for: model(data)` loop at one call site, every kernel of a forward on the caller's stream, one after
         #     the other — the definition of rounds 1-2 (round 3 reported the module's opt-in overlap mode here; it is the `overlap_mode`
-        #     block now).  The dominant kernel's HIP events are taken here: alone on the chip its duration is attributable.
+        #     block now).  With --full the dominant kernel's HIP events are taken here: alone on the chip its duration is attributable.
         sync_all()
         t0 = time.perf_counter()
-        with rec:
+        with rec if rec is not None else contextlib.nullcontext():
             for _ in range(args.steps):
-                model(data)
+                y = model(data)
             model.check_last()               # every forward's status flags read and clean before the clock stops
         sync_all()
         dt = time.perf_counter() - t0
-        # (2) extra pass (`overlap_mode`, not `value`): the same loop with the module's opt-in overlap mode (pyg.SignNetGNN.overlap_front):
-        #     a forward is a three-stage pipeline — batch plan + phi on side stream A, rho on side stream B, the GINE stage on the caller's
-        #     stream, chained by events — so the stages of consecutive steps share the GPU.  Outputs are bit-identical and ordered on the
-        #     caller's stream; the batch is resident (the mode's precondition).
-        # (small batches — configs[0], 32 graphs — are bound by the host's ~0.1 ms of stream / event calls per overlapped forward: the
-        #  mode is measured from 64 graphs per GPU on)
-        overlap = not args.no_overlap and WORKLOAD["B"] >= 64
-        dt_ovl = None
-        if overlap:
-            model.overlap_front = True
-            for _ in range(args.overlap_warmup):        # untimed: the mode's side streams, events and per-forward buffers reach their steady state
+        y_last = y.float().cpu() if args.dump_outputs else None     # (before any extra pass of --full runs the model again)
+        if args.full:
+            # (2) extra pass (`overlap_mode`, not `value`): the same loop with the module's opt-in overlap mode (pyg.SignNetGNN.overlap_front):
+            #     a forward is a three-stage pipeline — batch plan + phi on side stream A, rho on side stream B, the GINE stage on the caller's
+            #     stream, chained by events — so the stages of consecutive steps share the GPU.  Outputs are bit-identical and ordered on the
+            #     caller's stream; the batch is resident (the mode's precondition).
+            # (small batches — configs[0], 32 graphs — are bound by the host's ~0.1 ms of stream / event calls per overlapped forward: the
+            #  mode is measured from 64 graphs per GPU on)
+            overlap = not args.no_overlap and WORKLOAD["B"] >= 64
+            dt_ovl = None
+            if overlap:
+                model.overlap_front = True
+                for _ in range(args.overlap_warmup):        # untimed: the mode's side streams, events and per-forward buffers reach their steady state
+                    model(data)
+                sync_all()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    model(data)
+                model.check_last()
+                sync_all()
+                dt_ovl = time.perf_counter() - t0
+                model.overlap_front = False
+            # extra pass (not `value`): the module's DEFAULT mode, strict = True (the flags are waited for after every forward)
+            model.strict = True
+            for _ in range(3):
                 model(data)
             sync_all()
             t0 = time.perf_counter()
             for _ in range(args.steps):
                 model(data)
-            model.check_last()
             sync_all()
-            dt_ovl = time.perf_counter() - t0
-            model.overlap_front = False
-        # extra pass (not `value`): the module's DEFAULT mode, strict = True (the flags are waited for after every forward)
-        model.strict = True
-        for _ in range(3):
-            model(data)
-        sync_all()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            model(data)
-        sync_all()
-        dt_strict = time.perf_counter() - t0
-        model.strict = False
-        # extra pass (not `value`): the LAYER-AT-A-TIME path (model.use_fused = False) — what serves a batch beyond the stage kernels'
-        # limits (a graph of > 64 nodes or > 192 in-edges, d > 128, ...: the reference has no such limits, Alchemy/sign_net/sign_net.py:
-        # 96-118), one launch per op on the same batch
-        dt_layer = None
-        if not args.no_extras:
-            model.use_fused, model._prep = False, None
-            for _ in range(3):
-                model(data)
-            sync_all()
-            n_layer = max(3, min(args.steps, 10))
-            t0 = time.perf_counter()
-            for _ in range(n_layer):
-                model(data)
-            sync_all()
-            dt_layer = (time.perf_counter() - t0) / n_layer
-            model.use_fused, model._prep = True, None
-            for _ in range(3):
-                model(data)
-            sync_all()
-        # extra pass (not `value`): the one-stream loop kept running for --sustained-ms of wall clock, in chunks of 200 forwards with one
-        # host wait each — the rate the part settles at (clocks, temperature) rather than that of a 25 ms window, and seconds of GPU
-        # activity for an outside utilisation sampler to see
-        sustained = None
-        if args.sustained_ms is None:
-            # >= 6 s: an outside utilisation sampler with 5 s spacing lands in it at least once (`gpu_busy` of the driver's record read 0
-            # for three rounds: the longest busy window of a run was 1.5 s)
-            args.sustained_ms = 0.0 if args.no_cpu_baseline else 6500.0
-        if args.sustained_ms > 0 and world == 1:
-            chunk, rates, n_fw = 200, [], 0
-            sync_all()
-            t_s = time.perf_counter()
-            while (time.perf_counter() - t_s) * 1e3 < args.sustained_ms:
-                t_c = time.perf_counter()
-                for _ in range(chunk):
+            dt_strict = time.perf_counter() - t0
+            model.strict = False
+            # extra pass (not `value`): the LAYER-AT-A-TIME path (model.use_fused = False) — what serves a batch beyond the stage kernels'
+            # limits (a graph of > 64 nodes or > 192 in-edges, d > 128, ...: the reference has no such limits, Alchemy/sign_net/sign_net.py:
+            # 96-118), one launch per op on the same batch
+            dt_layer = None
+            if not args.no_extras:
+                model.use_fused, model._prep = False, None
+                for _ in range(3):
                     model(data)
-                torch.cuda.synchronize()
-                rates.append(chunk * host.num_graphs / (time.perf_counter() - t_c))
-                n_fw += chunk
-            dt_s = time.perf_counter() - t_s
-            sustained = {"value": n_fw * host.num_graphs / dt_s, "unit": "graphs/s", "ms_per_step": 1e3 * dt_s / n_fw, "forwards": n_fw,
-                         "wall_ms": 1e3 * dt_s, "chunk_forwards": chunk, "chunk_min": min(rates), "chunk_max": max(rates),
-                         "note": "the `value` loop kept running for --sustained-ms (one host wait per 200 forwards); not `value`"}
-        # extra pass (not `value`): the same K steps issued round-robin on S HIP streams, so that independent batches
-        # overlap on the device the way a serving loop would run them (fills the tails of one step's kernels with the
-        # next step's work).  Same barrier + synchronize bracket, max over ranks.
-        dt_pipe = None
-        if args.streams > 1:
-            streams = [torch.cuda.Stream(device=dev) for _ in range(args.streams)]
-            for i in range(2 * args.streams):
-                with torch.cuda.stream(streams[i % args.streams]):
+                sync_all()
+                n_layer = max(3, min(args.steps, 10))
+                t0 = time.perf_counter()
+                for _ in range(n_layer):
                     model(data)
-            sync_all()
-            t0 = time.perf_counter()
-            for i in range(args.steps):
-                with torch.cuda.stream(streams[i % args.streams]):
+                sync_all()
+                dt_layer = (time.perf_counter() - t0) / n_layer
+                model.use_fused, model._prep = True, None
+                for _ in range(3):
                     model(data)
-            sync_all()
-            dt_pipe = time.perf_counter() - t0
-        # extra pass (not `value`): SURVEY 8(d)'s literal protocol (20 warm-up + 200 timed, median), one GPU
-        proto = protocol_8d_block(model, data, host.num_graphs) if (world == 1 and args.config == 1 and not args.no_extras) else None
-        # untimed extra pass: events around every launch, for the per-kernel table
-        rec_all = ops.KernelTimer()
-        with rec_all:
-            for _ in range(min(args.steps, 20)):
-                model(data)
-        torch.cuda.synchronize()
+                sync_all()
+            # extra pass (not `value`): the one-stream loop kept running for --sustained-ms of wall clock, in chunks of 200 forwards with one
+            # host wait each — the rate the part settles at (clocks, temperature) rather than that of a 25 ms window, and seconds of GPU
+            # activity for an outside utilisation sampler to see
+            sustained = None
+            if args.sustained_ms is None:
+                # >= 6 s: an outside utilisation sampler with 5 s spacing lands in it at least once (`gpu_busy` of the driver's record read 0
+                # for three rounds: the longest busy window of a run was 1.5 s)
+                args.sustained_ms = 0.0 if args.no_cpu_baseline else 6500.0
+            if args.sustained_ms > 0 and world == 1:
+                chunk, rates, n_fw = 200, [], 0
+                sync_all()
+                t_s = time.perf_counter()
+                while (time.perf_counter() - t_s) * 1e3 < args.sustained_ms:
+                    t_c = time.perf_counter()
+                    for _ in range(chunk):
+                        model(data)
+                    torch.cuda.synchronize()
+                    rates.append(chunk * host.num_graphs / (time.perf_counter() - t_c))
+                    n_fw += chunk
+                dt_s = time.perf_counter() - t_s
+                sustained = {"value": n_fw * host.num_graphs / dt_s, "unit": "graphs/s", "ms_per_step": 1e3 * dt_s / n_fw, "forwards": n_fw,
+                             "wall_ms": 1e3 * dt_s, "chunk_forwards": chunk, "chunk_min": min(rates), "chunk_max": max(rates),
+                             "note": "the `value` loop kept running for --sustained-ms (one host wait per 200 forwards); not `value`"}
+            # extra pass (not `value`): the same K steps issued round-robin on S HIP streams, so that independent batches
+            # overlap on the device the way a serving loop would run them (fills the tails of one step's kernels with the
+            # next step's work).  Same barrier + synchronize bracket, max over ranks.
+            dt_pipe = None
+            if args.streams > 1:
+                streams = [torch.cuda.Stream(device=dev) for _ in range(args.streams)]
+                for i in range(2 * args.streams):
+                    with torch.cuda.stream(streams[i % args.streams]):
+                        model(data)
+                sync_all()
+                t0 = time.perf_counter()
+                for i in range(args.steps):
+                    with torch.cuda.stream(streams[i % args.streams]):
+                        model(data)
+                sync_all()
+                dt_pipe = time.perf_counter() - t0
+            # extra pass (not `value`): SURVEY 8(d)'s literal protocol (20 warm-up + 200 timed, median), one GPU
+            proto = protocol_8d_block(model, data, host.num_graphs) if (world == 1 and args.config == 1 and not args.no_extras) else None
+            # untimed extra pass: events around every launch, for the per-kernel table
+            rec_all = ops.KernelTimer()
+            with rec_all:
+                for _ in range(min(args.steps, 20)):
+                    model(data)
+            torch.cuda.synchronize()
     dt_ranks = D.all_ranks(dt, dist, dev)          # every rank's own clock over the K timed steps (the line's time is their maximum)
     graphs_ranks = [int(v) for v in D.all_ranks(float(host.num_graphs), dist, dev)]
     dt = D.max_over_ranks(dt, dist, dev)
-    dt_cold = D.max_over_ranks(dt_cold, dist, dev)
-    if dt_ovl is not None:
-        dt_ovl = D.max_over_ranks(dt_ovl, dist, dev)
-    dt_strict = D.max_over_ranks(dt_strict, dist, dev)
-    if dt_pipe is not None:
-        dt_pipe = D.max_over_ranks(dt_pipe, dist, dev)
+    if args.dump_outputs:
+        # what the timed path computed in its last step: the [graphs, n_out] predictions a caller of model(data) receives, every rank's
+        # shard in rank order (= graph order of the global batch)
+        ys = [y_last]
+        if dist is not None:
+            ys = [None] * world
+            dist.all_gather_object(ys, y_last)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"y": torch.cat(ys, 0)})
+    if args.full:
+        dt_cold = D.max_over_ranks(dt_cold, dist, dev)
+        if dt_ovl is not None:
+            dt_ovl = D.max_over_ranks(dt_ovl, dist, dev)
+        dt_strict = D.max_over_ranks(dt_strict, dist, dev)
+        if dt_pipe is not None:
+            dt_pipe = D.max_over_ranks(dt_pipe, dist, dev)
 
     if rank == 0:
         total_graphs = sum(graphs_ranks) * args.steps
-        dom_times = rec.summary()                    # {kernel: (launches, mean_ms)} — measured inside the timed region
-        roof = None
-        if DOMINANT in dom_times:
-            launches, mean_ms = dom_times[DOMINANT]
-            roof = ops.KERNEL_ROOFLINE[DOMINANT](fl, WORKLOAD, host, mean_ms, 1.0)      # one launch per step
-            roof.update({"timed_launches": launches, "event_stride": args.event_stride, "timed_pass": "sequential"})
-            roof["frac_vs_f32_mfma"] = roof["achieved"] / MFMA_F32_PEAK_TF      # the same rate against the fp32-input MFMA peak (157.3)
-            roof.update(recorded_traffic(DOMINANT))
-        ktimes = rec_all.summary()
-        nall = min(args.steps, 20)
-        all_roofs = {}
-        for name, (launches, mean_ms) in ktimes.items():
-            f = ops.KERNEL_ROOFLINE.get(name)
-            if f is not None:
-                r = f(fl, WORKLOAD, host, mean_ms, launches / nall)
-                all_roofs[name] = {"achieved_tflops": r["achieved"], "frac": r["frac"]}
         out = {
             "metric": "graphs/sec SignNet+GINE forward, ZINC batch=128 k=16" if (args.config == 1 and not args.all_eigenvectors) else
                       "graphs/sec SignNet+GINE forward, ZINC batch=128, all eigenvectors (extra measurement, not the headline)" if args.all_eigenvectors else
@@ -1204,49 +1244,69 @@ def main():
                        "module_mode": "strict=False (no host wait per forward; every forward's device flags checked inside the timed region); "
                                       "overlap_front=False: a forward's kernels one after the other on the caller's stream"},
             "value_definition": "K forwards of a plain `for: model(data)` loop at one call site, one stream, between barrier + synchronize "
-                                "(rounds 1-2's definition; round 3's `value` was the opt-in overlap mode, now the `overlap_mode` block)",
-            "warmup_effective": args.warmup + args.steps + ramp_steps,
-            "cold": {"value": total_graphs / dt_cold, "unit": "graphs/s", "ms_per_step": 1e3 * dt_cold / args.steps, "untimed_forwards_before": args.warmup,
-                     "note": "the same K-step loop timed right behind the W warm-up forwards and nothing else (no clock ramp): what `--warmup W "
-                             "--steps K` says literally; `value` is measured after this pass and the clock ramp (`warmup_effective` untimed forwards)"},
-            "sequential": {"value": total_graphs / dt, "unit": "graphs/s", "ms_per_step": 1e3 * dt / args.steps,
-                           "note": "identical to `value` since round 4 (kept so that the block rounds 1-3 printed stays comparable)"},
-            "overlap_mode": None if dt_ovl is None else {
-                "value": total_graphs / dt_ovl, "unit": "graphs/s", "ms_per_step": 1e3 * dt_ovl / args.steps, "untimed_forwards_before": args.overlap_warmup,
-                "note": "extra pass, not `value`: model.overlap_front = True (opt-in): a forward = plan + phi on side stream A -> rho on side "
-                        "stream B -> GINE on the caller's stream, chained by events; consecutive forwards of the one call site overlap; "
-                        "bit-identical outputs (round 3's `value`)"},
-            "sustained": sustained,
-            "device": device_block(dev),
-            "strict_mode": {"value": total_graphs / dt_strict, "unit": "graphs/s", "ms_per_step": 1e3 * dt_strict / args.steps,
-                            "note": "the module's default: flags waited for after every forward (one host round trip per step); extra pass, not `value`"},
+                                "(rounds 1-2's definition; round 3's `value` was the opt-in overlap mode, now the `overlap_mode` block of --full)",
+            "warmup_effective": args.warmup + (args.steps if args.full else 0) + ramp_steps,
             "clock_ramp": {"ms": args.clock_ramp_ms, "extra_untimed_steps": ramp_steps,
-                           "note": "untimed forwards issued after the cold pass until `ms` of wall time had passed since the first forward, so "
-                                   "that the timed K steps of `value` run at the sustained clock (an idle GPU needs tens of ms of work to reach "
-                                   "it; --clock-ramp-ms 0 switches this off: `value` then differs from `cold` only by the K steps of the cold pass)"},
-            "layer_path": None if dt_layer is None else {
-                "value": sum(graphs_ranks) / dt_layer, "unit": "graphs/s", "ms_per_step": 1e3 * dt_layer,
-                "note": "extra pass, not `value`: model.use_fused = False — every op its own launch (sn_masked_linear_f32, sn_gin_aggregate_f32, "
-                        "sn_set_attention_f32, ...): the path a batch takes that the whole-stage kernels cannot hold (a graph of > 64 nodes or "
-                        "> 192 in-edges, hidden width > 128); the default mode routes such a batch here by itself"},
-            "protocol_8d": proto,
-            "roofline": roof,
-            "kernels": {k: {"launches_per_step": v[0] / nall, "mean_us": 1e3 * v[1], **all_roofs.get(k, {}), **KERNEL_BOUND_NOTES.get(k, {})}
-                        for k, v in ktimes.items()},
+                           "note": "untimed forwards issued after the warm-up (and, with --full, the cold pass) until `ms` of wall time had passed "
+                                   "since the first forward, so that the timed K steps of `value` run at the sustained clock (an idle GPU needs "
+                                   "tens of ms of work to reach it; --clock-ramp-ms 0 switches this off)"},
+            "full": args.full,
         }
-        if world == 1 and args.config == 1 and not args.no_extras:
-            out["all_eigenvectors"] = all_eigenvectors_block(dev, host, data, args.steps, args.warmup)
-        if dt_pipe is not None:
-            out["pipelined"] = {"streams": args.streams, "value": total_graphs / dt_pipe, "unit": "graphs/s",
-                                "ms_per_step": 1e3 * dt_pipe / args.steps,
-                                "note": "same K steps round-robin on S streams (independent batches overlap); not the headline value"}
-        if world == 1 and not args.no_cpu_baseline:
-            sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-            out["cpu_baseline"] = cpu_baseline(host, sd)
-            out["vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-    # (outside the timed region) every rank takes part in the RCCL probe; rank 0 measures the scatter roofline
+        if args.full:
+            dom_times = rec.summary()                    # {kernel: (launches, mean_ms)} — measured inside the timed region
+            roof = None
+            if DOMINANT in dom_times:
+                launches, mean_ms = dom_times[DOMINANT]
+                roof = ops.KERNEL_ROOFLINE[DOMINANT](fl, WORKLOAD, host, mean_ms, 1.0)      # one launch per step
+                roof.update({"timed_launches": launches, "event_stride": args.event_stride, "timed_pass": "sequential"})
+                roof["frac_vs_f32_mfma"] = roof["achieved"] / MFMA_F32_PEAK_TF      # the same rate against the fp32-input MFMA peak (157.3)
+                roof.update(recorded_traffic(DOMINANT))
+            ktimes = rec_all.summary()
+            nall = min(args.steps, 20)
+            all_roofs = {}
+            for name, (launches, mean_ms) in ktimes.items():
+                f = ops.KERNEL_ROOFLINE.get(name)
+                if f is not None:
+                    r = f(fl, WORKLOAD, host, mean_ms, launches / nall)
+                    all_roofs[name] = {"achieved_tflops": r["achieved"], "frac": r["frac"]}
+            out.update({
+                "cold": {"value": total_graphs / dt_cold, "unit": "graphs/s", "ms_per_step": 1e3 * dt_cold / args.steps, "untimed_forwards_before": args.warmup,
+                         "note": "the same K-step loop timed right behind the W warm-up forwards and nothing else (no clock ramp): what `--warmup W "
+                                 "--steps K` says literally; `value` is measured after this pass and the clock ramp (`warmup_effective` untimed forwards)"},
+                "sequential": {"value": total_graphs / dt, "unit": "graphs/s", "ms_per_step": 1e3 * dt / args.steps,
+                               "note": "identical to `value` since round 4 (kept so that the block rounds 1-3 printed stays comparable)"},
+                "overlap_mode": None if dt_ovl is None else {
+                    "value": total_graphs / dt_ovl, "unit": "graphs/s", "ms_per_step": 1e3 * dt_ovl / args.steps, "untimed_forwards_before": args.overlap_warmup,
+                    "note": "extra pass, not `value`: model.overlap_front = True (opt-in): a forward = plan + phi on side stream A -> rho on side "
+                            "stream B -> GINE on the caller's stream, chained by events; consecutive forwards of the one call site overlap; "
+                            "bit-identical outputs (round 3's `value`)"},
+                "sustained": sustained,
+                "device": device_block(dev),
+                "strict_mode": {"value": total_graphs / dt_strict, "unit": "graphs/s", "ms_per_step": 1e3 * dt_strict / args.steps,
+                                "note": "the module's default: flags waited for after every forward (one host round trip per step); extra pass, not `value`"},
+                "layer_path": None if dt_layer is None else {
+                    "value": sum(graphs_ranks) / dt_layer, "unit": "graphs/s", "ms_per_step": 1e3 * dt_layer,
+                    "note": "extra pass, not `value`: model.use_fused = False — every op its own launch (sn_masked_linear_f32, sn_gin_aggregate_f32, "
+                            "sn_set_attention_f32, ...): the path a batch takes that the whole-stage kernels cannot hold (a graph of > 64 nodes or "
+                            "> 192 in-edges, hidden width > 128); the default mode routes such a batch here by itself"},
+                "protocol_8d": proto,
+                "roofline": roof,
+                "kernels": {k: {"launches_per_step": v[0] / nall, "mean_us": 1e3 * v[1], **all_roofs.get(k, {}), **KERNEL_BOUND_NOTES.get(k, {})}
+                            for k, v in ktimes.items()},
+            })
+            if world == 1 and args.config == 1 and not args.no_extras:
+                out["all_eigenvectors"] = all_eigenvectors_block(dev, host, data, args.steps, args.warmup)
+            if dt_pipe is not None:
+                out["pipelined"] = {"streams": args.streams, "value": total_graphs / dt_pipe, "unit": "graphs/s",
+                                    "ms_per_step": 1e3 * dt_pipe / args.steps,
+                                    "note": "same K steps round-robin on S streams (independent batches overlap); not the headline value"}
+            if world == 1 and not args.no_cpu_baseline:
+                sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+                out["cpu_baseline"] = cpu_baseline(host, sd)
+                out["vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
+    # (outside the timed region, --full) every rank takes part in the RCCL probe; rank 0 measures the scatter roofline
     rccl = None
-    if dist is not None:
+    if dist is not None and args.full:
         rccl = rccl_allreduce_probe(dist, dev, sum(p.numel() for p in model.parameters()))
     if rank == 0:
         out["distributed"] = {"world_size": world, "backend": (f"{backend} (RCCL)" if backend == "nccl" else backend) if dist is not None else None,
@@ -1256,7 +1316,7 @@ def main():
                               "graphs_per_rank": graphs_ranks,
                               "data_path_collectives": 0, "gradient_allreduce": rccl,
                               "allreduce_us": None if rccl is None else rccl["allreduce_us"]}
-        if args.config == 1 and not args.no_scatter:
+        if args.full and args.config == 1 and not args.no_scatter:
             out["scatter_roofline"] = scatter_roofline(dev)
         print(json.dumps(out))
     if dist is not None:

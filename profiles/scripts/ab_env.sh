@@ -4,7 +4,7 @@
 var=$1; a=$2; b=$3; rounds=${4:-2}; shift 4
 out=gpurun_out/ab_env; mkdir -p $out
 for r in $(seq 1 $rounds); do for v in $a $b; do
-  env $var=$v python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-scatter --no-extras --no-overlap --streams 1 "$@" > $out/${var}_${v}_$r.json 2> $out/${var}_${v}_$r.err
+  env $var=$v python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-scatter --no-extras --no-overlap --streams 1 "$@" > $out/${var}_${v}_$r.json 2> $out/${var}_${v}_$r.err
   python - "$var=$v" $out/${var}_${v}_$r.json <<'P'
 import json,sys
 try:

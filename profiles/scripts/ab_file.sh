@@ -14,7 +14,7 @@ for r in $(seq 1 $rounds); do
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -I$C -x hip -c $src -o $C/$f.o || { echo "build failed: $which"; continue; }
     hipcc --offload-arch=gfx950 -shared -fPIC -o signnet_basisnet_amd/libsignnet_hip.so $C/*.o
     for rep in 1 2; do
-      python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-scatter --no-extras --no-overlap --streams 1 > $out/f_${i}_$rep.json 2> $out/f_${i}_$rep.err
+      python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-scatter --no-extras --no-overlap --streams 1 > $out/f_${i}_$rep.json 2> $out/f_${i}_$rep.err
       python - "$which" $out/f_${i}_$rep.json <<'P'
 import json,sys
 try:

@@ -10,7 +10,7 @@ for flags in "$@"; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w $fl -c $C/$f.hip -o $C/$f.o || { echo "build failed: $flags"; continue; }
   hipcc --offload-arch=gfx950 -shared -fPIC -o signnet_basisnet_amd/libsignnet_hip.so $C/*.o
   O=gpurun_out/pmcab/p$i; rm -rf $O; mkdir -p $O
-  timeout 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $O -- python bench.py --steps 20 --warmup 5 --streams 1 --no-overlap --no-scatter --no-cpu-baseline > $O.json 2> $O.err
+  timeout 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $O -- python bench.py --full --steps 20 --warmup 5 --streams 1 --no-overlap --no-scatter --no-cpu-baseline > $O.json 2> $O.err
   python - "$flags" $O <<'P'
 import csv, glob, sys, collections
 fs = glob.glob(sys.argv[2] + '/**/*counter_collection.csv', recursive=True)

@@ -25,7 +25,7 @@ def _run(extra, port, world=2):
 
 
 def test_forward_bench_two_ranks():
-    d = _run(["--no-cpu-baseline", "--no-scatter", "--streams", "1"], 29731)
+    d = _run(["--full", "--no-cpu-baseline", "--no-scatter", "--streams", "1"], 29731)
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["warmup"] == 2 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 256 and d["config"]["graphs_per_gpu"] == 128
     assert d["value"] > 0 and abs(d["value"] - 256 * 4 / (d["ms_per_step"] * 4e-3)) <= 1e-6 * d["value"]
@@ -48,7 +48,7 @@ def test_forward_bench_eight_ranks():
     """The driver's largest scaling point (N = 8, BASELINE configs[3]: 1 024 graphs as 8 x 128), launched exactly as the driver launches
     it, on the one-GPU box: eight ranks share cuda:0 over gloo.  What an 8-GPU node cannot break silently afterwards: eight ranks seen
     by the backend, eight clocks, eight shards of 128 graphs, a whole-job value over all of them, ONE line."""
-    d = _run(["--no-cpu-baseline", "--no-scatter", "--streams", "1", "--no-overlap", "--no-extras"], 29741, world=8)
+    d = _run(["--full", "--no-cpu-baseline", "--no-scatter", "--streams", "1", "--no-overlap", "--no-extras"], 29741, world=8)
     assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["config"]["global_batch"] == 1024 and d["config"]["graphs_per_gpu"] == 128
     g = d["distributed"]
     assert g["world_size"] == 8 and g["ranks_seen_by_backend"] == 8 and g["data_path_collectives"] == 0
@@ -73,12 +73,12 @@ def test_train_bench_two_ranks_allreduces_the_flat_gradient():
 
 
 def test_plain_python_launch_reexecs_under_torchrun():
-    """`python bench.py --gpus 2` (no launcher, no WORLD_SIZE) re-executes itself under torch.distributed.run — the driver's
+    """`python bench.py --gpus 2` (no launcher, no WORLD_SIZE) runs itself again under torch.distributed.run — the driver's
     scaling run may start it either way.  Same one-GPU arrangement as above (gloo, both ranks on cuda:0)."""
     env = dict(os.environ, SN_BENCH_BACKEND="gloo", SN_BENCH_SHARE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
            "--no-scatter", "--streams", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

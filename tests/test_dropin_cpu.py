@@ -192,41 +192,3 @@ def test_install_is_scoped_to_the_listed_names():
     with pytest.raises(KeyError):
         D.shim_dir("nope")
 
-
-REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
-def test_real_reference_siblings_import_next_to_the_hip_modules():
-    """In the build container: the reference's OWN `core.model` / `load_net.py` / `layers.mlp_readout_layer` import beside the HIP
-    modules (third-party graph libraries through the stand-ins of tests/golden/ref_shim)."""
-    shim = os.path.join(REPO, "tests", "golden", "ref_shim")
-    code = textwrap.dedent(f"""
-        import sys
-        sys.path[:0] = [{shim!r}]
-        import signnet_basisnet_amd.dropin as D
-        tree = sys.argv[1]
-        D.install(tree)
-        out = {{}}
-        if tree == "gine_pyg":
-            sys.path.insert(0, {REF + '/GINESignNetPyG'!r})
-            from core.model import GNN
-            from core.sign_net import SignNetGNN
-            import core.model_utils.elements as E
-            out = dict(GNN=GNN.__module__, GNN_file=sys.modules[GNN.__module__].__file__, SignNetGNN=SignNetGNN.__module__,
-                       elements=E.__file__)
-        elif tree == "graphprediction":
-            sys.path.insert(0, {REF + '/GraphPrediction'!r})
-            from nets.ZINC_graph_regression.load_net import gnn_model
-            from layers.mlp_readout_layer import MLPReadout
-            import nets.ZINC_graph_regression.load_net as L
-            out = dict(load_net=L.__file__, MLPReadout=sys.modules[MLPReadout.__module__].__file__,
-                       nets={{k: getattr(L, k + "Net").__module__ for k in ("GatedGCN", "GIN", "GAT", "PNA", "Transformer")}})
-        import json; print("REPORT " + json.dumps(out))
-    """)
-    got = _run([sys.executable, "-c", code, "gine_pyg"], cwd=REPO)
-    assert got["GNN_file"].startswith(REF) and got["elements"].startswith(REF)
-    assert got["SignNetGNN"].startswith("signnet_basisnet_amd")
-    got = _run([sys.executable, "-c", code, "graphprediction"], cwd=REPO)
-    assert got["load_net"].startswith(REF) and got["MLPReadout"].startswith(REF)
-    assert all(v.startswith("signnet_basisnet_amd") for v in got["nets"].values()), got

@@ -440,6 +440,24 @@ SIZE_CASES = {
 }
 
 
+def size_case_batch(name):
+    """synth.make_batch's batch of SIZE_CASES[name] with its eigendecomposition read from tests/golden/size_cases_eig.npz
+    (tests/golden/make_size_cases_eig.py): the host's LAPACK gives other fp32 eigenvectors on another CPU, the fixture the same ones
+    everywhere.  Graphs and features are seeded; the stored eigenvalues are checked against this batch's own."""
+    import os
+
+    import numpy as np
+    from signnet_basisnet_amd import synth
+    c = SIZE_CASES[name]
+    data = synth.make_batch(c["B"], seed=c["seed"], n_lo=c["lo"], n_hi=c["hi"], features=c["feat"])
+    z = np.load(os.path.join(G.GOLDEN, "size_cases_eig.npz"), allow_pickle=False)
+    ev, V = torch.from_numpy(z[name + "/eigen_values"]), torch.from_numpy(z[name + "/eigen_vectors"])
+    assert ev.shape == data.eigen_values.shape and V.shape == data.eigen_vectors.shape, name
+    assert (ev - data.eigen_values).abs().max().item() <= 1e-5, f"{name}: the fixture belongs to other graphs"
+    data.eigen_values, data.eigen_vectors = ev, V
+    return data
+
+
 @pytest.mark.parametrize("name", list(SIZE_CASES))
 def test_parameter_gradients_at_baseline_size_vs_oracle_fp32_and_fp64(name):
     """d loss / d theta of a training step AT SIZE against torch.autograd over the fp32 oracle (what the reference's loss.backward()
@@ -452,7 +470,7 @@ def test_parameter_gradients_at_baseline_size_vs_oracle_fp32_and_fp64(name):
     torch.manual_seed(0)
     m = SignNetGNN(*c["ctor"], variant=c["variant"], max_k=c["k"])
     m.attn_dropout = 0.0
-    data = synth.make_batch(c["B"], seed=c["seed"], n_lo=c["lo"], n_hi=c["hi"], features=c["feat"])
+    data = size_case_batch(name)
     cfg = O.make_cfg(c["variant"], *c["ctor"])
     n_out = c["ctor"][3]
     cot = torch.randn(c["B"], n_out, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
