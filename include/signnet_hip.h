@@ -124,6 +124,46 @@ int sn_pack_eig_f32(const float* eigen_vectors, const float* eigen_values, const
                     int K, float* x0, float* s0 /* may be NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bucketed (padded) training batches (train_graph.BucketedStep).  A batch of N nodes, E edges, B graphs and S eigenvector entries is
+ * copied into capacity buffers of N_cap > N, E_cap >= E, B_cap > B, S_cap >= S rows: valid rows first, padding last.  Padding nodes
+ * belong to the spare graph B_cap-1 (graphs [B, B_cap-1) are empty), padding edge E + i is a self-loop on padding node
+ * N + i % (N_cap - N) (spread: no node with hundreds of in-edges), padding features /
+ * eigen data / targets are zero bytes (id 0: a valid embedding row).  node_valid / edge_valid / graph_valid are 0/1 int32 vectors
+ * (nvalid with K = 1 for every masked kernel); counts = [N, E, B, S] on the device.  ONE launch, grid-stride 16-byte copies.
+ * Row sizes in bytes (x, edge_attr, target: any dtype, rows of whole 4-byte words); every array 4-byte aligned. */
+typedef struct sn_bucket_pack_args {
+  const void* x; int64_t x_row_bytes;                 /* [N, ...] */
+  const int64_t* edge_index;                          /* [2, E] */
+  const void* edge_attr; int64_t edge_row_bytes;      /* [E, ...] (row bytes 0: no edge features) */
+  const int64_t* batch;                               /* [N] */
+  const float* eigen_values;                          /* [N] */
+  const float* eigen_vectors;                         /* [S] */
+  const void* target; int64_t target_row_bytes;       /* [B, ...] (row bytes 0: no target) */
+  int64_t N, E, B, S;
+  void* x_out; int64_t* edge_index_out;               /* [N_cap, ...], [2, E_cap] */
+  void* edge_attr_out; int64_t* batch_out;            /* [E_cap, ...], [N_cap] */
+  float* eigen_values_out; float* eigen_vectors_out;  /* [N_cap], [S_cap] */
+  void* target_out;                                   /* [B_cap, ...] */
+  int32_t* node_valid; int32_t* edge_valid; int32_t* graph_valid;   /* [N_cap], [E_cap], [B_cap] */
+  int32_t* counts;                                    /* [4] */
+  int64_t N_cap, E_cap, B_cap, S_cap;
+} sn_bucket_pack_args;
+int sn_bucket_pack(const sn_bucket_pack_args* args, void* stream);
+/* sn_batch_plan_ex over capacity buffers (B = B_cap), then the padding graphs g >= counts[2] (device): nvalid = 0 on their nodes and
+ * empty eigenvector blocks (evoff[g] = evoff[counts[2]] for g > counts[2]).  Padding of sn_bucket_pack raises no malformed-batch flag;
+ * status[1..3] (largest graph, in-degree, fused-stage limits) describe the padded batch.  sn_batch_plan_ex itself is unchanged. */
+int sn_batch_plan_padded(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index, int64_t E,
+                         int kmax, int32_t* graph_ptr, int32_t* node_graph, int32_t* nvalid, int64_t* evoff,
+                         int32_t* rowptr, int32_t* col, int32_t* eperm, int32_t* status,
+                         const sn_plan_bins* bins, int32_t* scratch, const sn_plan_early* early, const int32_t* counts, void* stream);
+/* L1 loss over the valid rows of y / target [R, C]: loss[0] = sum_{valid[r]} |y - t| / (count[0] * C) (count: device int32, e.g.
+ * counts + 2 of sn_bucket_pack); one workgroup, fixed order.  Adjoint: dy = valid[r] ? dloss[0] / (count[0] * C) * sign(y - t) : 0. */
+int sn_masked_l1_f32(const float* y, const float* target, int64_t R, int C, const int32_t* valid, const int32_t* count, float* loss,
+                     void* stream);
+int sn_masked_l1_bwd_f32(const float* y, const float* target, int64_t R, int C, const int32_t* valid, const int32_t* count,
+                         const float* dloss, float* dy, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Weight packing: W [d_out, d_in] (nn.Linear layout, row stride ldw) -> MFMA fragment order
  * Wp[ceil(d_out/16)][ceil(d_in/16)][64 lanes][4], zero padded.  Wp needs
  * sn_packed_weight_floats(d_out, d_in) floats. */

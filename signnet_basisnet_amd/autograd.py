@@ -681,3 +681,38 @@ class _Gated(Function):
 def gated_aggregate(Ah, Bh, Dh, Eh, Ce, plan, rplan):
     """(h, e) of GatedGCN's message passing (gatedgcn_layer.py:51-56); differentiable in all five inputs."""
     return _Gated.apply(Ah, Bh, Dh, Eh, Ce, plan, rplan)
+
+
+class _MaskedL1(Function):
+    """mean |y - t| over the valid rows of a padded batch, divided by the DEVICE row count (train_graph.BucketedStep: the graph count
+    of sn_bucket_pack's count block) — the reference's L1 loss (main_alchemy.py:107, core/train.py:61) with no host value of the
+    batch in it."""
+
+    @staticmethod
+    def forward(ctx, y, target, valid, count):
+        y, target = _c(y), _c(target)
+        R = y.shape[0]
+        Cc = y.numel() // R if R else 1
+        loss = torch.empty((), dtype=torch.float32, device=y.device)
+        with ops._span("sn_masked_l1_f32"):
+            check(lib().sn_masked_l1_f32(ptr(y), ptr(target), R, Cc, ptr(valid), ptr(count), ptr(loss), stream()), "sn_masked_l1_f32")
+        ctx.save_for_backward(y, target)
+        ctx.meta = (valid, count, R, Cc)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        y, target = ctx.saved_tensors
+        valid, count, R, Cc = ctx.meta
+        dy = torch.empty_like(y)
+        with ops._span("sn_masked_l1_bwd_f32"):
+            check(lib().sn_masked_l1_bwd_f32(ptr(y), ptr(target), R, Cc, ptr(valid), ptr(count), ptr(_c(g)), ptr(dy), stream()),
+                  "sn_masked_l1_bwd_f32")
+        return dy, None, None, None
+
+
+def masked_l1_loss(y, target, valid, count):
+    """y, target [R, ...] float32 of one shape; valid int32 [R] (0/1); count int32 [1] on the device."""
+    if y.shape != target.shape:
+        raise ValueError(f"masked_l1_loss: y {tuple(y.shape)} and target {tuple(target.shape)} differ")
+    return _MaskedL1.apply(y, target, valid, count)

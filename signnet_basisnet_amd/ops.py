@@ -216,11 +216,12 @@ def early_supported(N: int, E: int, B: int) -> bool:
 
 
 def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, kmax: int = 0, bins: bool = False,
-               early: "EarlyReport | None" = None, columns: bool = False) -> GraphPlan:
+               early: "EarlyReport | None" = None, columns: bool = False, counts: torch.Tensor = None) -> GraphPlan:
     """bins=True also lays out the work bins of the fused stages (same launch, no host sync).  early: an armed EarlyReport — the
     batch's flags are also written to its pinned buffer by the plan kernel itself (one-launch plans only: early_supported()).
     columns=True: the planner's column arrays (phi_bin_col, phi_col_bin0, phi_col_mem, phi_col_off) are written too — the stage kernels
-    walk the per-bin member records (phi_bin_mem) only, so the forward leaves them out."""
+    walk the per-bin member records (phi_bin_mem) only, so the forward leaves them out.
+    counts: the device count block of a padded batch (sn_bucket_pack): graphs >= counts[2] get no eigenvector slot (sn_batch_plan_padded)."""
     require_cuda(batch, edge_index)
     if batch.dtype != torch.int64 or edge_index.dtype != torch.int64:
         raise ValueError("build_plan: batch and edge_index must be int64 (the reference's index dtype)")
@@ -251,11 +252,19 @@ def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, k
             bc = cb0 = mem = off = None
             cs = _PlanBinsC(None, mb, None, None, None, rb0.data_ptr(), meta.data_ptr(), node_graph.data_ptr(), bmem.data_ptr())
         pb = PlanBins(bc, mb, cb0, mem, off, rb0, meta, cs, bmem)
-    with _span("sn_batch_plan"):
-        check(lib().sn_batch_plan_ex(ptr(batch), N, B, ptr(edge_index), E, int(kmax), ptr(graph_ptr), ptr(node_graph),
-                                     ptr(nvalid), ptr(evoff), ptr(rowptr), ptr(col), ptr(eperm), ptr(status),
-                                     C.byref(pb.cstruct) if pb is not None else None, ptr(scratch),
-                                     C.byref(early.cstruct) if early is not None else None, stream()), "sn_batch_plan")
+    if counts is not None:
+        with _span("sn_batch_plan_padded"):
+            check(lib().sn_batch_plan_padded(ptr(batch), N, B, ptr(edge_index), E, int(kmax), ptr(graph_ptr), ptr(node_graph),
+                                             ptr(nvalid), ptr(evoff), ptr(rowptr), ptr(col), ptr(eperm), ptr(status),
+                                             C.byref(pb.cstruct) if pb is not None else None, ptr(scratch),
+                                             C.byref(early.cstruct) if early is not None else None, ptr(counts), stream()),
+                  "sn_batch_plan_padded")
+    else:
+        with _span("sn_batch_plan"):
+            check(lib().sn_batch_plan_ex(ptr(batch), N, B, ptr(edge_index), E, int(kmax), ptr(graph_ptr), ptr(node_graph),
+                                         ptr(nvalid), ptr(evoff), ptr(rowptr), ptr(col), ptr(eperm), ptr(status),
+                                         C.byref(pb.cstruct) if pb is not None else None, ptr(scratch),
+                                         C.byref(early.cstruct) if early is not None else None, stream()), "sn_batch_plan")
     plan = GraphPlan(N, B, E, int(kmax), graph_ptr, node_graph, nvalid, evoff, rowptr, col, eperm, status, pb)
     plan.flags = arena[offs[7]:offs[7] + 16] if bins else status      # [status(8) | meta(8)] contiguous
     return plan
@@ -1053,3 +1062,50 @@ def _roof_gnn(fl, wl, host, mean_ms, per_step):
 
 KERNEL_ROOFLINE = {"sn_masked_linear_f32": _roof_linear, "sn_phi_fused_f32": _roof_phi, "sn_rho_fused_f32": _roof_rho,
                    "sn_gnn_fused_f32": _roof_gnn}
+
+
+# ----------------------------------------------------------------------------- bucketed (padded) training batches
+class _BucketPackC(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_row_bytes", C.c_int64), ("edge_index", C.c_void_p), ("edge_attr", C.c_void_p),
+                ("edge_row_bytes", C.c_int64), ("batch", C.c_void_p), ("eigen_values", C.c_void_p), ("eigen_vectors", C.c_void_p),
+                ("target", C.c_void_p), ("target_row_bytes", C.c_int64),
+                ("N", C.c_int64), ("E", C.c_int64), ("B", C.c_int64), ("S", C.c_int64),
+                ("x_out", C.c_void_p), ("edge_index_out", C.c_void_p), ("edge_attr_out", C.c_void_p), ("batch_out", C.c_void_p),
+                ("eigen_values_out", C.c_void_p), ("eigen_vectors_out", C.c_void_p), ("target_out", C.c_void_p),
+                ("node_valid", C.c_void_p), ("edge_valid", C.c_void_p), ("graph_valid", C.c_void_p), ("counts", C.c_void_p),
+                ("N_cap", C.c_int64), ("E_cap", C.c_int64), ("B_cap", C.c_int64), ("S_cap", C.c_int64)]
+
+
+def _row_bytes(t):
+    return t.element_size() * (t[0].numel() if t.dim() > 1 else 1)
+
+
+def bucket_pack(data, target, out):
+    """Copy a batch (and its target) of any shape into the capacity buffers `out` (a PaddedBatch of train_graph) in ONE launch
+    (sn_bucket_pack): the padding rows, the node / edge / graph validity vectors and the device count block [N, E, B, S] too."""
+    x, ei, ea, bt = data.x.contiguous(), data.edge_index.contiguous(), data.edge_attr.contiguous(), data.batch.contiguous()
+    ev, es = _f32c(data.eigen_vectors, "eigen_vectors"), _f32c(data.eigen_values, "eigen_values")
+    require_cuda(x, ei, ea, bt, ev, es)
+    N, E, B, S = bt.numel(), (ei.shape[1] if ei.numel() else 0), int(data.num_graphs), ev.numel()
+    for name, src, dst in (("x", x, out.x), ("edge_attr", ea, out.edge_attr), ("batch", bt, out.batch)):
+        if src.dtype != dst.dtype or tuple(src.shape[1:]) != tuple(dst.shape[1:]):
+            raise ValueError(f"bucket_pack: {name} is {src.dtype} {tuple(src.shape)}, the bucket holds {dst.dtype} {tuple(dst.shape)}")
+    if ei.dtype != torch.int64 or ei.dim() != 2 or ei.shape[0] != 2:
+        raise ValueError("bucket_pack: edge_index must be int64 [2, E]")
+    if es.numel() != N or x.shape[0] != N or ea.shape[0] != E:
+        raise ValueError(f"bucket_pack: x / eigen_values / edge_attr rows ({x.shape[0]}, {es.numel()}, {ea.shape[0]}) do not match "
+                         f"N = {N}, E = {E}")
+    t = None
+    if target is not None:
+        t = target.contiguous()
+        if t.dtype != out.target.dtype or t.numel() != B * out.target[0].numel():
+            raise ValueError(f"bucket_pack: target {t.dtype} {tuple(t.shape)} for {B} graphs, the bucket holds rows of "
+                             f"{tuple(out.target.shape[1:])} {out.target.dtype}")
+    a = _BucketPackC(ptr(x), _row_bytes(out.x), ptr(ei), ptr(ea), _row_bytes(out.edge_attr), ptr(bt), ptr(es), ptr(ev),
+                     ptr(t), 0 if t is None else _row_bytes(out.target),
+                     N, E, B, S, ptr(out.x), ptr(out.edge_index), ptr(out.edge_attr), ptr(out.batch), ptr(out.eigen_values),
+                     ptr(out.eigen_vectors), ptr(out.target), ptr(out.node_valid), ptr(out.edge_valid), ptr(out.graph_valid),
+                     ptr(out.counts), out.N_cap, out.E_cap, out.B_cap, out.S_cap)
+    with _span("sn_bucket_pack"):
+        check(lib().sn_bucket_pack(C.byref(a), stream()), "sn_bucket_pack")
+    return N, E, B, S

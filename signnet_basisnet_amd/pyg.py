@@ -658,14 +658,29 @@ class SignNetGNN(nn.Module):
         each wrapped in a torch.autograd.Function whose backward is its hand-written adjoint (autograd.py).  `.backward()`
         on a loss of the result fills `.grad` of every parameter the reference's forward uses (loss.backward() at
         Alchemy/main_alchemy.py:108, GINESignNetPyG/core/train.py:62).  The attention dropout (self.attn_dropout,
-        transformer_module.py:46,55) is an explicit mask drawn once per layer and shared by forward and backward."""
+        transformer_module.py:46,55) is an explicit mask drawn once per layer and shared by forward and backward.
+
+        Under the switch `_bucket` (set only by train_graph.BucketedStep while it runs the model) `data` is a PADDED batch in capacity
+        buffers (ops.bucket_pack): the plan gives the padding graphs no eigenvector slot, K is the bucket's slot capacity, and every op
+        over plain node / edge / graph rows that treats all rows as valid today takes the 0/1 validity vector of the bucket (K = 1), so
+        padding rows enter no batch statistic and no parameter gradient.  Without it every launch and argument is as before."""
         from . import autograd as AG
         ops.require_cuda(data.edge_index, data.batch, data.eigen_vectors)
         sn, g = self.sign_net, self.gnn
         B = int(data.num_graphs)
-        plan = ops.build_plan(data.batch, data.edge_index, B, self.max_k or 0)
+        pad = getattr(self, "_bucket", None)
+        # (padded all-eigenvector batch: slots capped at the bucket's K, which is >= the largest graph when the bucket was chosen by
+        # BucketedStep — the same valid slots as kmax = 0)
+        plan = ops.build_plan(data.batch, data.edge_index, B, self.max_k or (0 if pad is None else int(pad.K)),
+                              counts=None if pad is None else pad.counts)
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, self.max_k or 0)   # out-edge CSR
-        K = int(self.max_k) if self.max_k else plan.check()[1]
+        if pad is None:
+            K = int(self.max_k) if self.max_k else plan.check()[1]
+            vN = vE = vB = None          # node / edge / graph rows: all valid
+            k1 = 0
+        else:
+            K = int(pad.K)
+            vN, vE, vB, k1 = pad.node_valid, pad.edge_valid, pad.graph_valid, 1
         N, nv = plan.N, plan.nvalid
         alchemy_eig = self.variant == "alchemy" and not sn.ignore_eigval
         want_vals = alchemy_eig or self.variant != "alchemy"
@@ -751,14 +766,15 @@ class SignNetGNN(nn.Module):
             z = lin(z, f.w_2)
             x = AG.masked_layernorm(z, y, f.norm.ln.weight, f.norm.ln.bias, LN_EPS, nv, K)
         s = AG.slot_sum(x, N, K, nv)
-        pe = lin_bn(s, sn.rho.out[0], sn.rho.out[1], relu=False)
+        pe = lin_bn(s, sn.rho.out[0], sn.rho.out[1], vN, k1, relu=False)
         # ---- GINE network
         xin = data.x.squeeze() if data.x.dim() > 1 and data.x.shape[-1] == 1 else data.x
         if isinstance(g.input_encoder, DiscreteEncoder):
             h = AG.embedding_sum(xin, [e.weight for e in g.input_encoder.embeddings], plan.status[5:6])
         else:
-            h = lin_bn(xin.contiguous(), g.input_encoder.layers[0], g.input_encoder.norms[0])
-        h = AG.linear(torch.cat([h, pe], dim=-1), g.linear.weight, g.linear.bias)
+            h = lin_bn(xin.contiguous(), g.input_encoder.layers[0], g.input_encoder.norms[0], vN, k1)
+        # (the embedding rows of padding nodes are masked here: their gradient into the tables is exactly 0)
+        h = AG.linear(torch.cat([h, pe], dim=-1), g.linear.weight, g.linear.bias, vN, k1)
         staged = [stage and isinstance(conv.nn.norms[0], nn.BatchNorm1d) and isinstance(norm, nn.BatchNorm1d)
                   for conv, norm in zip(g.convs, g.norms)]
         # every layer embeds the same edge_attr with its own tables: one [L, E, C] block, one adjoint launch pair for all layers
@@ -767,22 +783,25 @@ class SignNetGNN(nn.Module):
             e_all = AG.embedding_sum_layers(data.edge_attr, [[t.weight for t in enc.embeddings] for enc in g.edge_encoders], plan.status[5:6])
         for li, (enc, conv, norm) in enumerate(zip(g.edge_encoders, g.convs, g.norms)):
             if e_all is not None:
-                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li)
+                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li,
+                                 nvalid=vN, K=k1)
                 continue
             if isinstance(enc, DiscreteEncoder):
                 e = AG.embedding_sum(data.edge_attr, [t.weight for t in enc.embeddings], plan.status[5:6])
             else:
-                e = lin_bn(data.edge_attr.contiguous(), enc.layers[0], enc.norms[0])
+                e = lin_bn(data.edge_attr.contiguous(), enc.layers[0], enc.norms[0], vE, k1)
             if staged[li]:
-                h = T.gine_layer(h, e, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan)
+                h = T.gine_layer(h, e, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan,
+                                 nvalid=vN, K=k1)
             else:
                 u = AG.gine_aggregate(h, e, conv.layer.eps, plan, rplan)
-                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0], vN, k1)
+                h = lin_bn(u, conv.nn.layers[1], norm, vN, k1, residual=h)
+        # (padded batch: h is 0 on padding nodes, so the spare graph pools zeros and the empty graphs [B, B_cap-1) pool nothing)
         pooled = AG.segment_pool(h, plan, g.pooling)
         oe = g.output_encoder
-        y = lin_bn(pooled, oe.layers[0], oe.norms[0])
-        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias)
+        y = lin_bn(pooled, oe.layers[0], oe.norms[0], vB, k1)
+        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, vB, k1)
         discrete = isinstance(g.input_encoder, DiscreteEncoder) or any(isinstance(e, DiscreteEncoder) for e in g.edge_encoders)
         self._train_status = plan.status if discrete else None
         if not getattr(self, "_defer_status", False):

@@ -16,6 +16,7 @@ model(data), L1 loss, loss.backward(), optimizer.step().
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 
 import torch
@@ -48,16 +49,7 @@ class GraphedStep:
         # the attention dropout (transformer_module.py:46,55; the one dropout the reference leaves active) is random per step: its masks
         # are drawn OUTSIDE the graph with torch's device generator — the same draws in the same order as the eager step — into static
         # buffers the captured kernels read
-        self._masks = None
-        if getattr(model, "attn_dropout", 0.0):
-            from . import ops
-            from .pyg import N_HEAD
-            N, K = int(data.batch.numel()), int(model.max_k)
-            self._draw = lambda: [ops.attention_dropout_mask(N, K, N_HEAD, model.attn_dropout, data.batch.device)
-                                  for _ in model.sign_net.rho.transformer_layers]
-            st0 = torch.cuda.get_rng_state(data.batch.device)
-            self._masks = [torch.empty_like(m) for m in self._draw()]
-            torch.cuda.set_rng_state(st0, data.batch.device)       # (the sizing draw does not count)
+        self._draw, self._masks = _mask_buffers(model, int(data.batch.numel()), int(model.max_k), data.batch.device)
         self._status = None
 
         def fwd_bwd():
@@ -67,29 +59,7 @@ class GraphedStep:
             loss.backward()
             return loss, y
 
-        # warm-up on a side stream (lazy one-time setup: LDS limits, allocator pools) without touching the model's state
-        saved = [b.detach().clone() for b in model.buffers()]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        rng = torch.cuda.get_rng_state(data.batch.device) if self._masks is not None else None
-        with self._scoped():
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._refresh_masks()
-                    fwd_bwd()
-            torch.cuda.current_stream().wait_stream(side)
-            model.check_train()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                loss, y = fwd_bwd()
-            # the captured forward's status words (static memory of the graph): every replay rewrites them, check() reads them
-            self._status, model._train_status = getattr(model, "_train_status", None), None
-        with torch.no_grad():
-            for b, sv in zip(model.buffers(), saved):
-                b.copy_(sv)
-        if rng is not None:
-            torch.cuda.set_rng_state(rng, data.batch.device)      # the warm-up's draws do not count: the first step draws what an eager one would
-        self.loss, self.y = loss.detach(), y.detach()
+        self.graph, self.loss, self.y, self._status = _capture(self, fwd_bwd, data.batch.device, warmup)
 
     @contextlib.contextmanager
     def _scoped(self):
@@ -141,6 +111,254 @@ class GraphedStep:
         if self.check_every and self._nsteps % self.check_every == 0:
             self.check()
         return self.loss
+
+
+def _mask_buffers(model, N, K, dev):
+    """(draw, static buffers) of the attention-dropout masks [N, H, K, K] per rho layer, or (None, None) without dropout."""
+    if not getattr(model, "attn_dropout", 0.0):
+        return None, None
+    from . import ops
+    from .pyg import N_HEAD
+    draw = lambda: [ops.attention_dropout_mask(N, K, N_HEAD, model.attn_dropout, dev) for _ in model.sign_net.rho.transformer_layers]
+    st0 = torch.cuda.get_rng_state(dev)
+    masks = [torch.empty_like(m) for m in draw()]
+    torch.cuda.set_rng_state(st0, dev)       # (the sizing draw does not count)
+    return draw, masks
+
+
+def _capture(step, fwd_bwd, dev, warmup):
+    """Warm up `fwd_bwd` on a side stream (lazy one-time setup: LDS limits, allocator pools) and capture it, under `step._scoped()`,
+    without touching the model's state: buffers (running statistics, counters) and the generator are restored afterwards.
+    -> (graph, loss, y, the captured forward's status words)."""
+    model = step.model
+    saved = [b.detach().clone() for b in model.buffers()]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    rng = torch.cuda.get_rng_state(dev) if step._masks is not None else None
+    with step._scoped():
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                step._refresh_masks()
+                fwd_bwd()
+        torch.cuda.current_stream().wait_stream(side)
+        model.check_train()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            loss, y = fwd_bwd()
+        # the captured forward's status words (static memory of the graph): every replay rewrites them, check() reads them
+        status, model._train_status = getattr(model, "_train_status", None), None
+    with torch.no_grad():
+        for b, sv in zip(model.buffers(), saved):
+            b.copy_(sv)
+    if rng is not None:
+        torch.cuda.set_rng_state(rng, dev)      # the warm-up's draws do not count: the first step draws what an eager one would
+    return graph, loss.detach(), y.detach(), status
+
+
+# ----------------------------------------------------------------------------- variable-shape batches: one capture per capacity bucket
+class Bucket(tuple):
+    """The capacities of a padded batch: N_cap > N nodes (the spare graph holds >= 1 padding node), E_cap >= E edges, S_cap >= S
+    eigenvector entries, K_cap eigenvector slots per node (max_k, or >= the largest graph in the all-eigenvector mode)."""
+    __slots__ = ()
+    _names = ("N", "E", "S", "K")
+
+    def __new__(cls, N, E, S, K):
+        return tuple.__new__(cls, (int(N), int(E), int(S), int(K)))
+
+    N = property(lambda s: s[0])
+    E = property(lambda s: s[1])
+    S = property(lambda s: s[2])
+    K = property(lambda s: s[3])
+
+    def __repr__(self):
+        return "Bucket(N=%d, E=%d, S=%d, K=%d)" % self
+
+
+def _round_up(v, g):
+    g = max(int(g), 1)
+    return -(-int(v) // g) * g
+
+
+class PaddedBatch:
+    """The static buffers of one bucket: the padded batch the captured step reads (the PyG field names, `num_graphs` = B_cap), the
+    padded target, the 0/1 validity vectors and the device count block [N, E, B, S] (ops.bucket_pack writes all of them)."""
+
+    def __init__(self, bucket, B_cap, data, target, dev):
+        self.N_cap, self.E_cap, self.S_cap, self.K = bucket.N, bucket.E, bucket.S, bucket.K
+        self.B_cap = int(B_cap)
+        z = lambda n, like: torch.zeros((n,) + tuple(like.shape[1:]), dtype=like.dtype, device=dev)
+        self.x = z(self.N_cap, data.x)
+        self.edge_index = torch.zeros(2, self.E_cap, dtype=torch.int64, device=dev)
+        self.edge_attr = z(self.E_cap, data.edge_attr)
+        self.batch = torch.zeros(self.N_cap, dtype=torch.int64, device=dev)
+        self.eigen_values = torch.zeros(self.N_cap, dtype=torch.float32, device=dev)
+        self.eigen_vectors = torch.zeros(self.S_cap, dtype=torch.float32, device=dev)
+        self.target = torch.zeros(self.B_cap, target.numel() // max(int(data.num_graphs), 1), dtype=torch.float32, device=dev)
+        self.node_valid = torch.zeros(self.N_cap, dtype=torch.int32, device=dev)
+        self.edge_valid = torch.zeros(self.E_cap, dtype=torch.int32, device=dev)
+        self.graph_valid = torch.zeros(self.B_cap, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.num_graphs, self.num_nodes = self.B_cap, self.N_cap
+
+
+class _BucketCapture:
+    """One bucket's captured forward + masked L1 + backward (the machinery of GraphedStep: warm-up on a side stream, buffers and
+    generator restored, the switches scoped to the capture) and its own memory pool."""
+
+    def __init__(self, owner, bucket, data, target, warmup):
+        model, optimizer = owner.model, owner.optimizer
+        dev = data.batch.device
+        self.model, self.bucket = model, bucket
+        r0 = torch.cuda.memory_reserved(dev)
+        self.pad = PaddedBatch(bucket, owner.B_cap, data, target, dev)
+        from . import ops
+        ops.bucket_pack(data, target, self.pad)
+        self._draw, self._masks = _mask_buffers(model, bucket.N, bucket.K, dev)
+        self._status = None
+        from .autograd import masked_l1_loss
+        pad = self.pad
+
+        def fwd_bwd():
+            optimizer.flat_g.zero_()
+            y = model(pad)
+            loss = masked_l1_loss(y, pad.target.view_as(y), pad.graph_valid, pad.counts[2:3])
+            loss.backward()
+            return loss, y
+
+        self.graph, self.loss, self.y, self._status = _capture(self, fwd_bwd, dev, warmup)
+        self.memory_reserved = torch.cuda.memory_reserved(dev) - r0
+
+    @contextlib.contextmanager
+    def _scoped(self):
+        m = self.model
+        saved = (getattr(m, "_defer_status", False), getattr(m, "_attn_masks", None), getattr(m, "_bucket", None))
+        m._defer_status, m._attn_masks, m._bucket = True, self._masks, self.pad
+        try:
+            yield
+        finally:
+            m._defer_status, m._attn_masks, m._bucket = saved
+
+    _refresh_masks = GraphedStep._refresh_masks
+    check = GraphedStep.check
+
+
+class BucketedStep:
+    """The captured training step for a real loader: batches of any shape (node count N, edge count E, eigenvector entries S, at most
+    `max_graphs` graphs; max_k fixed or None = all eigenvectors) are padded into fixed-capacity buffers and run through a step captured
+    ONCE per capacity bucket (the reference's loops: Alchemy/main_alchemy.py:99-110, GINESignNetPyG/core/train.py:55-66).
+
+        step = BucketedStep(model, flat_adam, max_graphs=128, granule=dict(N=64, E=128, S=4096, K=8), max_captures=4)
+        loss = step.step(data, target)
+
+    step(): the bucket is chosen on the HOST from tensor shapes (each capacity rounded up to its granule; N_cap >= N + 1, B_cap =
+    max_graphs + 1: the spare graph holds the padding nodes); a new bucket is captured on first use (`captures`), a known one replayed
+    (`hits`); the captures live in an LRU of `max_captures`, each with its own memory pool.  A step is then ONE pack launch
+    (sn_bucket_pack: batch + target + padding + validity + count block), one graph replay and the one Adam launch of optim.FlatAdam.
+    Padding rows enter no batch statistic, no running statistic and no gradient: the losses and gradients are those of the eager step
+    on the unpadded batch (up to summation order), and the padding content cannot change a bit of them.
+
+    All-eigenvector mode (max_k=None): K_cap comes from the largest graph — from host bookkeeping when the batch carries it
+    (pyg.host_max_nodes: data.sizes, PyG's _slice_dict / a CPU ptr); otherwise ONE device read of the largest graph size per step, as
+    the reference itself does (`int(num_nodes.max())`, GINESignNetPyG/core/transform.py:29-38).
+
+    Loss: the reference's L1 (mean |y - target| over the batch's graphs), divided by the device graph count.  Data parallel training is
+    not supported (optimizer.dist must be None)."""
+
+    check_every = 64     # replays between two reads of the status words (0 = only when the caller calls check())
+
+    def __init__(self, model, optimizer, loss="l1", max_graphs=128, granule=None, max_captures=4, warmup=2):
+        from .optim import FlatAdam
+        if not isinstance(optimizer, FlatAdam):
+            raise TypeError("BucketedStep needs optim.FlatAdam (static flat parameter / gradient buffers)")
+        if optimizer.dist is not None:
+            raise ValueError("BucketedStep: data-parallel training (FlatAdam with dist) is not supported; use GraphedStep or the eager step")
+        if loss != "l1":
+            raise ValueError(f"BucketedStep: loss {loss!r} is not supported (only 'l1', the reference's loss)")
+        if int(max_graphs) < 1 or int(max_captures) < 1:
+            raise ValueError("BucketedStep: max_graphs and max_captures must be >= 1")
+        if getattr(model, "variant", None) not in ("gine", "alchemy"):
+            raise TypeError("BucketedStep needs a pyg.SignNetGNN")
+        self.model, self.optimizer = model, optimizer
+        self.max_graphs, self.B_cap = int(max_graphs), int(max_graphs) + 1
+        self.granule = dict(N=64, E=128, S=4096, K=8)
+        for k, v in (granule or {}).items():
+            if k not in self.granule or int(v) < 1:
+                raise ValueError(f"BucketedStep: granule {k}={v} (keys N, E, S, K; values >= 1)")
+            self.granule[k] = int(v)
+        self.max_captures, self.warmup = int(max_captures), int(warmup)
+        self._lru = collections.OrderedDict()       # Bucket -> _BucketCapture, least recently used first
+        self.captures = self.hits = 0
+        self._last, self._nsteps = None, 0
+
+    @property
+    def buckets(self):
+        """The buckets captured now, least recently used first."""
+        return list(self._lru)
+
+    def bucket_of(self, data):
+        """The capacity bucket of a batch (host only, unless max_k is None and the batch has no host-side sizes: one device read)."""
+        B = int(data.num_graphs)
+        if B > self.max_graphs:
+            raise ValueError(f"BucketedStep: a batch of {B} graphs exceeds max_graphs={self.max_graphs}")
+        N = int(data.batch.numel())
+        E = int(data.edge_index.shape[1]) if data.edge_index.numel() else 0
+        S = int(data.eigen_vectors.numel())
+        g = self.granule
+        mk = getattr(self.model, "max_k", None)
+        if mk:
+            K = int(mk)
+        else:
+            from .pyg import host_max_nodes
+            nmax = host_max_nodes(data)
+            if nmax is None:       # (the one allowed device read: the reference's int(num_nodes.max()))
+                nmax = int(torch.bincount(data.batch).max()) if N else 1
+            K = _round_up(max(nmax, 1), g["K"])
+        return Bucket(_round_up(N + 1, g["N"]), _round_up(max(E, 1), g["E"]), _round_up(max(S, 1), g["S"]), K)
+
+    def _admit(self, bucket):
+        """LRU bookkeeping for a bucket about to be used: True if it is captured already."""
+        if bucket in self._lru:
+            self._lru.move_to_end(bucket)
+            return True
+        while len(self._lru) >= self.max_captures:
+            _, old = self._lru.popitem(last=False)
+            if self._last is old:
+                self._last = None
+            old.graph.reset()           # (its private memory pool goes back to the allocator)
+        return False
+
+    def step(self, data, target, bucket=None):
+        """One training step on `data` / `target` ([num_graphs, n_out]): returns the loss (a device scalar, rewritten by the next
+        step of the same bucket).  `bucket`: explicit capacities (Bucket / (N, E, S, K)) instead of the granule rounding."""
+        b = self.bucket_of(data) if bucket is None else Bucket(*bucket)
+        if bucket is not None and int(data.num_graphs) > self.max_graphs:
+            raise ValueError(f"BucketedStep: a batch of {int(data.num_graphs)} graphs exceeds max_graphs={self.max_graphs}")
+        if self._admit(b):
+            cap = self._lru[b]
+            from . import ops
+            ops.bucket_pack(data, target, cap.pad)
+            self.hits += 1
+        else:
+            from . import train_stage
+            train_stage.flush_deferred()      # (nothing of an earlier eager backward may be left for the captured one to reduce)
+            self.model.train()
+            cap = _BucketCapture(self, b, data, target, self.warmup)
+            self._lru[b] = cap
+            self.captures += 1
+        self._last = cap
+        cap._refresh_masks()
+        cap.graph.replay()
+        self.optimizer.step()
+        self._nsteps += 1
+        if self.check_every and self._nsteps % self.check_every == 0:
+            self.check()
+        return cap.loss
+
+    def check(self):
+        """Reads the status words of the LAST replayed step (one host wait): raises IndexError for a discrete feature outside its
+        embedding table, as nn.Embedding does in the reference's eager step."""
+        if self._last is not None:
+            self._last.check()
 
 
 class GraphedForward:

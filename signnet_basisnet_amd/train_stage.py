@@ -584,24 +584,24 @@ class _GineLayer(Function):
     autograd, so the L edge encoders' table gradients are ONE launch pair (no slice / zero-fill / add per layer)."""
 
     @staticmethod
-    def forward(ctx, h, e, eps, W1, b1, g1, be1, W2, b2, g2, be2, lin1, bn1, lin2, bn2, plan, rplan, lidx, gbuf):
+    def forward(ctx, h, e, eps, W1, b1, g1, be1, W2, b2, g2, be2, lin1, bn1, lin2, bn2, plan, rplan, lidx, gbuf, nvalid, K):
         h = _c(h)
         ev = _c(e) if lidx < 0 else e[lidx]
         u = ops.gine_aggregate(h, ev, plan, eps.detach())
-        y, z1, z2, st1, st2 = _mlp2_forward(u, h.shape[0], 1, lin1, bn1, lin2, bn2, None, 0, True, h)
+        y, z1, z2, st1, st2 = _mlp2_forward(u, h.shape[0], 1, lin1, bn1, lin2, bn2, nvalid, K, True, h)
         ctx.save_for_backward(h, ev, u, z1, z2, eps)
         ctx.eps_param = eps
-        ctx.meta = (st1, st2, lin1, bn1, lin2, bn2, rplan, lidx, gbuf)
+        ctx.meta = (st1, st2, lin1, bn1, lin2, bn2, rplan, lidx, gbuf, nvalid, K)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         h, e, u, z1, z2, eps = ctx.saved_tensors
-        st1, st2, lin1, bn1, lin2, bn2, rplan, lidx, gbuf = ctx.meta
+        st1, st2, lin1, bn1, lin2, bn2, rplan, lidx, gbuf, nvalid, K = ctx.meta
         dy = _c(dy)
         N, d = h.shape
         want_eps = ctx.needs_input_grad[2]
-        grads = _mlp2_backward(dy, u, z1, z2, st1, st2, N, 1, lin1, bn1, lin2, bn2, None, 0, True, True, dot_x=h if want_eps else None,
+        grads = _mlp2_backward(dy, u, z1, z2, st1, st2, N, 1, lin1, bn1, lin2, bn2, nvalid, K, True, True, dot_x=h if want_eps else None,
                                dot_acc=direct_grad(ctx.eps_param) if want_eps else None)
         du = grads[0]
         deps = eps_grad(ctx.eps_param) if want_eps else None
@@ -613,16 +613,18 @@ class _GineLayer(Function):
                   "sn_gine_aggregate_bwd_add_f32")
         if lidx >= 0:
             dee = gbuf if lidx == 0 else None
-        return (dh, dee, deps) + grads[1:] + (None,) * 8
+        return (dh, dee, deps) + grads[1:] + (None,) * 10
 
 
-def gine_layer(h, e, conv_eps, lin1, bn1, lin2, bn2, plan, rplan, layer=-1):
-    """layer >= 0: e is the [L, E, C] block of autograd.embedding_sum_layers (see _GineLayer)."""
+def gine_layer(h, e, conv_eps, lin1, bn1, lin2, bn2, plan, rplan, layer=-1, nvalid=None, K=0):
+    """layer >= 0: e is the [L, E, C] block of autograd.embedding_sum_layers (see _GineLayer).  nvalid / K: the node validity of a
+    padded batch (train_graph.BucketedStep: K = 1, 0/1 per node) — batch statistics, dW and eps sums over the valid nodes only, the
+    output and the input gradient 0 on the others; None: every node is valid."""
     gbuf = getattr(e, "_sn_gbuf", None) if layer >= 0 else None
     if layer >= 0 and gbuf is None:
         raise ValueError("gine_layer: a layer index needs the block of embedding_sum_layers")
     return _GineLayer.apply(h, e, conv_eps, lin1.weight, lin1.bias, bn1.weight, bn1.bias, lin2.weight, lin2.bias, bn2.weight, bn2.bias,
-                            lin1, bn1, lin2, bn2, plan, rplan, layer, gbuf)
+                            lin1, bn1, lin2, bn2, plan, rplan, layer, gbuf, nvalid, K)
 
 
 def mlp2_bn(x, lin1, bn1, lin2, bn2, nvalid=None, K=0, G=1, residual=None, relu_out=True):
