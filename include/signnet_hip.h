@@ -149,6 +149,33 @@ typedef struct sn_bucket_pack_args {
   int64_t N_cap, E_cap, B_cap, S_cap;
 } sn_bucket_pack_args;
 int sn_bucket_pack(const sn_bucket_pack_args* args, void* stream);
+/* The same for a DGL batch (train_graph.DGLBucketedStep: the loop body of GraphPrediction/train/train_ZINC_graph_regression.py:60-82,
+ * one batch of main_ZINC_graph_regression.py's loader per step), same padding convention.  Copies src / dst [E], the atom ids h [N],
+ * the bond ids e [E] (e_out NULL: none), pos_enc p [N, K], snorm_n [N] (snorm_n_out NULL: none) and the targets [B] into [E_cap],
+ * [N_cap], [E_cap], [N_cap, K], [N_cap], [B_cap]; writes batch_num_nodes_out [B_cap] = the B real node counts, 0 for the empty graphs,
+ * N_cap - N for the spare graph (they sum to N_cap: the node -> graph vector is rebuilt from them on the device), the 0/1 node / edge /
+ * graph validity, node_slots [N_cap] = K on valid nodes, 0 on padding nodes (nvalid of the N_cap * K slot rows) and counts = [N, E, B].
+ * Node counts that are negative, above N or do not sum to N (a batch_num_nodes() inconsistent with the N feature rows) are replaced by
+ * ONE graph of N_cap nodes, so that the padded counts always total N_cap, and count_error[0] = 1 (else 0).  ONE launch. */
+typedef struct sn_bucket_pack_dgl_args {
+  const int64_t* src; const int64_t* dst;             /* [E] */
+  const int64_t* h; const int64_t* e;                 /* [N], [E] */
+  const float* p; const float* snorm_n;               /* [N, K], [N] */
+  const float* target;                                /* [B] */
+  const int64_t* batch_num_nodes;                     /* [B] */
+  int64_t N, E, B, K;
+  int64_t* src_out; int64_t* dst_out;                 /* [E_cap] */
+  int64_t* h_out; int64_t* e_out;                     /* [N_cap], [E_cap] */
+  float* p_out; float* snorm_n_out;                   /* [N_cap, K], [N_cap] */
+  float* target_out;                                  /* [B_cap] */
+  int64_t* batch_num_nodes_out;                       /* [B_cap] */
+  int32_t* node_valid; int32_t* edge_valid; int32_t* graph_valid;   /* [N_cap], [E_cap], [B_cap] */
+  int32_t* node_slots;                                /* [N_cap] */
+  int32_t* counts;                                    /* [3] */
+  int32_t* count_error;                               /* [1] */
+  int64_t N_cap, E_cap, B_cap;
+} sn_bucket_pack_dgl_args;
+int sn_bucket_pack_dgl(const sn_bucket_pack_dgl_args* args, void* stream);
 /* sn_batch_plan_ex over capacity buffers (B = B_cap), then the padding graphs g >= counts[2] (device): nvalid = 0 on their nodes and
  * empty eigenvector blocks (evoff[g] = evoff[counts[2]] for g > counts[2]).  Padding of sn_bucket_pack raises no malformed-batch flag;
  * status[1..3] (largest graph, in-degree, fused-stage limits) describe the padded batch.  sn_batch_plan_ex itself is unchanged. */

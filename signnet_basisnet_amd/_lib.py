@@ -31,6 +31,7 @@ SIGNATURES = {
     "sn_batch_plan_early_supported": [_l, _l, _l],                # (returns 0 / 1, not a status)
     "sn_pack_eig_f32": [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p],
     "sn_bucket_pack": [_p, _p],
+    "sn_bucket_pack_dgl": [_p, _p],
     "sn_batch_plan_padded": [_p, _l, _l, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_masked_l1_f32": [_p, _p, _l, _i, _p, _p, _p, _p],
     "sn_masked_l1_bwd_f32": [_p, _p, _l, _i, _p, _p, _p, _p, _p],

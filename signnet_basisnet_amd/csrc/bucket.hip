@@ -2,7 +2,9 @@
 //
 //   sn_bucket_pack        : ONE launch copies a batch of any shape into the capacity buffers of its bucket and writes the padding, the
 //                           0/1 validity vectors (node, edge, graph) and the device count block [N, E, B, S].
-//   sn_batch_plan_padded  : sn_batch_plan_ex, then the padding graphs (id >= counts[2]) get nvalid = 0 and empty eigenvector blocks.
+//   sn_bucket_pack_dgl    : the same for a DGL batch (train_graph.DGLBucketedStep): edge list, atom / bond ids, pos_enc, snorm_n,
+//                           targets, the padded per-graph node counts, the validity vectors, the node-slot vector and [N, E, B].
+//   sn_batch_plan_padded: sn_batch_plan_ex, then the padding graphs (id >= counts[2]) get nvalid = 0 and empty eigenvector blocks.
 //   sn_masked_l1_f32 / _bwd_f32 : mean |y - t| over the valid rows, divided by the device row count; its adjoint.
 //
 // Padding convention: valid rows first; padding nodes belong to the spare graph B_cap-1; graphs [B, B_cap-1) are empty; padding edges
@@ -28,16 +30,59 @@ struct PackSeg {
   int64_t spread;          // > 0 (edge endpoints, int64): padding element i gets fill_lo + (i - ncopy / 2) % spread instead
 };
 
+// The per-graph node counts of a DGL batch, padded to B_cap (sn_bucket_pack_dgl): the B real counts, 0 for the empty graphs,
+// N_cap - N for the spare graph.  The node -> graph vector is rebuilt from them on the device (repeat_interleave with
+// output_size = N_cap), which is only in bounds if they total N_cap: counts that are negative, above N or do not sum to N (a
+// batch_num_nodes() inconsistent with the feature rows) are replaced by ONE graph holding all N_cap nodes and flagged in `error`
+// (train_graph.DGLBucketedStep.check() raises the eager step's ValueError).
+struct NodeCountJob {
+  const int64_t* src;      // [B]
+  int64_t* dst;            // [B_cap]; NULL: no job (sn_bucket_pack)
+  int32_t* error;          // [1]
+  int64_t B, Bc, N, Nc;
+};
+
 struct PackTab {
   PackSeg s[PACK_SEGS];
   int n;
+  int ncnt;                // words of the count block: 4 ([N, E, B, S]) or 3 ([N, E, B])
   int64_t chunks;
   int32_t* counts;
   int32_t cnt[4];
+  NodeCountJob nc;
 };
 
+// one workgroup: sum and range check of the B counts (fixed order), then the padded counts
+__device__ void pack_node_counts(const NodeCountJob& j) {
+  __shared__ int64_t s_sum[PACK_T];
+  __shared__ int s_bad[PACK_T];
+  const int t = threadIdx.x;
+  int64_t sum = 0;
+  int bad = 0;
+  for (int64_t i = t; i < j.B; i += PACK_T) {
+    const int64_t v = j.src[i];
+    bad |= (v < 0) | (v > j.N);          // (each count <= N: the sum of B < 2^31 of them cannot overflow)
+    sum += v;
+  }
+  s_sum[t] = sum;
+  s_bad[t] = bad;
+  __syncthreads();
+  for (int w = PACK_T / 2; w > 0; w >>= 1) {
+    if (t < w) {
+      s_sum[t] += s_sum[t + w];
+      s_bad[t] |= s_bad[t + w];
+    }
+    __syncthreads();
+  }
+  const bool ok = !s_bad[0] && s_sum[0] == j.N;
+  for (int64_t i = t; i < j.Bc; i += PACK_T)
+    j.dst[i] = i == j.Bc - 1 ? (ok ? j.Nc - j.N : j.Nc) : (ok && i < j.B ? j.src[i] : 0);
+  if (t == 0) j.error[0] = ok ? 0 : 1;
+}
+
 __global__ __launch_bounds__(PACK_T) void k_bucket_pack(const PackTab tab) {
-  if (blockIdx.x == 0 && threadIdx.x < 4) tab.counts[threadIdx.x] = tab.cnt[threadIdx.x];
+  if (blockIdx.x == 0 && (int)threadIdx.x < tab.ncnt) tab.counts[threadIdx.x] = tab.cnt[threadIdx.x];
+  if (blockIdx.x == 0 && tab.nc.dst) pack_node_counts(tab.nc);
   for (int64_t c = (int64_t)blockIdx.x * PACK_T + threadIdx.x; c < tab.chunks; c += (int64_t)gridDim.x * PACK_T) {
     int k = 0;
 #pragma unroll
@@ -113,15 +158,15 @@ __global__ __launch_bounds__(256) void k_masked_l1_bwd(const float* __restrict__
 
 using namespace sn;
 
-static int add_seg(PackTab& tb, const void* src, void* dst, int64_t ncopy_bytes, int64_t ntot_bytes, uint32_t val, uint32_t lo,
-                   uint32_t hi, int64_t spread = 0) {
-  SN_REQUIRE(tb.n < PACK_SEGS, "sn_bucket_pack: too many segments");
+static int add_seg(PackTab& tb, const char* who, const void* src, void* dst, int64_t ncopy_bytes, int64_t ntot_bytes, uint32_t val,
+                   uint32_t lo, uint32_t hi, int64_t spread = 0) {
+  SN_REQUIRE(tb.n < PACK_SEGS, "%s: too many segments", who);
   SN_REQUIRE(ncopy_bytes % 4 == 0 && ntot_bytes % 4 == 0 && ncopy_bytes >= 0 && ncopy_bytes <= ntot_bytes,
-             "sn_bucket_pack: segment of %lld bytes into %lld (rows must be whole 4-byte words and fit the capacity)",
+             "%s: segment of %lld bytes into %lld (rows must be whole 4-byte words and fit the capacity)", who,
              (long long)ncopy_bytes, (long long)ntot_bytes);
-  SN_REQUIRE(ntot_bytes == 0 || dst, "sn_bucket_pack: null capacity buffer");
+  SN_REQUIRE(ntot_bytes == 0 || dst, "%s: null capacity buffer", who);
   SN_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0 && (ncopy_bytes == 0 || (reinterpret_cast<uintptr_t>(src) & 3) == 0),
-             "sn_bucket_pack: arrays must be 4-byte aligned");
+             "%s: arrays must be 4-byte aligned", who);
   if (ntot_bytes == 0) return SN_OK;
   PackSeg& s = tb.s[tb.n++];
   s.src = static_cast<const uint32_t*>(src);
@@ -145,6 +190,14 @@ static int add_seg(PackTab& tb, const void* src, void* dst, int64_t ncopy_bytes,
     if (rc__ != SN_OK) return rc__; \
   } while (0)
 
+static int launch_pack(const PackTab& tb, void* stream, const char* who) {
+  int64_t blocks = cdiv(tb.chunks > 0 ? tb.chunks : 1, PACK_T);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(k_bucket_pack, dim3((unsigned)blocks), dim3(PACK_T), 0, (hipStream_t)stream, tb);
+  SN_CHECK_LAUNCH(who);
+  return SN_OK;
+}
+
 extern "C" int sn_bucket_pack(const sn_bucket_pack_args* a, void* stream) {
   SN_REQUIRE(a, "sn_bucket_pack: null args");
   const int64_t N = a->N, E = a->E, B = a->B, S = a->S, Nc = a->N_cap, Ec = a->E_cap, Bc = a->B_cap, Sc = a->S_cap;
@@ -161,31 +214,69 @@ extern "C" int sn_bucket_pack(const sn_bucket_pack_args* a, void* stream) {
   SN_REQUIRE(a->batch_out && a->eigen_values_out && a->node_valid && a->graph_valid && a->counts && (Ec == 0 || (a->edge_index_out && a->edge_valid)),
              "sn_bucket_pack: null capacity buffer");
   PackTab tb{};
+  const char* who = "sn_bucket_pack";
   // padding edge i (0-based) is a self-loop on padding node N + i % (N_cap - N): spread over the padding nodes, never hundreds of
   // in-edges on one node (the aggregations walk a node's in-edges serially: one node with 250 self-loops was a 0.3 ms tail per step)
   const uint32_t pad_node = (uint32_t)N, pad_graph = (uint32_t)(Bc - 1);
-  SN_TRY(add_seg(tb, a->x, a->x_out, N * a->x_row_bytes, Nc * a->x_row_bytes, 0, 0, 0));
-  SN_TRY(add_seg(tb, a->edge_index, a->edge_index_out, 8 * E, 8 * Ec, 0, pad_node, 0, Nc - N));
-  SN_TRY(add_seg(tb, a->edge_index ? a->edge_index + E : nullptr, a->edge_index_out ? a->edge_index_out + Ec : nullptr, 8 * E, 8 * Ec, 0,
-                 pad_node, 0, Nc - N));
-  SN_TRY(add_seg(tb, a->edge_attr, a->edge_attr_out, E * a->edge_row_bytes, Ec * a->edge_row_bytes, 0, 0, 0));
-  SN_TRY(add_seg(tb, a->batch, a->batch_out, 8 * N, 8 * Nc, 0, pad_graph, 0));
-  SN_TRY(add_seg(tb, a->eigen_values, a->eigen_values_out, 4 * N, 4 * Nc, 0, 0, 0));
-  SN_TRY(add_seg(tb, a->eigen_vectors, a->eigen_vectors_out, 4 * S, 4 * Sc, 0, 0, 0));
-  SN_TRY(add_seg(tb, a->target, a->target_out, B * a->target_row_bytes, Bc * a->target_row_bytes, 0, 0, 0));
-  SN_TRY(add_seg(tb, nullptr, a->node_valid, 4 * N, 4 * Nc, 1u, 0, 0));
-  SN_TRY(add_seg(tb, nullptr, a->edge_valid, 4 * E, 4 * Ec, 1u, 0, 0));
-  SN_TRY(add_seg(tb, nullptr, a->graph_valid, 4 * B, 4 * Bc, 1u, 0, 0));
+  SN_TRY(add_seg(tb, who, a->x, a->x_out, N * a->x_row_bytes, Nc * a->x_row_bytes, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, a->edge_index, a->edge_index_out, 8 * E, 8 * Ec, 0, pad_node, 0, Nc - N));
+  SN_TRY(add_seg(tb, who, a->edge_index ? a->edge_index + E : nullptr, a->edge_index_out ? a->edge_index_out + Ec : nullptr, 8 * E, 8 * Ec,
+                 0, pad_node, 0, Nc - N));
+  SN_TRY(add_seg(tb, who, a->edge_attr, a->edge_attr_out, E * a->edge_row_bytes, Ec * a->edge_row_bytes, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, a->batch, a->batch_out, 8 * N, 8 * Nc, 0, pad_graph, 0));
+  SN_TRY(add_seg(tb, who, a->eigen_values, a->eigen_values_out, 4 * N, 4 * Nc, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, a->eigen_vectors, a->eigen_vectors_out, 4 * S, 4 * Sc, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, a->target, a->target_out, B * a->target_row_bytes, Bc * a->target_row_bytes, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->node_valid, 4 * N, 4 * Nc, 1u, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->edge_valid, 4 * E, 4 * Ec, 1u, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->graph_valid, 4 * B, 4 * Bc, 1u, 0, 0));
   tb.counts = a->counts;
+  tb.ncnt = 4;
   tb.cnt[0] = (int32_t)N;
   tb.cnt[1] = (int32_t)E;
   tb.cnt[2] = (int32_t)B;
   tb.cnt[3] = (int32_t)S;
-  int64_t blocks = cdiv(tb.chunks > 0 ? tb.chunks : 1, PACK_T);
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(k_bucket_pack, dim3((unsigned)blocks), dim3(PACK_T), 0, (hipStream_t)stream, tb);
-  SN_CHECK_LAUNCH("sn_bucket_pack");
-  return SN_OK;
+  return launch_pack(tb, stream, who);
+}
+
+extern "C" int sn_bucket_pack_dgl(const sn_bucket_pack_dgl_args* a, void* stream) {
+  SN_REQUIRE(a, "sn_bucket_pack_dgl: null args");
+  const int64_t N = a->N, E = a->E, B = a->B, K = a->K, Nc = a->N_cap, Ec = a->E_cap, Bc = a->B_cap;
+  SN_REQUIRE(N >= 0 && E >= 0 && B >= 0 && K >= 0, "sn_bucket_pack_dgl: negative size");
+  SN_REQUIRE(N < Nc && E <= Ec && B < Bc, "sn_bucket_pack_dgl: batch (N %lld, E %lld, B %lld) does not fit the bucket "
+             "(N_cap %lld > N, E_cap %lld, B_cap %lld > B)", (long long)N, (long long)E, (long long)B, (long long)Nc, (long long)Ec,
+             (long long)Bc);
+  SN_REQUIRE(Nc < (1ll << 31) && Ec < (1ll << 31) && Bc < (1ll << 31) && K < (1ll << 31) && Nc * K < (1ll << 40),
+             "sn_bucket_pack_dgl: capacities exceed int32");
+  SN_REQUIRE((E == 0 || (a->src && a->dst)) && (N == 0 || (a->h && (K == 0 || a->p))) && (B == 0 || (a->target && a->batch_num_nodes)) &&
+             (E == 0 || !a->e_out || a->e) && (N == 0 || !a->snorm_n_out || a->snorm_n),
+             "sn_bucket_pack_dgl: null source array");
+  SN_REQUIRE(a->h_out && (K == 0 || a->p_out) && a->target_out && a->batch_num_nodes_out && a->node_valid && a->graph_valid && a->node_slots &&
+             a->counts && a->count_error && (Ec == 0 || (a->src_out && a->dst_out && a->edge_valid)),
+             "sn_bucket_pack_dgl: null capacity buffer");
+  PackTab tb{};
+  const char* who = "sn_bucket_pack_dgl";
+  const uint32_t pad_node = (uint32_t)N;
+  // the padding convention of sn_bucket_pack: padding edge E + i is a self-loop on padding node N + i % (N_cap - N)
+  SN_TRY(add_seg(tb, who, a->src, a->src_out, 8 * E, 8 * Ec, 0, pad_node, 0, Nc - N));
+  SN_TRY(add_seg(tb, who, a->dst, a->dst_out, 8 * E, 8 * Ec, 0, pad_node, 0, Nc - N));
+  SN_TRY(add_seg(tb, who, a->h, a->h_out, 8 * N, 8 * Nc, 0, 0, 0));
+  if (a->e_out) SN_TRY(add_seg(tb, who, a->e, a->e_out, 8 * E, 8 * Ec, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, a->p, a->p_out, 4 * N * K, 4 * Nc * K, 0, 0, 0));
+  if (a->snorm_n_out) SN_TRY(add_seg(tb, who, a->snorm_n, a->snorm_n_out, 4 * N, 4 * Nc, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, a->target, a->target_out, 4 * B, 4 * Bc, 0, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->node_valid, 4 * N, 4 * Nc, 1u, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->edge_valid, 4 * E, 4 * Ec, 1u, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->graph_valid, 4 * B, 4 * Bc, 1u, 0, 0));
+  SN_TRY(add_seg(tb, who, nullptr, a->node_slots, 4 * N, 4 * Nc, (uint32_t)K, 0, 0));
+  // per-graph node counts: the B real ones, 0 for the empty graphs [B, B_cap-1), N_cap - N for the spare graph (workgroup 0)
+  tb.nc = NodeCountJob{a->batch_num_nodes, a->batch_num_nodes_out, a->count_error, B, Bc, N, Nc};
+  tb.counts = a->counts;
+  tb.ncnt = 3;
+  tb.cnt[0] = (int32_t)N;
+  tb.cnt[1] = (int32_t)E;
+  tb.cnt[2] = (int32_t)B;
+  return launch_pack(tb, stream, who);
 }
 
 extern "C" int sn_batch_plan_padded(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index, int64_t E, int kmax,

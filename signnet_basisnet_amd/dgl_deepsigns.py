@@ -291,6 +291,17 @@ def _max_in_edges(g):
     return me
 
 
+def _bucket_rows(mod):
+    """Row validity of a PADDED batch while train_graph.DGLBucketedStep runs the module (its switch `_bucket`, set only during the
+    step's warm-up and capture): (node, edge, graph) 0/1 vectors and K = 1 — the nvalid, K every op over plain node / edge / graph rows
+    takes, so padding rows enter no batch statistic and no parameter gradient.  Without the switch (None, None, None, 0): all rows
+    valid, every launch as it was."""
+    pad = getattr(mod, "_bucket", None)
+    if pad is None:
+        return None, None, None, 0
+    return pad.node_valid, pad.edge_valid, pad.graph_valid, 1
+
+
 def _await_side(g, plan=None):
     """The sign-invariant net may have built this graph's plan — and its own output — on its side stream (`overlap = True`): whoever picks
     the plan up on another stream first waits for that stream's event there and tells the allocator (once per graph object)."""
@@ -373,7 +384,8 @@ class _DeepSignsBase(nn.Module):
             P["gin"].append(dict(eps=conv.eps, mlp=_prep_mlp(conv.apply_func, train), next_bn=nxt))
         return P
 
-    def _plan(self, g, N, fused=False):
+    def _plan(self, g, N, fused=False, counts=None):
+        """counts: the device count block of a padded batch (train_graph.DGLBucketedStep): its padding graphs get no slot."""
         src, dst = g.edges()
         bnn = g.batch_num_nodes().to(src.device)
         B = int(bnn.numel())
@@ -384,7 +396,7 @@ class _DeepSignsBase(nn.Module):
         batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)      # index plumbing only
         if fused:     # kmax = -k: work bins over all k slots of every graph (zero-padded columns are evaluated like any other)
             return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, -self.k, bins=True)
-        return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, self.k)
+        return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, self.k, counts=counts)
 
     def _phi(self, P, plan, x, N, K, train=False):
         """enc(g, x) + enc(g, -x): GIN.forward, gnns.py:102-114, twice."""
@@ -401,22 +413,31 @@ class _DeepSignsBase(nn.Module):
         """Differentiable train-mode forward: the same launches as the value path, recorded as
         torch.autograd.Function nodes whose backward are the hand-written adjoints of csrc/backward.hip, so that the
         gradient a DGL base network sends back into `p = sign_inv_net(g, pos_enc)` (train_ZINC_graph_regression.py:20-25)
-        reaches these parameters.  Dropout is not applied (the shipped configs use 0.0)."""
+        reaches these parameters.  Dropout is not applied (the shipped configs use 0.0).
+
+        Under the switch `_bucket` (train_graph.DGLBucketedStep) `g` is a PADDED batch: the plan gives the padding graphs no slot
+        (sn_batch_plan_padded), the ops over the N*K slot rows take the node-slot vector (K on valid nodes, 0 on padding nodes: every
+        slot of a valid node counts, as in the reference's BatchNorm over all rows), those over the N rows of rho the node validity."""
         from . import autograd as AG
         N, K = x.shape[0], self.k
-        plan = self._plan(g, N)
+        pad = getattr(self, "_bucket", None)
+        plan = self._plan(g, N, counts=None if pad is None else pad.counts)
         src, dst = g.edges()
-        rplan = self._plan(Graph(dst, src, g.batch_num_nodes()), N)              # out-edge CSR for the aggregation adjoint
+        rg = Graph(dst, src, g.batch_num_nodes())
+        rg._sn_node_counts = _node_counts(g)           # (the same batch: its node counts are not read back a second time)
+        rplan = self._plan(rg, N)                                                # out-edge CSR for the aggregation adjoint
         enc = self.enc
+        sv, sk = (None, 0) if pad is None else (pad.node_slots, K)               # the N*K slot rows
+        vN, _, _, k1 = _bucket_rows(self)                                        # the N rows of rho
 
-        def run_mlp(mlp, h, tail_bn=None):
+        def run_mlp(mlp, h, tail_bn=None, nv=None, kv=0):
             n = len(mlp.lins)
             for i, lin in enumerate(mlp.lins):
                 last = i == n - 1
-                h = AG.linear(h, lin.weight, lin.bias, relu=not last)             # mlp.py:40-46: bias -> relu -> BN
+                h = AG.linear(h, lin.weight, lin.bias, nv, kv, relu=not last)     # mlp.py:40-46: bias -> relu -> BN
                 bn = tail_bn if last else (mlp.bns[i] if mlp.use_bn else None)
                 if bn is not None:
-                    h = AG.bn_act(h, bn, relu=False)                               # statistics over ALL rows, as the reference
+                    h = AG.bn_act(h, bn, nv, kv, relu=False)                       # statistics over ALL rows, as the reference
             return h
 
         outs = []
@@ -426,14 +447,14 @@ class _DeepSignsBase(nn.Module):
             h = x
             for l, conv in enumerate(enc.layers):
                 a = AG.gin_aggregate(h.reshape(N, -1), conv.eps, plan, rplan, negate=(sign == 1 and l == 0))
-                h = run_mlp(conv.apply_func, a.view(N * K, -1), enc.bns[l] if (enc.use_bn and l < L - 1) else None)
+                h = run_mlp(conv.apply_func, a.view(N * K, -1), enc.bns[l] if (enc.use_bn and l < L - 1) else None, sv, sk)
             outs.append(h)
         if self.masked:
             z = AG.masked_add(outs[0], outs[1], plan.nvalid, K)
-            y = run_mlp(self.rho, AG.slot_sum(z, N, K, plan.nvalid))
+            y = run_mlp(self.rho, AG.slot_sum(z, N, K, plan.nvalid), nv=vN, kv=k1)
         else:
-            z = AG.masked_add(outs[0], outs[1])
-            y = run_mlp(self.rho, z.view(N, -1))
+            z = AG.masked_add(outs[0], outs[1], sv, sk)
+            y = run_mlp(self.rho, z.view(N, -1), nv=vN, kv=k1)
         return y.view(N, K, 1)
 
     def _phi_eval_merged(self, P, plan, x, N, K):

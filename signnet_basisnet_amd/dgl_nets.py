@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import check, lib, ptr, stream
-from .dgl_deepsigns import MLP, cached_plan, _await_side, _max_nodes, _max_in_edges, _node_counts, _BNSite, _GINConv, _pack, _prep_mlp, _run_mlp, get_sign_inv_net
+from .dgl_deepsigns import MLP, cached_plan, _await_side, _bucket_rows, _max_nodes, _max_in_edges, _node_counts, _BNSite, _GINConv, _pack, _prep_mlp, _run_mlp, get_sign_inv_net
 
 
 class MLPReadout(nn.Module):
@@ -356,22 +356,23 @@ class GINNet(_PackCache, nn.Module):
 
     def _forward_grad(self, plan, batch, ei, B, hidx, p):
         from . import autograd as AG
+        vN, _, vB, k1 = _bucket_rows(self)          # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias), x)
+        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), x, vN, k1)
         for conv in self.layers:
             mlp = conv.apply_func
             a = AG.gin_aggregate(x, conv.eps, plan, rplan)
             n = len(mlp.lins)
             for i, lin in enumerate(mlp.lins):
-                a = AG.linear(a, lin.weight, lin.bias, relu=i < n - 1)
+                a = AG.linear(a, lin.weight, lin.bias, vN, k1, relu=i < n - 1)
                 if mlp.use_bn and i < n - 1:
-                    a = AG.bn_act(a, mlp.bns[i], relu=False)
+                    a = AG.bn_act(a, mlp.bns[i], vN, k1, relu=False)
             x = a
         hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, relu=i < len(fcs) - 1)
+            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         return hg
 
     def loss(self, scores, targets):
@@ -650,24 +651,25 @@ class GatedGCNNet(_PackCache, nn.Module):
 
     def _forward_grad(self, plan, batch, ei, B, hidx, p, eidx):
         from . import autograd as AG
+        vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias)
+        pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
         if self.pe_aggregate == "concat":
-            x = AG.linear(torch.cat([x, pp], dim=1), self.pe_proj.weight, self.pe_proj.bias)
+            x = AG.linear(torch.cat([x, pp], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
         else:
-            x = AG.masked_add(pp, x)
+            x = AG.masked_add(pp, x, vN, k1)
         e = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
-            Ah, Bh, Dh, Eh = (AG.linear(x, getattr(L, n).weight, getattr(L, n).bias) for n in "ABDE")
-            Ce = AG.linear(e, L.C.weight, L.C.bias)
+            Ah, Bh, Dh, Eh = (AG.linear(x, getattr(L, n).weight, getattr(L, n).bias, vN, k1) for n in "ABDE")
+            Ce = AG.linear(e, L.C.weight, L.C.bias, vE, k1)
             h2, e2 = AG.gated_aggregate(Ah, Bh, Dh, Eh, Ce, plan, rplan)
-            x = AG.bn_act(h2, L.bn_node_h, relu=True, residual=x if L.residual else None)
-            e = AG.bn_act(e2, L.bn_node_e, relu=True, residual=e if L.residual else None)
+            x = AG.bn_act(h2, L.bn_node_h, vN, k1, relu=True, residual=x if L.residual else None)
+            e = AG.bn_act(e2, L.bn_node_e, vE, k1, relu=True, residual=e if L.residual else None)
         hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, relu=i < len(fcs) - 1)
+            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         return hg
 
     def loss(self, scores, targets):
@@ -937,9 +939,11 @@ class PNANet(_PackCache, nn.Module):
         """Differentiable train-mode forward (SURVEY.md §8 f1 for this net): the same ops as autograd nodes with hand-written adjoints
         (csrc/dgl_layers.hip: CSR walks, no atomics); towers' column slices and concatenations are torch views / copies."""
         from . import autograd as AG
+        vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE: adjoint of h[src]
         src, dst = ei[0], ei[1]
-        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias), AG.embedding_sum(hidx, [self.embedding_h.weight]))
+        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), AG.embedding_sum(hidx, [self.embedding_h.weight]),
+                          vN, k1)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             it = L.in_dim // L.n_towers
@@ -948,17 +952,17 @@ class PNANet(_PackCache, nn.Module):
                 ht = x[:, t * it:(t + 1) * it].contiguous()
                 z = torch.cat([AG.gather_rows(ht, src, rplan), AG.gather_rows(ht, dst, plan), ef], dim=1)
                 pre, post = T.pretrans_h.fully_connected[0].linear, T.posttrans_h.fully_connected[0].linear
-                m = AG.linear(z, pre.weight, pre.bias)
+                m = AG.linear(z, pre.weight, pre.bias, vE, k1)
                 a = AG.pna_aggregate(m, ht, plan, avg_log)
-                y = AG.act_residual(AG.linear(a, post.weight, post.bias), rowscale=sn)             # graph_norm: h * snorm_n
-                outs.append(AG.bn_act(y, T.batchnorm_h, relu=False))
+                y = AG.act_residual(AG.linear(a, post.weight, post.bias, vN, k1), rowscale=sn)     # graph_norm: h * snorm_n
+                outs.append(AG.bn_act(y, T.batchnorm_h, vN, k1, relu=False))
             mixl = L.mixing_network_h.linear
-            mix = AG.linear(torch.cat(outs, dim=1), mixl.weight, mixl.bias)
+            mix = AG.linear(torch.cat(outs, dim=1), mixl.weight, mixl.bias, vN, k1)
             x = AG.act_residual(mix, residual=x if L.residual else None, act="leaky", slope=0.01)
         hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, relu=i < len(fcs) - 1)
+            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         self._h_last = x.detach()
         return hg
 
@@ -1225,27 +1229,29 @@ class TransformerNet(_PackCache, nn.Module):
         """Differentiable train-mode forward: the sparse attention's adjoint is sn_edge_attention_bwd_f32 (destination pass + source
         pass over the reverse CSR, no atomics); BatchNorm with batch statistics, residuals, FFN as in the value path."""
         from . import autograd as AG
+        vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        pe = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias)
+        pe = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
         if self.pe_aggregate == "concat":
-            x = AG.linear(torch.cat([x, pe], dim=1), self.pe_proj.weight, self.pe_proj.bias)
+            x = AG.linear(torch.cat([x, pe], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
         else:
-            x = AG.masked_add(pe, x)
+            x = AG.masked_add(pe, x, vN, k1)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             A = L.attention_h
-            Q, K, V = (AG.linear(x, getattr(A, n).weight, None) for n in "QKV")
-            Ee = AG.linear(ef, A.E.weight, None)
+            Q, K, V = (AG.linear(x, getattr(A, n).weight, None, vN, k1) for n in "QKV")
+            Ee = AG.linear(ef, A.E.weight, None, vE, k1)
             a = AG.edge_attention(Q, K, V, Ee, plan, rplan, L.num_heads)
-            o = AG.linear(a, L.O_h.weight, L.O_h.bias)
-            x1 = AG.bn_act(AG.masked_add(o, x), L.batch_norm1_h, relu=False)
-            f = AG.linear(AG.linear(x1, L.FFN_h_layer1.weight, L.FFN_h_layer1.bias, relu=True), L.FFN_h_layer2.weight, L.FFN_h_layer2.bias)
-            x = AG.bn_act(AG.masked_add(f, x1), L.batch_norm2_h, relu=False)
+            o = AG.linear(a, L.O_h.weight, L.O_h.bias, vN, k1)
+            x1 = AG.bn_act(AG.masked_add(o, x, vN, k1), L.batch_norm1_h, vN, k1, relu=False)
+            f = AG.linear(AG.linear(x1, L.FFN_h_layer1.weight, L.FFN_h_layer1.bias, vN, k1, relu=True), L.FFN_h_layer2.weight,
+                          L.FFN_h_layer2.bias, vN, k1)
+            x = AG.bn_act(AG.masked_add(f, x1, vN, k1), L.batch_norm2_h, vN, k1, relu=False)
         hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, relu=i < len(fcs) - 1)
+            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         self._h_last = x.detach()
         return hg
 
@@ -1357,20 +1363,33 @@ class GATNet(_PackCache, nn.Module):
         """Differentiable train-mode forward (SURVEY.md §8 f1 for this net): the same ops as autograd nodes; the GATConv adjoint is
         sn_gat_aggregate_bwd_f32 (CSR walks over the in-edges, then over the out-edges; no atomics)."""
         from . import autograd as AG
-        plan.check()
-        if bool((plan.rowptr[1:] == plan.rowptr[:-1]).any()):
-            raise ValueError("There are 0-in-degree nodes in the graph: GATConv's edge softmax is undefined for them")
+        vN, _, vB, k1 = _bucket_rows(self)          # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
+
+        def zero_deg():
+            z = plan.rowptr[1:] == plan.rowptr[:-1]
+            # (a padded batch: E_cap - E self-loops may not reach all N_cap - N padding nodes — only valid nodes count)
+            return (z if vN is None else z & (vN != 0)).any()
+
+        zero_msg = "There are 0-in-degree nodes in the graph: GATConv's edge softmax is undefined for them"
+        if ops.deferring():              # a captured step must not wait for the host: its check() reads these
+            ops.defer("plan", plan)
+            ops.defer("flag", zero_deg(), zero_msg)
+        else:
+            plan.check()
+            if bool(zero_deg()):
+                raise ValueError(zero_msg)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE
         N, H = hidx.shape[0], self.n_heads
-        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias), AG.embedding_sum(hidx, [self.embedding_h.weight]))
+        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), AG.embedding_sum(hidx, [self.embedding_h.weight]),
+                          vN, k1)
         for L in self.layers:
-            x = AG.gat_aggregate(AG.linear(x, L.fc.weight), L.attn_l, L.attn_r, L.bias, plan, rplan, H, L.negative_slope, True)
+            x = AG.gat_aggregate(AG.linear(x, L.fc.weight, None, vN, k1), L.attn_l, L.attn_r, L.bias, plan, rplan, H, L.negative_slope, True)
         x = AG.slot_sum(x.view(N * H, -1), N, H)                               # mean over the heads (:110)
         x = AG.act_residual(x, rowscale=torch.full((N,), 1.0 / H, dtype=torch.float32, device=x.device))
         hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, relu=i < len(fcs) - 1)
+            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         self._h_last = x.detach()
         return hg
 

@@ -1109,3 +1109,69 @@ def bucket_pack(data, target, out):
     with _span("sn_bucket_pack"):
         check(lib().sn_bucket_pack(C.byref(a), stream()), "sn_bucket_pack")
     return N, E, B, S
+
+
+class _BucketPackDglC(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("h", C.c_void_p), ("e", C.c_void_p), ("p", C.c_void_p),
+                ("snorm_n", C.c_void_p), ("target", C.c_void_p), ("batch_num_nodes", C.c_void_p),
+                ("N", C.c_int64), ("E", C.c_int64), ("B", C.c_int64), ("K", C.c_int64),
+                ("src_out", C.c_void_p), ("dst_out", C.c_void_p), ("h_out", C.c_void_p), ("e_out", C.c_void_p), ("p_out", C.c_void_p),
+                ("snorm_n_out", C.c_void_p), ("target_out", C.c_void_p), ("batch_num_nodes_out", C.c_void_p),
+                ("node_valid", C.c_void_p), ("edge_valid", C.c_void_p), ("graph_valid", C.c_void_p), ("node_slots", C.c_void_p),
+                ("counts", C.c_void_p), ("count_error", C.c_void_p), ("N_cap", C.c_int64), ("E_cap", C.c_int64), ("B_cap", C.c_int64)]
+
+
+NODE_COUNT_ERROR = "batch_num_nodes does not sum to the number of feature rows"      # (the eager step's message: dgl_nets / dgl_deepsigns _plan)
+
+
+def check_node_total(bnn, N):
+    """A host-side batch_num_nodes() (a DGL batch on the CPU, a list of sizes) must sum to the N feature rows: the ValueError of the
+    eager step, raised before any launch.  Device counts are checked by sn_bucket_pack_dgl itself (count_error)."""
+    if not (torch.is_tensor(bnn) and bnn.is_cuda):
+        t = torch.as_tensor(bnn)
+        if int(t.sum()) != int(N) or (t.numel() and int(t.min()) < 0):
+            raise ValueError(NODE_COUNT_ERROR)
+
+
+def bucket_pack_dgl(g, h, p, e, snorm_n, target, out):
+    """Copy a DGL batch of any shape — `g` (only edges() and batch_num_nodes() are read), atom ids h [N] / [N, 1], pos_enc p [N, K],
+    bond ids e [E] or None, snorm_n [N, 1] or None, targets [B, 1] — into the capacity buffers `out` (a DGLPaddedBatch of train_graph)
+    in ONE launch (sn_bucket_pack_dgl): the padding, the padded per-graph node counts, the node / edge / graph validity, the node-slot
+    vector and the device count block [N, E, B] too.  No device read; a host-side batch_num_nodes() is checked against N here (ValueError)
+    and copied through pinned memory; device counts that do not sum to N set out.count_error instead (the padded counts then still
+    total N_cap: one graph holds every node)."""
+    src, dst = g.edges()
+    dev = out.h.device
+    src, dst = src.long().contiguous(), dst.long().contiguous()
+    bnn = torch.as_tensor(g.batch_num_nodes())
+    check_node_total(bnn, h.shape[0])
+    if bnn.is_cuda:
+        bnn = bnn.long().contiguous()
+    else:
+        bnn = bnn.long().contiguous().pin_memory().to(dev, non_blocking=True)
+    hh = h.long().reshape(-1).contiguous()
+    pp = p.contiguous()
+    t = target.contiguous()
+    ee = None if e is None else e.long().reshape(-1).contiguous()
+    sn = None if snorm_n is None else snorm_n.reshape(-1).contiguous()
+    require_cuda(src, dst, hh, pp, t, ee, sn)
+    N, E, B = hh.numel(), src.numel(), bnn.numel()
+    if dst.numel() != E:
+        raise ValueError(f"bucket_pack_dgl: src has {E} edges, dst {dst.numel()}")
+    if pp.dtype != torch.float32 or tuple(pp.shape) != (N, out.K):
+        raise ValueError(f"bucket_pack_dgl: p is {pp.dtype} {tuple(pp.shape)}, the bucket holds float32 [N, {out.K}] with N = {N}")
+    if t.dtype != torch.float32 or t.numel() != B:
+        raise ValueError(f"bucket_pack_dgl: targets {t.dtype} {tuple(t.shape)} for {B} graphs (one float32 score per graph)")
+    for name, src_t, dst_t, n in (("e", ee, out.e, E), ("snorm_n", sn, out.snorm_n, N)):
+        if (src_t is None) != (dst_t is None):
+            raise ValueError(f"bucket_pack_dgl: {name} is {'missing' if src_t is None else 'given'}, the bucket was captured "
+                             f"{'with' if src_t is None else 'without'} it")
+        if src_t is not None and (src_t.numel() != n or src_t.dtype != dst_t.dtype):
+            raise ValueError(f"bucket_pack_dgl: {name} is {src_t.dtype} with {src_t.numel()} entries, expected {dst_t.dtype} x {n}")
+    a = _BucketPackDglC(ptr(src), ptr(dst), ptr(hh), ptr(ee), ptr(pp), ptr(sn), ptr(t), ptr(bnn), N, E, B, out.K,
+                        ptr(out.src), ptr(out.dst), ptr(out.h), ptr(out.e), ptr(out.p), ptr(out.snorm_n), ptr(out.target),
+                        ptr(out.batch_num_nodes), ptr(out.node_valid), ptr(out.edge_valid), ptr(out.graph_valid), ptr(out.node_slots),
+                        ptr(out.counts), ptr(out.count_error), out.N_cap, out.E_cap, out.B_cap)
+    with _span("sn_bucket_pack_dgl"):
+        check(lib().sn_bucket_pack_dgl(C.byref(a), stream()), "sn_bucket_pack_dgl")
+    return N, E, B

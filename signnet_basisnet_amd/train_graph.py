@@ -126,9 +126,10 @@ def _mask_buffers(model, N, K, dev):
     return draw, masks
 
 
-def _capture(step, fwd_bwd, dev, warmup):
+def _capture(step, fwd_bwd, dev, warmup, check=None):
     """Warm up `fwd_bwd` on a side stream (lazy one-time setup: LDS limits, allocator pools) and capture it, under `step._scoped()`,
     without touching the model's state: buffers (running statistics, counters) and the generator are restored afterwards.
+    `check`: what raises for a bad batch after the warm-up (default: the model's check_train()).
     -> (graph, loss, y, the captured forward's status words)."""
     model = step.model
     saved = [b.detach().clone() for b in model.buffers()]
@@ -141,7 +142,7 @@ def _capture(step, fwd_bwd, dev, warmup):
                 step._refresh_masks()
                 fwd_bwd()
         torch.cuda.current_stream().wait_stream(side)
-        model.check_train()
+        (check or model.check_train)()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             loss, y = fwd_bwd()
@@ -242,7 +243,60 @@ class _BucketCapture:
     check = GraphedStep.check
 
 
-class BucketedStep:
+class _CaptureLRU:
+    """What BucketedStep and DGLBucketedStep share: the LRU of `max_captures` captured buckets (each with its own memory pool), the
+    `captures` / `hits` counters, the replay (one graph launch + the one Adam launch of optim.FlatAdam) and check()."""
+
+    check_every = 64     # replays between two reads of the status words (0 = only when the caller calls check())
+
+    def _init_lru(self, max_captures):
+        self.max_captures = int(max_captures)
+        self._lru = collections.OrderedDict()       # bucket -> capture, least recently used first
+        self.captures = self.hits = 0
+        self._last, self._nsteps = None, 0
+
+    @property
+    def buckets(self):
+        """The buckets captured now, least recently used first."""
+        return list(self._lru)
+
+    def _admit(self, bucket):
+        """LRU bookkeeping for a bucket about to be used: True if it is captured already."""
+        if bucket in self._lru:
+            self._lru.move_to_end(bucket)
+            return True
+        while len(self._lru) >= self.max_captures:
+            _, old = self._lru.popitem(last=False)
+            if self._last is old:
+                self._last = None
+            old.graph.reset()           # (its private memory pool goes back to the allocator)
+        return False
+
+    def release(self):
+        """Drop every capture (their memory pools go back to the allocator); the next step of any bucket captures again."""
+        while self._lru:
+            _, old = self._lru.popitem(last=False)
+            old.graph.reset()
+        self._last = None
+
+    def _replay(self, cap):
+        self._last = cap
+        cap._refresh_masks()
+        cap.graph.replay()
+        self.optimizer.step()
+        self._nsteps += 1
+        if self.check_every and self._nsteps % self.check_every == 0:
+            self.check()
+        return cap.loss
+
+    def check(self):
+        """Reads the status words of the LAST replayed step (one host wait): raises IndexError for a discrete feature outside its
+        embedding table, as nn.Embedding does in the reference's eager step (and, for a DGL GATNet, the eager step's batch errors)."""
+        if self._last is not None:
+            self._last.check()
+
+
+class BucketedStep(_CaptureLRU):
     """The captured training step for a real loader: batches of any shape (node count N, edge count E, eigenvector entries S, at most
     `max_graphs` graphs; max_k fixed or None = all eigenvectors) are padded into fixed-capacity buffers and run through a step captured
     ONCE per capacity bucket (the reference's loops: Alchemy/main_alchemy.py:99-110, GINESignNetPyG/core/train.py:55-66).
@@ -285,15 +339,8 @@ class BucketedStep:
             if k not in self.granule or int(v) < 1:
                 raise ValueError(f"BucketedStep: granule {k}={v} (keys N, E, S, K; values >= 1)")
             self.granule[k] = int(v)
-        self.max_captures, self.warmup = int(max_captures), int(warmup)
-        self._lru = collections.OrderedDict()       # Bucket -> _BucketCapture, least recently used first
-        self.captures = self.hits = 0
-        self._last, self._nsteps = None, 0
-
-    @property
-    def buckets(self):
-        """The buckets captured now, least recently used first."""
-        return list(self._lru)
+        self.warmup = int(warmup)
+        self._init_lru(max_captures)                # Bucket -> _BucketCapture
 
     def bucket_of(self, data):
         """The capacity bucket of a batch (host only, unless max_k is None and the batch has no host-side sizes: one device read)."""
@@ -315,18 +362,6 @@ class BucketedStep:
             K = _round_up(max(nmax, 1), g["K"])
         return Bucket(_round_up(N + 1, g["N"]), _round_up(max(E, 1), g["E"]), _round_up(max(S, 1), g["S"]), K)
 
-    def _admit(self, bucket):
-        """LRU bookkeeping for a bucket about to be used: True if it is captured already."""
-        if bucket in self._lru:
-            self._lru.move_to_end(bucket)
-            return True
-        while len(self._lru) >= self.max_captures:
-            _, old = self._lru.popitem(last=False)
-            if self._last is old:
-                self._last = None
-            old.graph.reset()           # (its private memory pool goes back to the allocator)
-        return False
-
     def step(self, data, target, bucket=None):
         """One training step on `data` / `target` ([num_graphs, n_out]): returns the loss (a device scalar, rewritten by the next
         step of the same bucket).  `bucket`: explicit capacities (Bucket / (N, E, S, K)) instead of the granule rounding."""
@@ -345,20 +380,194 @@ class BucketedStep:
             cap = _BucketCapture(self, b, data, target, self.warmup)
             self._lru[b] = cap
             self.captures += 1
-        self._last = cap
-        cap._refresh_masks()
-        cap.graph.replay()
-        self.optimizer.step()
-        self._nsteps += 1
-        if self.check_every and self._nsteps % self.check_every == 0:
-            self.check()
-        return cap.loss
+        return self._replay(cap)
+
+
+# ----------------------------------------------------------------------------- the DGL tree's loop (GraphPrediction)
+_DGL_NETS = ("GINNet", "GatedGCNNet", "GATNet", "PNANet", "TransformerNet")
+
+
+class DGLBucket(tuple):
+    """The capacities of a padded DGL batch: N_cap > N nodes (the spare graph holds >= 1 padding node), E_cap >= E edges."""
+    __slots__ = ()
+
+    def __new__(cls, N, E):
+        return tuple.__new__(cls, (int(N), int(E)))
+
+    N = property(lambda s: s[0])
+    E = property(lambda s: s[1])
+
+    def __repr__(self):
+        return "DGLBucket(N=%d, E=%d)" % self
+
+
+class DGLPaddedBatch:
+    """The static buffers of one DGL bucket (ops.bucket_pack_dgl writes all of them): edge list, atom / bond ids, pos_enc, snorm_n and
+    targets in capacity buffers, the padded per-graph node counts, the 0/1 node / edge / graph validity, the node-slot vector (K on valid
+    nodes, 0 on padding nodes), the device count block [N, E, B] — and `g`, the padded graph object the nets read.  Its host-side node
+    counts are frozen (total N_cap): the plans' node-count check reads no device value; the node -> graph vector is rebuilt on the device
+    from the padded counts by the recorded repeat_interleave(..., output_size=N_cap) at every replay.  The pack guarantees that they
+    total N_cap, also for a batch whose counts do not sum to its N rows (count_error: check() raises the eager step's ValueError)."""
+
+    def __init__(self, bucket, B_cap, K, has_e, has_snorm, dev):
+        from .dgl_deepsigns import Graph
+        self.N_cap, self.E_cap, self.B_cap, self.K = bucket.N, bucket.E, int(B_cap), int(K)
+        i64, i32, f32 = (dict(dtype=t, device=dev) for t in (torch.int64, torch.int32, torch.float32))
+        self.src, self.dst = torch.zeros(self.E_cap, **i64), torch.zeros(self.E_cap, **i64)
+        self.h = torch.zeros(self.N_cap, **i64)
+        self.e = torch.zeros(self.E_cap, **i64) if has_e else None
+        self.p = torch.zeros(self.N_cap, self.K, **f32)
+        self.snorm_n = torch.zeros(self.N_cap, 1, **f32) if has_snorm else None
+        self.target = torch.zeros(self.B_cap, 1, **f32)
+        self.batch_num_nodes = torch.zeros(self.B_cap, **i64)
+        self.node_valid, self.node_slots = torch.zeros(self.N_cap, **i32), torch.zeros(self.N_cap, **i32)
+        self.edge_valid = torch.zeros(self.E_cap, **i32)
+        self.graph_valid = torch.zeros(self.B_cap, **i32)
+        self.counts = torch.zeros(3, **i32)
+        self.count_error = torch.zeros(1, **i32)                 # 1: the batch's node counts did not sum to N (check() raises)
+        self.g = Graph(self.src, self.dst, self.batch_num_nodes)
+        self.g._sn_node_counts = (self.N_cap, self.N_cap)       # (largest graph: an upper bound; only eval paths read it)
+
+
+class _DGLBucketCapture:
+    """One DGL bucket's captured step — sign_inv_net -> net -> masked L1 over the valid graphs -> backward (the loop body of
+    train_ZINC_graph_regression.py:60-82) — with the host checks of its forward deferred (ops.defer_status) and its own memory pool."""
+
+    _masks = None
+    _refresh_masks = GraphedStep._refresh_masks
+
+    def __init__(self, owner, bucket, batch, warmup):
+        net, optimizer = owner.model, owner.optimizer
+        g, h, p, e, snorm_n, targets = batch
+        dev = h.device
+        self.model, self.bucket = net, bucket
+        r0 = torch.cuda.memory_reserved(dev)
+        self.pad = pad = DGLPaddedBatch(bucket, owner.B_cap, owner.K, e is not None, snorm_n is not None, dev)
+        from . import ops
+        ops.bucket_pack_dgl(g, h, p, e, snorm_n, targets, pad)
+        self._words = []
+        from .autograd import masked_l1_loss
+
+        def fwd_bwd():
+            optimizer.flat_g.zero_()
+            # (the embedding index checks and GAT's batch checks hand their device words over instead of reading them: check() does)
+            with ops.defer_status() as words:
+                pe = net.sign_inv_net(pad.g, pad.p.unsqueeze(-1)).squeeze(-1)                   # handle_lap, sign_inv (:20-25)
+                y, _ = net(pad.g, pad.h, pe, pad.e, pad.snorm_n)
+            self._words = words
+            loss = masked_l1_loss(y, pad.target.view_as(y), pad.graph_valid, pad.counts[2:3])
+            loss.backward()
+            return loss, y
+
+        self.graph, self.loss, self.y, _ = _capture(self, fwd_bwd, dev, warmup, check=self.check)
+        self.memory_reserved = torch.cuda.memory_reserved(dev) - r0
+
+    @contextlib.contextmanager
+    def _scoped(self):
+        """The switch `_bucket` on the net AND its sign_inv_net, set only while this object runs them (warm-up and capture)."""
+        mods = (self.model, self.model.sign_inv_net)
+        saved = [getattr(m, "_bucket", None) for m in mods]
+        for m in mods:
+            m._bucket = self.pad
+        try:
+            yield
+        finally:
+            for m, s in zip(mods, saved):
+                m._bucket = s
 
     def check(self):
-        """Reads the status words of the LAST replayed step (one host wait): raises IndexError for a discrete feature outside its
-        embedding table, as nn.Embedding does in the reference's eager step."""
-        if self._last is not None:
-            self._last.check()
+        """The deferred checks of the captured forward, read now (one host wait): what the eager step raises at once."""
+        from . import ops
+        if int(self.pad.count_error[0]):
+            raise ValueError(ops.NODE_COUNT_ERROR)
+        ops.raise_deferred(self._words)
+
+
+class DGLBucketedStep(_CaptureLRU):
+    """The captured training step of the DGL tree's loop (GraphPrediction/train/train_ZINC_graph_regression.py:54-88): batches of any
+    shape (N nodes, E edges, at most `max_graphs` graphs) are padded into fixed-capacity buffers and run through a step captured ONCE
+    per capacity bucket.
+
+        step = DGLBucketedStep(net, flat_adam, max_graphs=128, granule=dict(N=256, E=512), max_captures=4)
+        loss = step.step(g, h, p, e, snorm_n, targets)      # p: the raw pos_enc [N, pos_enc_dim]; e / snorm_n None where unused
+
+    `net`: GINNet, GatedGCNNet, GATNet, PNANet or TransformerNet of dgl_nets with lap_method 'sign_inv' and its sign_inv_net
+    (GINDeepSigns / MaskedGINDeepSigns); `g`: a DGL batched graph or dgl_deepsigns.Graph (only edges() and batch_num_nodes() are
+    read).  step(): the bucket is chosen on the HOST from tensor shapes, with no device read (N_cap >= N + 1 and E_cap >= max(E, 1),
+    each rounded up to its granule; B_cap = max_graphs + 1: the spare graph holds the padding nodes; K = net.pos_enc_dim); a new bucket
+    is captured on first use (`captures`), a known one replayed (`hits`); the captures live in an LRU of `max_captures`, each with its
+    own memory pool.  The captured region is sign_inv_net -> net -> the L1 loss over the valid graphs divided by the device graph count
+    -> backward; a step is then ONE pack launch (sn_bucket_pack_dgl), one graph replay and the one Adam launch of optim.FlatAdam.
+    Padding rows enter no batch statistic, no running statistic and no gradient: losses and gradients are those of the eager step on
+    the unpadded batch (up to summation order), and the padding content cannot change a bit of them.  The forward's host checks (atom /
+    bond ids outside their tables, GAT's malformed batch and zero-in-degree tests, node counts on the device that do not sum to N) are
+    read by check(), every `check_every` steps, and raise what the eager step raises; host-side node counts that do not sum to N raise
+    that ValueError before any launch.  Data-parallel training is not supported (optimizer.dist must be None)."""
+
+    def __init__(self, net, optimizer, max_graphs=128, granule=None, max_captures=4, warmup=2):
+        from . import dgl_nets
+        from .optim import FlatAdam
+        if not isinstance(optimizer, FlatAdam):
+            raise TypeError("DGLBucketedStep needs optim.FlatAdam (static flat parameter / gradient buffers)")
+        if not isinstance(net, tuple(getattr(dgl_nets, n) for n in _DGL_NETS)):
+            raise TypeError("DGLBucketedStep needs a dgl_nets network (" + ", ".join(_DGL_NETS) + ")")
+        if optimizer.dist is not None:
+            raise ValueError("DGLBucketedStep: data-parallel training (FlatAdam with dist) is not supported; use the eager step")
+        if getattr(net, "lap_method", None) != "sign_inv":
+            raise ValueError(f"DGLBucketedStep: lap_method {getattr(net, 'lap_method', None)!r} is not supported (only 'sign_inv')")
+        if getattr(net, "use_lapeig_loss", False):
+            raise ValueError("DGLBucketedStep: use_lapeig_loss is not supported (the L1 task loss only)")
+        if getattr(net, "sign_inv_net", None) is None:
+            raise ValueError("DGLBucketedStep: the net has no sign_inv_net")
+        if int(max_graphs) < 1 or int(max_captures) < 1:
+            raise ValueError("DGLBucketedStep: max_graphs and max_captures must be >= 1")
+        self.model, self.optimizer = net, optimizer
+        self.max_graphs, self.B_cap = int(max_graphs), int(max_graphs) + 1
+        self.K = int(net.pos_enc_dim)
+        self.granule = dict(N=256, E=512)
+        for k, v in (granule or {}).items():
+            if k not in self.granule or int(v) < 1:
+                raise ValueError(f"DGLBucketedStep: granule {k}={v} (keys N, E; values >= 1)")
+            self.granule[k] = int(v)
+        self.warmup = int(warmup)
+        self._init_lru(max_captures)                # DGLBucket -> _DGLBucketCapture
+
+    def _num_graphs(self, g):
+        B = int(g.batch_num_nodes().numel())
+        if B > self.max_graphs:
+            raise ValueError(f"DGLBucketedStep: a batch of {B} graphs exceeds max_graphs={self.max_graphs}")
+        return B
+
+    def bucket_of(self, g, h):
+        """The capacity bucket of a batch: from tensor shapes on the host, no device read."""
+        self._num_graphs(g)
+        src, _ = g.edges()
+        N, E = int(h.shape[0]), int(src.numel())
+        return DGLBucket(_round_up(N + 1, self.granule["N"]), _round_up(max(E, 1), self.granule["E"]))
+
+    def step(self, g, h, p, e, snorm_n, targets, bucket=None):
+        """One training step on a batch (targets [num_graphs, 1]): returns the loss (a device scalar, rewritten by the next step of the
+        same bucket).  `bucket`: explicit capacities (DGLBucket / (N_cap, E_cap)) instead of the granule rounding."""
+        self._num_graphs(g)
+        b = self.bucket_of(g, h) if bucket is None else DGLBucket(*bucket)
+        N = int(h.shape[0])
+        if tuple(p.shape) != (N, self.K):
+            raise ValueError(f"DGLBucketedStep: p has shape {tuple(p.shape)}, expected [N, pos_enc_dim] = [{N}, {self.K}] (the raw pos_enc)")
+        from . import ops
+        ops.check_node_total(g.batch_num_nodes(), N)     # (host counts; device counts: the pack flags them, check() raises)
+        batch = (g, h, p, e, snorm_n, targets)
+        if self._admit(b):
+            cap = self._lru[b]
+            ops.bucket_pack_dgl(*batch, cap.pad)
+            self.hits += 1
+        else:
+            from . import train_stage
+            train_stage.flush_deferred()      # (nothing of an earlier eager backward may be left for the captured one to reduce)
+            self.model.train()
+            cap = _DGLBucketCapture(self, b, batch, self.warmup)
+            self._lru[b] = cap
+            self.captures += 1
+        return self._replay(cap)
 
 
 class GraphedForward:
