@@ -208,6 +208,20 @@ int sn_pack_weight_t_f32(const float* W, int rows, int cols, int ldw, float* Wp,
  * followed by SN_SPLIT_EPI per-channel fp32 vectors e0,e1,e2 (bias / folded BatchNorm of the Linear's epilogue,
  * length d_out, NULL = zeros) in the accumulator layout — the whole Linear streams through LDS as one buffer. */
 #define SN_SPLIT_EPI 3
+/* Matmul precision of the split-packed Linears of the fused eval stages: which of the six partial products of the exact split
+ * x = h + m + l (h = top 16 bits, m = top 16 bits of x - h, l = the rest) are issued — the `precision` argument of the *_prec_f32
+ * entry points below (the names of torch.set_float32_matmul_precision).  fp32 accumulate in every mode; the packed weights are the
+ * same for all of them (nothing is repacked); everything that is not a split-packed weight GEMM (layer 0 of phi, aggregation,
+ * BatchNorm / LayerNorm, residuals, attention scores and values, softmax, slot sums) is the same arithmetic in every mode.
+ *   SN_PREC_HIGHEST  hh + hm + mh + hl + lh + mm   (dropped terms <= 2^-23 |x||w|: what the entry points without `precision` compute)
+ *   SN_PREC_HIGH     hh + hm + mh                  (dropped terms <= 2^-13 |x||w|, "bf16x3")
+ *   SN_PREC_MEDIUM   hh                            (dropped terms <= (2^-6 + 2^-14) |x||w|: bf16 operands)
+ * The value travels with the call (no process-wide state).  Any other value is SN_ERR_ARG.  The two reduced modes are built for the
+ * widths of the shipped configurations only — ceil(d/16) in {4, 7, 8} (phi, rho), padded width 64 / 80 / 96 (sn_deepsigns_phi), every
+ * width of sn_mlp_chain — and return SN_ERR_UNSUPPORTED elsewhere: a mode is never replaced by another. */
+#define SN_PREC_HIGHEST 0
+#define SN_PREC_HIGH 1
+#define SN_PREC_MEDIUM 2
 int64_t sn_split_packed_bytes(int d_out, int d_in);
 int sn_pack_split_f32(const float* W, int d_out, int d_in, int ldw, const float* e0, const float* e1,
                       const float* e2, void* Wsp /* 16-byte aligned */, void* stream);
@@ -655,6 +669,11 @@ int sn_phi_fused_f32(const sn_phi_params* params /* host struct of device pointe
                      const int32_t* rowptr, const int32_t* col, const sn_plan_bins* bins,
                      int kmax /* as given to sn_batch_plan */, int K /* row stride of out in slots */,
                      float* out, void* stream);
+/* The same with the matmul precision of its [d, d] Linears (SN_PREC_*); sn_phi_fused_f32 is precision = SN_PREC_HIGHEST.  Layer 0 with
+ * hid0 == 1 has no [d, d] Linear and is the same in every mode. */
+int sn_phi_fused_prec_f32(const sn_phi_params* params, const float* eigen_vectors, const int32_t* graph_ptr, const int64_t* evoff,
+                          const int32_t* rowptr, const int32_t* col, const sn_plan_bins* bins, int kmax, int K, float* out,
+                          int precision, void* stream);
 
 /* The sign-invariant encoder of the DGL tree, enc(g, x) + enc(g, -x) with enc = GIN (GraphPrediction/layers/deepsigns.py:45-46 /
  * :72-73, layers/gnns.py:81-114, layers/mlp.py:37-56), eval mode, ONE launch — the same stage kernel as sn_phi_fused_f32 with the
@@ -669,6 +688,9 @@ int sn_phi_fused_f32(const sn_phi_params* params /* host struct of device pointe
  * (row = node*K + slot), reserved = phi_out_dim <= d.  Graphs of more than 64 nodes: meta[1] != 0, nothing is written. */
 int sn_deepsigns_phi_f32(const sn_phi_params* params, const float* x, int ldx, const int32_t* graph_ptr, const int32_t* rowptr,
                          const int32_t* col, const sn_plan_bins* bins, int K, float* out, void* stream);
+/* The same with the matmul precision of its Linears (SN_PREC_*; reduced modes: d = 64, 80, 96); sn_deepsigns_phi_f32 is SN_PREC_HIGHEST. */
+int sn_deepsigns_phi_prec_f32(const sn_phi_params* params, const float* x, int ldx, const int32_t* graph_ptr, const int32_t* rowptr,
+                              const int32_t* col, const sn_plan_bins* bins, int K, float* out, int precision, void* stream);
 
 /* A whole MLP over matrix rows in one launch: y = W_{L-1} relu(... relu(W_0 x + b_0) ...) + b_{L-1} — rho of the DGL sign-invariant
  * nets (layers/deepsigns.py:47-49 and :81-84 with layers/mlp.py:37-56; eval BatchNorms, which sit between a ReLU and the next
@@ -678,6 +700,9 @@ int sn_deepsigns_phi_f32(const sn_phi_params* params, const float* x, int ldx, c
 #define SN_MLP_MAX_LAYERS 16
 int sn_mlp_chain_f32(const float* x, int ldx, int64_t R, int d_in, const int32_t* nvalid, int K, const void* const* weights,
                      int n_layers, int d_pad, float* y, int ldy, int d_out, void* stream);
+/* The same with the matmul precision of every Linear of the chain (SN_PREC_*, every width); sn_mlp_chain_f32 is SN_PREC_HIGHEST. */
+int sn_mlp_chain_prec_f32(const float* x, int ldx, int64_t R, int d_in, const int32_t* nvalid, int K, const void* const* weights,
+                          int n_layers, int d_pad, float* y, int ldy, int d_out, int precision, void* stream);
 
 /* rho: the set-transformer encoder layers over each node's valid slots and the sum over slots, one launch.
  * Replaces SetTransformer.forward up to torch.sum(x, dim=1) (sign_net.py:60-70 / core/sign_net.py:64-75)
@@ -714,6 +739,10 @@ typedef struct {
 int sn_rho_fused_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
                      const int32_t* graph_ptr, int64_t B, int64_t N, const sn_plan_bins* bins, int kmax, int K,
                      float* out_sum, void* stream);
+/* The same with the matmul precision of the six [d, d] projections of every encoder layer (SN_PREC_*); the attention's score and
+ * value products (fp32 MFMA) are not split-packed GEMMs and do not change.  sn_rho_fused_f32 is precision = SN_PREC_HIGHEST. */
+int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x, const float* eigen_values, const int32_t* graph_ptr, int64_t B,
+                          int64_t N, const sn_plan_bins* bins, int kmax, int K, float* out_sum, int precision, void* stream);
 
 /* The GINE network on top of the positional encoding, one launch: rho's output Linear+BatchNorm on the slot
  * sum (sign_net.py:71), then GNN.forward (model.py:36-64 / core/model.py:44-79): input encoder

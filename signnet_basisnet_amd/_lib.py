@@ -50,6 +50,8 @@ SIGNATURES = {
     "sn_colstats_blocks": [_l],
     "sn_phi_fused_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p],
     "sn_rho_fused_f32": [_p, _p, _p, _p, _l, _l, _p, _i, _i, _p, _p],
+    "sn_phi_fused_prec_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p],
+    "sn_rho_fused_prec_f32": [_p, _p, _p, _p, _l, _l, _p, _i, _i, _p, _i, _p],
     "sn_gnn_fused_f32": [_p, _p, _i, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p, _p],
     "sn_gin_net_fused_f32": [_p, _p, _i, _p, _p, _i, _i, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p],
     "sn_transformer_net_fused_f32": [_p, _p, _i, _p, _p, _i, _i, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p],
@@ -87,6 +89,8 @@ SIGNATURES = {
     "sn_pointwise_f32": [_p, _i, _l, _i, _p, _p, _p, _i, _f, _p, _i, _p, _i, _p],
     "sn_deepsigns_phi_f32": [_p, _p, _i, _p, _p, _p, _p, _i, _p, _p],
     "sn_mlp_chain_f32": [_p, _i, _l, _i, _p, _i, _p, _i, _i, _p, _i, _i, _p],
+    "sn_deepsigns_phi_prec_f32": [_p, _p, _i, _p, _p, _p, _p, _i, _p, _i, _p],
+    "sn_mlp_chain_prec_f32": [_p, _i, _l, _i, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p],
     "sn_gat_aggregate_f32": [_p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _p, _p, _p],
     "sn_gat_aggregate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_edge_rows_sum_f32": [_p, _i, _i, _l, _p, _p, _p, _i, _p],

@@ -76,6 +76,22 @@ constexpr int SPLIT_RING = 3;
 static_assert(SPLIT_RING == 3, "slot_of() is x mod 3");
 constexpr int SPLIT_EPI = SN_SPLIT_EPI;
 
+// Product sets (PREC, a compile-time parameter of the workgroup GEMMs; SN_PREC_* of signnet_hip.h): which of the six partial
+// products are issued.  The packed weights and the LDS-DMA stream are the same in every mode (all three planes are staged); a
+// reduced mode neither reads the unused weight planes from LDS nor computes the unused activation planes (their split arithmetic
+// is dead code of the instantiation).
+//   PREC_HIGHEST  hh + hm + mh + hl + lh + mm   fp32-class (dropped: <= 2^-23 |x||w|)
+//   PREC_HIGH     hh + hm + mh                  dropped: <= 2^-13 |x||w|   ("bf16x3")
+//   PREC_MEDIUM   hh                            dropped: <= (2^-6 + 2^-14) |x||w|   (bf16 operands, fp32 accumulate)
+constexpr int PREC_HIGHEST = SN_PREC_HIGHEST, PREC_HIGH = SN_PREC_HIGH, PREC_MEDIUM = SN_PREC_MEDIUM;
+// the last plane of an activation split a mode reads (scheduling fences name it)
+template <int PREC, typename S>
+__device__ __forceinline__ auto& last_plane(S& s) {
+  if constexpr (PREC == PREC_HIGHEST) return s.l;
+  else if constexpr (PREC == PREC_HIGH) return s.m;
+  else return s.h;
+}
+
 struct Split8 { u32x4 h, m, l; };
 
 __device__ __forceinline__ unsigned pack_hi16(float a, float b) {   // bf16 bits of a | bf16 bits of b << 16
@@ -202,20 +218,45 @@ struct WRing {
 
 struct WFrag { u32x4 h, m, l; };
 
+// the weight planes of one K block a mode multiplies with: LDS -> VGPR (p: the lane's address of the block's h plane)
+template <int PREC>
+__device__ __forceinline__ WFrag read_wfrag(const lds_char_t* p) {
+  typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
+  WFrag f;
+  f.h = *(lds_u32x4*)(p);
+  if constexpr (PREC <= PREC_HIGH) f.m = *(lds_u32x4*)(p + 1024); else f.m = u32x4{0u, 0u, 0u, 0u};
+  if constexpr (PREC == PREC_HIGHEST) f.l = *(lds_u32x4*)(p + 2048); else f.l = u32x4{0u, 0u, 0u, 0u};
+  return f;
+}
+// the partial products of K block `kb` of a reduced mode (A = weight planes unless SWAP).  high: hm on a1, mh and hh on a0;
+// medium: the K blocks alternate between the two accumulators — two independent MFMA chains as in the full product.
+template <int PREC, bool SWAP>
+__device__ __forceinline__ void mm_reduced(const WFrag& f, const Split8& x, int kb, f32x4& a0, f32x4& a1) {
+  static_assert(PREC == PREC_HIGH || PREC == PREC_MEDIUM, "the six-product form is written out at its call sites");
+  if constexpr (PREC == PREC_HIGH) {
+    a1 = SWAP ? mfma_bf(x.h, f.m, a1) : mfma_bf(f.m, x.h, a1);
+    a0 = SWAP ? mfma_bf(x.m, f.h, a0) : mfma_bf(f.h, x.m, a0);
+    a0 = SWAP ? mfma_bf(x.h, f.h, a0) : mfma_bf(f.h, x.h, a0);
+  } else {
+    f32x4& a = (kb & 1) ? a1 : a0;
+    a = SWAP ? mfma_bf(x.h, f.h, a) : mfma_bf(f.h, x.h, a);
+  }
+}
+
 // acc(ot) = W[16 outputs of tile ot] . x  for ot < NTO, consumed by epi(ot, acc, e0, e1, e2, pv) (e*: the chunk's
 // epilogue vectors in the accumulator layout; pv = pre(ot), an f32x4 the caller wants fetched BEFORE the tile's
 // MFMAs, e.g. the residual from LDS).  EVERY wave of the workgroup must call it (barriers, DMA shares);
 // `live` = this wave has rows (a dead wave only keeps the stream going).  `wnext` (never null): the matrix whose
 // first chunks are staged behind this one's — the next wg_gemm_split() of the workgroup must be on `wnext`; the
 // kernel starts the stream with WRing::prologue(first matrix) and ends with WRing::drain().  SWAP: operands exchanged -> acc[r] = Y[row = 4g + r][out = 16*ot + (l&15)].
-template <int NT, int NTO, bool SWAP, bool EPIV = true, int NW = 4, int RING = SPLIT_RING, typename Pre, typename Epi>
+// PREC: the product set (above).
+template <int NT, int NTO, bool SWAP, bool EPIV = true, int NW = 4, int RING = SPLIT_RING, int PREC = PREC_HIGHEST, typename Pre, typename Epi>
 __device__ __forceinline__ void wg_gemm_split(WRing<NT, NW, RING>& ring, const void* w, const void* wnext, bool live,
                                               const Split8 (&xs)[(NT + 1) / 2], Pre pre, Epi epi) {
   using R = WRing<NT, NW, RING>;
   constexpr int NKB = R::NKB;
   constexpr bool CHAIN = NTO >= RING;     // the stream runs on into the next matrix; else: one prologue per GEMM
   if (!CHAIN) ring.prologue(w, NTO);
-  typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
   typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
   int sl[RING];
 #pragma unroll
@@ -231,16 +272,11 @@ __device__ __forceinline__ void wg_gemm_split(WRing<NT, NW, RING>& ring, const v
     int ln16 = ring.lane * 16;
     asm volatile("" : "+v"(ln16));   // per call: keeps the per-lane fragment addresses of every GEMM from being hoisted and held
     const lds_char_t* lbase = ring.base + ln16;
-    auto rd = [&](int c, int kb) {
-      const lds_char_t* p = lbase + slot(c) * R::CHUNK + kb * 3072;
-      WFrag f;
-      f.h = *(lds_u32x4*)(p);
-      f.m = *(lds_u32x4*)(p + 1024);
-      f.l = *(lds_u32x4*)(p + 2048);
-      return f;
-    };
-    auto mm = [&](const WFrag& f, const Split8& x, f32x4& a0, f32x4& a1) {
-      if (!SWAP) {
+    auto rd = [&](int c, int kb) { return read_wfrag<PREC>(lbase + slot(c) * R::CHUNK + kb * 3072); };
+    auto mm = [&](const WFrag& f, const Split8& x, int kb, f32x4& a0, f32x4& a1) {
+      if constexpr (PREC != PREC_HIGHEST) {
+        mm_reduced<PREC, SWAP>(f, x, kb, a0, a1);
+      } else if (!SWAP) {
         a1 = mfma_bf(f.l, x.h, a1);
         a0 = mfma_bf(f.m, x.h, a0);
         a1 = mfma_bf(f.h, x.l, a1);
@@ -271,7 +307,7 @@ __device__ __forceinline__ void wg_gemm_split(WRing<NT, NW, RING>& ring, const v
       for (int kb = 0; kb + 1 < NKB; ++kb) {
         fb = rd(ot, kb + 1);
         __builtin_amdgcn_sched_barrier(0);
-        mm(fa, xs[kb], a0, a1);
+        mm(fa, xs[kb], kb, a0, a1);
         __builtin_amdgcn_sched_barrier(0);
         fa = fb;
       }
@@ -285,7 +321,7 @@ __device__ __forceinline__ void wg_gemm_split(WRing<NT, NW, RING>& ring, const v
       }
       if (ot + 1 < NTO) fb = rd(ot + 1, 0);
       __builtin_amdgcn_sched_barrier(0);
-      mm(fa, xs[NKB - 1], a0, a1);
+      mm(fa, xs[NKB - 1], NKB - 1, a0, a1);
       __builtin_amdgcn_sched_barrier(0);
       epi(ot, a0 + a1, e0, e1, e2, pv);
       fa = fb;
@@ -348,13 +384,12 @@ __device__ __forceinline__ void ring_prologue3_issue(WRing<NT, NW, LAG_RING>& ri
   ring.issue(w, 2, 2);
 }
 
-template <int NT, int NTO, int BAR_KB, int NW, typename Pre, typename Epi>
+template <int NT, int NTO, int BAR_KB, int NW, int PREC = PREC_HIGHEST, typename Pre, typename Epi>
 __device__ __forceinline__ void wg_gemm_split_lag(WRing<NT, NW, LAG_RING>& ring, const void* w, const void* wnext, bool live,
                                                   const Split8 (&xs)[(NT + 1) / 2], Pre pre, Epi epi) {
   using R = WRing<NT, NW, LAG_RING>;
   constexpr int NKB = R::NKB;
   static_assert(NTO >= 3 && BAR_KB >= 0 && BAR_KB < NKB, "look-ahead of three chunks; the barrier sits in front of a K block of the tile");
-  typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
   typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
   int sl[LAG_RING];
 #pragma unroll
@@ -371,14 +406,7 @@ __device__ __forceinline__ void wg_gemm_split_lag(WRing<NT, NW, LAG_RING>& ring,
     int ln16 = ring.lane * 16;
     asm volatile("" : "+v"(ln16));   // per call: keeps the per-lane fragment addresses of every GEMM from being hoisted and held
     const lds_char_t* lbase = ring.base + ln16;
-    auto rd = [&](int c, int kb) {
-      const lds_char_t* p = lbase + slot(c) * R::CHUNK + kb * 3072;
-      WFrag f;
-      f.h = *(lds_u32x4*)(p);
-      f.m = *(lds_u32x4*)(p + 1024);
-      f.l = *(lds_u32x4*)(p + 2048);
-      return f;
-    };
+    auto rd = [&](int c, int kb) { return read_wfrag<PREC>(lbase + slot(c) * R::CHUNK + kb * 3072); };
     WFrag fa = rd(0, 0), fb;
 #pragma unroll
     for (int ot = 0; ot < NTO; ++ot) {
@@ -393,12 +421,16 @@ __device__ __forceinline__ void wg_gemm_split_lag(WRing<NT, NW, LAG_RING>& ring,
         if (kb + 1 < NKB) fb = rd(ot, kb + 1);
         else if (ot + 1 < NTO) fb = rd(ot + 1, 0);     // (behind barrier ot, which published chunk ot + 1)
         __builtin_amdgcn_sched_barrier(0);
-        a1 = mfma_bf(fa.l, xs[kb].h, a1);
-        a0 = mfma_bf(fa.m, xs[kb].h, a0);
-        a1 = mfma_bf(fa.h, xs[kb].l, a1);
-        a0 = mfma_bf(fa.h, xs[kb].m, a0);
-        a1 = mfma_bf(fa.m, xs[kb].m, a1);
-        a0 = mfma_bf(fa.h, xs[kb].h, a0);
+        if constexpr (PREC != PREC_HIGHEST) {
+          mm_reduced<PREC, false>(fa, xs[kb], kb, a0, a1);
+        } else {
+          a1 = mfma_bf(fa.l, xs[kb].h, a1);
+          a0 = mfma_bf(fa.m, xs[kb].h, a0);
+          a1 = mfma_bf(fa.h, xs[kb].l, a1);
+          a0 = mfma_bf(fa.h, xs[kb].m, a0);
+          a1 = mfma_bf(fa.m, xs[kb].m, a1);
+          a0 = mfma_bf(fa.h, xs[kb].h, a0);
+        }
         __builtin_amdgcn_sched_barrier(0);
         fa = fb;
       }

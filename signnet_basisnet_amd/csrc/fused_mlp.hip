@@ -26,7 +26,8 @@ struct MlpStruct {
   const void* w[SN_MLP_MAX_LAYERS];
 };
 
-template <int NT>
+// PREC: the product set of every Linear of the chain (fused_common.hpp)
+template <int NT, int PREC = PREC_HIGHEST>
 __global__ __launch_bounds__(MLP_R * 4, 2) void k_mlp_chain(MlpStruct S) {
   constexpr int NKB = (NT + 1) / 2;
   using Ring = WRing<NT>;
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(MLP_R * 4, 2) void k_mlp_chain(MlpStruct S) {
       if (wave_live) split_rows<NT>(in, sp);
       const bool last = l + 1 == S.n_layers;
       const void* nxt = last ? S.w[0] : S.w[l + 1];            // the next bin restarts the stream at the first matrix
-      wg_gemm_split<NT, NT, false>(ring, S.w[l], nxt, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b, f32x4, f32x4, f32x4) {
+      wg_gemm_split<NT, NT, false, true, 4, SPLIT_RING, PREC>(ring, S.w[l], nxt, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b, f32x4, f32x4, f32x4) {
         const f32x4 v = acc + b;
         in[ot] = last ? v : relu4(v);
       });
@@ -94,13 +95,13 @@ __global__ __launch_bounds__(MLP_R * 4, 2) void k_mlp_chain(MlpStruct S) {
   ring.drain();
 }
 
-template <int NT>
+template <int NT, int PREC = PREC_HIGHEST>
 static int launch_mlp(const MlpStruct& S, hipStream_t st) {
   const size_t lds = (size_t)WRing<NT>::BYTES;
   static int cus = 0;
   if (cus == 0) {
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_chain<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_chain<NT, PREC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return fail(SN_ERR_LAUNCH, "sn_mlp_chain_f32: cannot raise the dynamic LDS limit to %zu", lds);
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
@@ -109,7 +110,7 @@ static int launch_mlp(const MlpStruct& S, hipStream_t st) {
   const int64_t nbins = (S.R + MLP_R - 1) / MLP_R;
   const int64_t cap = 2 * (int64_t)cus;
   const int64_t grid = nbins < cap ? nbins : cap;
-  hipLaunchKernelGGL((k_mlp_chain<NT>), dim3((unsigned)grid), dim3(MLP_R * 4), lds, st, S);
+  hipLaunchKernelGGL((k_mlp_chain<NT, PREC>), dim3((unsigned)grid), dim3(MLP_R * 4), lds, st, S);
   return SN_OK;
 }
 
@@ -117,13 +118,27 @@ static int launch_mlp(const MlpStruct& S, hipStream_t st) {
 
 using namespace sn;
 
-extern "C" int sn_mlp_chain_f32(const float* x, int ldx, int64_t R, int d_in, const int32_t* nvalid, int K, const void* const* weights,
-                                int n_layers, int d_pad, float* y, int ldy, int d_out, void* stream) {
+template <int PREC>
+static int dispatch_mlp(int nt, const MlpStruct& S, hipStream_t st) {
+  switch (nt) {
+    case 3: return launch_mlp<3, PREC>(S, st);
+    case 4: return launch_mlp<4, PREC>(S, st);
+    case 5: return launch_mlp<5, PREC>(S, st);
+    case 6: return launch_mlp<6, PREC>(S, st);
+    case 7: return launch_mlp<7, PREC>(S, st);
+    default: return launch_mlp<8, PREC>(S, st);
+  }
+}
+
+extern "C" int sn_mlp_chain_prec_f32(const float* x, int ldx, int64_t R, int d_in, const int32_t* nvalid, int K, const void* const* weights,
+                                     int n_layers, int d_pad, float* y, int ldy, int d_out, int precision, void* stream) {
   SN_REQUIRE(x && weights && y && R >= 0 && d_in >= 1 && d_out >= 1 && ldx >= d_in && ldy >= d_out, "sn_mlp_chain_f32: bad arguments");
   SN_REQUIRE(n_layers >= 1 && n_layers <= SN_MLP_MAX_LAYERS, "sn_mlp_chain_f32: %d layers unsupported (max %d)", n_layers, SN_MLP_MAX_LAYERS);
   SN_REQUIRE(d_pad >= 48 && d_pad <= 128 && (d_pad & 15) == 0 && d_in <= d_pad && d_out <= d_pad,
              "sn_mlp_chain_f32: padded width %d must be a multiple of 16 in [48, 128] covering d_in / d_out", d_pad);
   SN_REQUIRE(!nvalid || K > 0, "sn_mlp_chain_f32: nvalid needs K > 0");
+  SN_REQUIRE(precision == SN_PREC_HIGHEST || precision == SN_PREC_HIGH || precision == SN_PREC_MEDIUM,
+             "sn_mlp_chain_prec_f32: unknown matmul precision %d (SN_PREC_HIGHEST, SN_PREC_HIGH, SN_PREC_MEDIUM)", precision);
   if (R == 0) return SN_OK;
   MlpStruct S{x, R, ldx, d_in, nvalid, K, y, ldy, d_out, n_layers, {}};
   for (int l = 0; l < n_layers; ++l) {
@@ -132,15 +147,17 @@ extern "C" int sn_mlp_chain_f32(const float* x, int ldx, int64_t R, int d_in, co
   }
   int rc = SN_OK;
   hipStream_t st = (hipStream_t)stream;
-  switch (d_pad / 16) {
-    case 3: rc = launch_mlp<3>(S, st); break;
-    case 4: rc = launch_mlp<4>(S, st); break;
-    case 5: rc = launch_mlp<5>(S, st); break;
-    case 6: rc = launch_mlp<6>(S, st); break;
-    case 7: rc = launch_mlp<7>(S, st); break;
-    default: rc = launch_mlp<8>(S, st); break;
+  switch (precision) {
+    case SN_PREC_HIGH: rc = dispatch_mlp<PREC_HIGH>(d_pad / 16, S, st); break;
+    case SN_PREC_MEDIUM: rc = dispatch_mlp<PREC_MEDIUM>(d_pad / 16, S, st); break;
+    default: rc = dispatch_mlp<PREC_HIGHEST>(d_pad / 16, S, st); break;
   }
   if (rc != SN_OK) return rc;
   SN_CHECK_LAUNCH("sn_mlp_chain_f32");
   return SN_OK;
+}
+
+extern "C" int sn_mlp_chain_f32(const float* x, int ldx, int64_t R, int d_in, const int32_t* nvalid, int K, const void* const* weights,
+                                int n_layers, int d_pad, float* y, int ldy, int d_out, void* stream) {
+  return sn_mlp_chain_prec_f32(x, ldx, R, d_in, nvalid, K, weights, n_layers, d_pad, y, ldy, d_out, SN_PREC_HIGHEST, stream);
 }

@@ -92,7 +92,9 @@ constexpr int PHI_DESC_BYTES = 5 * PHI_GB * PHI_R * 4 + PHI_GB * PHI_R + PHI_GB 
 // BatchNorm that follows the ReLU is folded into W1', b1', the one in front of the next layer is (s, t)); all |kmax| slots of every
 // node are evaluated (zero-padded eigenvector columns included), the input is a dense [N, K] matrix, and the output rows are
 // P.reserved (= phi_out_dim) wide.  Instantiated separately so that the PyG kernels carry none of it.
-template <int NT, bool HID1, bool DGL = false>
+// PREC: the product set of the [d, d] Linears (fused_common.hpp); layer 0 of the HID1 variant, the aggregation, the epilogues and the
+// sign sum are the same arithmetic in every mode — truncation is symmetric in the sign, so the sum stays exactly sign-invariant.
+template <int NT, bool HID1, bool DGL = false, int PREC = PREC_HIGHEST>
 __global__ __launch_bounds__(PHI_WAVES * 64, 2) void k_phi_fused(PhiStruct S, sn_phi_params P) {
   constexpr int D = 16 * NT;
   constexpr int LD = D + 4;  // +4 floats: conflict-free ds_write_b128 of 8 consecutive rows
@@ -318,8 +320,8 @@ __global__ __launch_bounds__(PHI_WAVES * 64, 2) void k_phi_fused(PhiStruct S, sn
           const f32x4 v = (acc + b2) * s1 + h1;
           in[ot] = DGL ? v : relu4(v);
         };
-        if constexpr (LAG) wg_gemm_split_lag<NT, NT, BARKB>(ring, P.l0_w2, nxt, LIVE, sp, NoPre(), epi0);
-        else wg_gemm_split<NT, NT, false>(ring, P.l0_w2, nxt, LIVE, sp, NoPre(), epi0);
+        if constexpr (LAG) wg_gemm_split_lag<NT, NT, BARKB, PHI_WAVES, PREC>(ring, P.l0_w2, nxt, LIVE, sp, NoPre(), epi0);
+        else wg_gemm_split<NT, NT, false, true, PHI_WAVES, SPLIT_RING, PREC>(ring, P.l0_w2, nxt, LIVE, sp, NoPre(), epi0);
       }
       if (LIVE && !valid) {
 #pragma unroll
@@ -389,7 +391,7 @@ __global__ __launch_bounds__(PHI_WAVES * 64, 2) void k_phi_fused(PhiStruct S, sn
           pt = clock64();
 #endif
           split_rows<NT>(o, sp);
-          asm volatile("" :: "v"(sp[0].h), "v"(sp[NKB - 1].l));
+          asm volatile("" :: "v"(sp[0].h), "v"(last_plane<PREC>(sp[NKB - 1])));
           SN_ACCUM(6, pt);
         }
 #ifdef SN_PROFILE
@@ -397,15 +399,15 @@ __global__ __launch_bounds__(PHI_WAVES * 64, 2) void k_phi_fused(PhiStruct S, sn
 #endif
         // MaskedMLP: Linear . BN . ReLU . Linear [+b]
         auto epi1 = [&](int ot, f32x4 acc, f32x4 s0, f32x4 h0, f32x4, f32x4) { o[ot] = relu4(acc * s0 + h0); };
-        if constexpr (LAG) wg_gemm_split_lag<NT, NT, BARKB>(ring, Lp.w1s, Lp.w2s, LIVE, sp, NoPre(), epi1);
-        else wg_gemm_split<NT, NT, false>(ring, Lp.w1s, Lp.w2s, LIVE, sp, NoPre(), epi1);
+        if constexpr (LAG) wg_gemm_split_lag<NT, NT, BARKB, PHI_WAVES, PREC>(ring, Lp.w1s, Lp.w2s, LIVE, sp, NoPre(), epi1);
+        else wg_gemm_split<NT, NT, false, true, PHI_WAVES, SPLIT_RING, PREC>(ring, Lp.w1s, Lp.w2s, LIVE, sp, NoPre(), epi1);
         SN_ACCUM(7, pt);
 #ifdef SN_PROFILE
         pt = clock64();
 #endif
         if (LIVE) {
           split_rows<NT>(o, sp);
-          asm volatile("" :: "v"(sp[0].h), "v"(sp[NKB - 1].l));
+          asm volatile("" :: "v"(sp[0].h), "v"(last_plane<PREC>(sp[NKB - 1])));
         }
         SN_ACCUM(8, pt);
 #ifdef SN_PROFILE
@@ -418,8 +420,8 @@ __global__ __launch_bounds__(PHI_WAVES * 64, 2) void k_phi_fused(PhiStruct S, sn
           const f32x4 v = (acc + b2) * s1 + h1;
           in[ot] = DGL ? v : relu4(v) + prev;
         };
-        if constexpr (LAG) wg_gemm_split_lag<NT, NT, BARKB>(ring, Lp.w2s, nxt, LIVE, sp, pre2, epi2);
-        else wg_gemm_split<NT, NT, false>(ring, Lp.w2s, nxt, LIVE, sp, pre2, epi2);
+        if constexpr (LAG) wg_gemm_split_lag<NT, NT, BARKB, PHI_WAVES, PREC>(ring, Lp.w2s, nxt, LIVE, sp, pre2, epi2);
+        else wg_gemm_split<NT, NT, false, true, PHI_WAVES, SPLIT_RING, PREC>(ring, Lp.w2s, nxt, LIVE, sp, pre2, epi2);
         if (LIVE && !valid) {
 #pragma unroll
           for (int kk = 0; kk < NT; ++kk) in[kk] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -502,7 +504,7 @@ __global__ __launch_bounds__(PHI_WAVES * 64, 2) void k_phi_fused(PhiStruct S, sn
   SN_TL(7);
 }
 
-template <int NT, bool HID1, bool DGL = false>
+template <int NT, bool HID1, bool DGL = false, int PREC = PREC_HIGHEST>
 static int launch_phi(const PhiStruct& S, const sn_phi_params& P, hipStream_t st) {
   constexpr int LD = 16 * NT + 4;
   const size_t lds = (size_t)WRing<NT, PHI_WAVES, phi_lagged(NT) ? LAG_RING : SPLIT_RING>::BYTES + (size_t)(2 * PHI_R * LD) * sizeof(float) +
@@ -510,7 +512,7 @@ static int launch_phi(const PhiStruct& S, const sn_phi_params& P, hipStream_t st
   static int cus = 0;  // idempotent one-time setup (same values whichever thread wins)
   if (cus == 0) {
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_phi_fused<NT, HID1, DGL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_phi_fused<NT, HID1, DGL, PREC>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess)
       return fail(SN_ERR_LAUNCH, "sn_phi_fused_f32: cannot raise the dynamic LDS limit to %zu", lds);
     int dev = 0, n = 256;
@@ -519,12 +521,94 @@ static int launch_phi(const PhiStruct& S, const sn_phi_params& P, hipStream_t st
   }
   int64_t grid = S.max_bins < (int64_t)cus ? S.max_bins : (int64_t)cus;   // one 8-wave workgroup per CU (113 KB of LDS)
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_phi_fused<NT, HID1, DGL>), dim3((unsigned)grid), dim3(PHI_WAVES * 64), lds, st, S, P);
+  hipLaunchKernelGGL((k_phi_fused<NT, HID1, DGL, PREC>), dim3((unsigned)grid), dim3(PHI_WAVES * 64), lds, st, S, P);
   return SN_OK;
 }
 
+// The launch of one product set.  The two reduced sets are instantiated for the tile counts of the shipped configurations only
+// (hidden 64 / 108 / 128: NT 4, 7, 8; the DGL nets' padded widths 64 / 80 / 96: NT 4, 5, 6) and live in translation units of their
+// own (fused_phi_high.hip, fused_phi_medium.hip include this file with SN_PREC_TU set), so that they compile beside the default set.
+template <int PREC>
+static int dispatch_phi(const PhiStruct& S, const sn_phi_params& P, hipStream_t st) {
+  const int nt = (P.d + 15) / 16;
+  if constexpr (PREC != PREC_HIGHEST) {
+    if (P.hid0 == 1) {
+      switch (nt) {
+        case 4: return launch_phi<4, true, false, PREC>(S, P, st);
+        case 7: return launch_phi<7, true, false, PREC>(S, P, st);
+        case 8: return launch_phi<8, true, false, PREC>(S, P, st);
+      }
+    } else {
+      switch (nt) {
+        case 4: return launch_phi<4, false, false, PREC>(S, P, st);
+        case 7: return launch_phi<7, false, false, PREC>(S, P, st);
+        case 8: return launch_phi<8, false, false, PREC>(S, P, st);
+      }
+    }
+    return fail(SN_ERR_UNSUPPORTED, "sn_phi_fused_prec_f32: matmul precision %d is built for hidden widths with ceil(d/16) in {4, 7, 8} "
+                "(got d = %d); SN_PREC_HIGHEST serves every width", PREC, P.d);
+  } else if (P.hid0 == 1) {
+    switch (nt) {
+      case 1: return launch_phi<1, true>(S, P, st);
+      case 2: return launch_phi<2, true>(S, P, st);
+      case 3: return launch_phi<3, true>(S, P, st);
+      case 4: return launch_phi<4, true>(S, P, st);
+      case 5: return launch_phi<5, true>(S, P, st);
+      case 6: return launch_phi<6, true>(S, P, st);
+      case 7: return launch_phi<7, true>(S, P, st);
+      default: return launch_phi<8, true>(S, P, st);
+    }
+  } else {
+    switch (nt) {
+      case 1: return launch_phi<1, false>(S, P, st);
+      case 2: return launch_phi<2, false>(S, P, st);
+      case 3: return launch_phi<3, false>(S, P, st);
+      case 4: return launch_phi<4, false>(S, P, st);
+      case 5: return launch_phi<5, false>(S, P, st);
+      case 6: return launch_phi<6, false>(S, P, st);
+      case 7: return launch_phi<7, false>(S, P, st);
+      default: return launch_phi<8, false>(S, P, st);
+    }
+  }
+}
+
+template <int PREC>
+static int dispatch_phi_dgl(const PhiStruct& S, const sn_phi_params& P, hipStream_t st) {
+  if constexpr (PREC != PREC_HIGHEST) {
+    switch (P.d / 16) {
+      case 4: return launch_phi<4, false, true, PREC>(S, P, st);
+      case 5: return launch_phi<5, false, true, PREC>(S, P, st);
+      case 6: return launch_phi<6, false, true, PREC>(S, P, st);
+    }
+    return fail(SN_ERR_UNSUPPORTED, "sn_deepsigns_phi_prec_f32: matmul precision %d is built for the padded widths 64, 80 and 96 (got %d); "
+                "SN_PREC_HIGHEST serves every width", PREC, P.d);
+  } else {
+    switch (P.d / 16) {
+      case 3: return launch_phi<3, false, true>(S, P, st);
+      case 4: return launch_phi<4, false, true>(S, P, st);
+      case 5: return launch_phi<5, false, true>(S, P, st);
+      case 6: return launch_phi<6, false, true>(S, P, st);
+      default: return launch_phi<7, false, true>(S, P, st);
+    }
+  }
+}
+
+// the reduced product sets' launches, one translation unit each
+int phi_launch_high(const PhiStruct& S, const sn_phi_params& P, bool dgl, hipStream_t st);
+int phi_launch_medium(const PhiStruct& S, const sn_phi_params& P, bool dgl, hipStream_t st);
+#if defined(SN_PREC_TU) && SN_PREC_TU == SN_PREC_HIGH
+int phi_launch_high(const PhiStruct& S, const sn_phi_params& P, bool dgl, hipStream_t st) {
+  return dgl ? dispatch_phi_dgl<PREC_HIGH>(S, P, st) : dispatch_phi<PREC_HIGH>(S, P, st);
+}
+#elif defined(SN_PREC_TU) && SN_PREC_TU == SN_PREC_MEDIUM
+int phi_launch_medium(const PhiStruct& S, const sn_phi_params& P, bool dgl, hipStream_t st) {
+  return dgl ? dispatch_phi_dgl<PREC_MEDIUM>(S, P, st) : dispatch_phi<PREC_MEDIUM>(S, P, st);
+}
+#endif
+
 }  // namespace sn
 
+#ifndef SN_PREC_TU
 using namespace sn;
 
 #ifdef SN_TIMELINE
@@ -534,9 +618,17 @@ extern "C" int sn_timeline_read_phi(long long* host) { return (int)hipMemcpyFrom
 extern "C" int sn_prof_read_phi(long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_prof), sizeof(long long) * 64); }
 #endif
 
-extern "C" int sn_phi_fused_f32(const sn_phi_params* params, const float* eigen_vectors, const int32_t* graph_ptr,
-                                const int64_t* evoff, const int32_t* rowptr, const int32_t* col,
-                                const sn_plan_bins* bins, int kmax, int K, float* out, void* stream) {
+static int phi_launch(int precision, const PhiStruct& S, const sn_phi_params& P, bool dgl, hipStream_t st) {
+  switch (precision) {
+    case SN_PREC_HIGH: return phi_launch_high(S, P, dgl, st);
+    case SN_PREC_MEDIUM: return phi_launch_medium(S, P, dgl, st);
+    default: return dgl ? dispatch_phi_dgl<PREC_HIGHEST>(S, P, st) : dispatch_phi<PREC_HIGHEST>(S, P, st);
+  }
+}
+
+extern "C" int sn_phi_fused_prec_f32(const sn_phi_params* params, const float* eigen_vectors, const int32_t* graph_ptr,
+                                     const int64_t* evoff, const int32_t* rowptr, const int32_t* col,
+                                     const sn_plan_bins* bins, int kmax, int K, float* out, int precision, void* stream) {
   SN_REQUIRE(params && eigen_vectors && graph_ptr && evoff && rowptr && bins && out, "sn_phi_fused_f32: null pointer");
   SN_REQUIRE(bins->phi_bin_mem && bins->meta, "sn_phi_fused_f32: incomplete sn_plan_bins (phi_bin_mem, meta)");
   const sn_phi_params& P = *params;
@@ -551,43 +643,26 @@ extern "C" int sn_phi_fused_f32(const sn_phi_params* params, const float* eigen_
     SN_REQUIRE(L.w1s && L.w2s && L.eps, "sn_phi_fused_f32: layer %d parameters missing", l);
   }
   SN_REQUIRE(K > 0 && bins->phi_max_bins >= 0, "sn_phi_fused_f32: bad K / max_bins");
+  SN_REQUIRE(precision == SN_PREC_HIGHEST || precision == SN_PREC_HIGH || precision == SN_PREC_MEDIUM,
+             "sn_phi_fused_prec_f32: unknown matmul precision %d (SN_PREC_HIGHEST, SN_PREC_HIGH, SN_PREC_MEDIUM)", precision);
   if (bins->phi_max_bins == 0) return SN_OK;
   PhiStruct S{eigen_vectors, graph_ptr, evoff, rowptr, col, bins->phi_bin_mem, bins->meta, bins->phi_max_bins, kmax, K, out, 0};
-  hipStream_t st = (hipStream_t)stream;
-  int rc = SN_OK;
-  const int nt = (P.d + 15) / 16;
-  if (P.hid0 == 1) {
-    switch (nt) {
-      case 1: rc = launch_phi<1, true>(S, P, st); break;
-      case 2: rc = launch_phi<2, true>(S, P, st); break;
-      case 3: rc = launch_phi<3, true>(S, P, st); break;
-      case 4: rc = launch_phi<4, true>(S, P, st); break;
-      case 5: rc = launch_phi<5, true>(S, P, st); break;
-      case 6: rc = launch_phi<6, true>(S, P, st); break;
-      case 7: rc = launch_phi<7, true>(S, P, st); break;
-      default: rc = launch_phi<8, true>(S, P, st); break;
-    }
-  } else {
-    switch (nt) {
-      case 1: rc = launch_phi<1, false>(S, P, st); break;
-      case 2: rc = launch_phi<2, false>(S, P, st); break;
-      case 3: rc = launch_phi<3, false>(S, P, st); break;
-      case 4: rc = launch_phi<4, false>(S, P, st); break;
-      case 5: rc = launch_phi<5, false>(S, P, st); break;
-      case 6: rc = launch_phi<6, false>(S, P, st); break;
-      case 7: rc = launch_phi<7, false>(S, P, st); break;
-      default: rc = launch_phi<8, false>(S, P, st); break;
-    }
-  }
+  const int rc = phi_launch(precision, S, P, false, (hipStream_t)stream);
   if (rc != SN_OK) return rc;
   SN_CHECK_LAUNCH("sn_phi_fused_f32");
   return SN_OK;
 }
 
+extern "C" int sn_phi_fused_f32(const sn_phi_params* params, const float* eigen_vectors, const int32_t* graph_ptr,
+                                const int64_t* evoff, const int32_t* rowptr, const int32_t* col,
+                                const sn_plan_bins* bins, int kmax, int K, float* out, void* stream) {
+  return sn_phi_fused_prec_f32(params, eigen_vectors, graph_ptr, evoff, rowptr, col, bins, kmax, K, out, SN_PREC_HIGHEST, stream);
+}
+
 /* The DGL tree's GIN sign-invariant encoder, both signs and their sum, one launch (see sn_deepsigns_phi_f32 in signnet_hip.h). */
-extern "C" int sn_deepsigns_phi_f32(const sn_phi_params* params, const float* x, int ldx, const int32_t* graph_ptr,
-                                    const int32_t* rowptr, const int32_t* col, const sn_plan_bins* bins, int K, float* out,
-                                    void* stream) {
+extern "C" int sn_deepsigns_phi_prec_f32(const sn_phi_params* params, const float* x, int ldx, const int32_t* graph_ptr,
+                                         const int32_t* rowptr, const int32_t* col, const sn_plan_bins* bins, int K, float* out,
+                                         int precision, void* stream) {
   SN_REQUIRE(params && x && graph_ptr && rowptr && bins && out, "sn_deepsigns_phi_f32: null pointer");
   SN_REQUIRE(bins->phi_bin_mem && bins->meta, "sn_deepsigns_phi_f32: incomplete sn_plan_bins (phi_bin_mem, meta)");
   const sn_phi_params& P = *params;
@@ -600,18 +675,19 @@ extern "C" int sn_deepsigns_phi_f32(const sn_phi_params* params, const float* x,
     SN_REQUIRE(L.w1s && L.w2s && L.eps, "sn_deepsigns_phi_f32: layer %d parameters missing", l);
   }
   SN_REQUIRE(K > 0 && K <= 64 && ldx >= K && bins->phi_max_bins >= 0, "sn_deepsigns_phi_f32: bad K / ldx / max_bins");
+  SN_REQUIRE(precision == SN_PREC_HIGHEST || precision == SN_PREC_HIGH || precision == SN_PREC_MEDIUM,
+             "sn_deepsigns_phi_prec_f32: unknown matmul precision %d (SN_PREC_HIGHEST, SN_PREC_HIGH, SN_PREC_MEDIUM)", precision);
   if (bins->phi_max_bins == 0) return SN_OK;
   PhiStruct S{x, graph_ptr, nullptr, rowptr, col, bins->phi_bin_mem, bins->meta, bins->phi_max_bins, K, K, out, ldx};
-  hipStream_t st = (hipStream_t)stream;
-  int rc = SN_OK;
-  switch (P.d / 16) {
-    case 3: rc = launch_phi<3, false, true>(S, P, st); break;
-    case 4: rc = launch_phi<4, false, true>(S, P, st); break;
-    case 5: rc = launch_phi<5, false, true>(S, P, st); break;
-    case 6: rc = launch_phi<6, false, true>(S, P, st); break;
-    default: rc = launch_phi<7, false, true>(S, P, st); break;
-  }
+  const int rc = phi_launch(precision, S, P, true, (hipStream_t)stream);
   if (rc != SN_OK) return rc;
   SN_CHECK_LAUNCH("sn_deepsigns_phi_f32");
   return SN_OK;
 }
+
+extern "C" int sn_deepsigns_phi_f32(const sn_phi_params* params, const float* x, int ldx, const int32_t* graph_ptr,
+                                    const int32_t* rowptr, const int32_t* col, const sn_plan_bins* bins, int K, float* out,
+                                    void* stream) {
+  return sn_deepsigns_phi_prec_f32(params, x, ldx, graph_ptr, rowptr, col, bins, K, out, SN_PREC_HIGHEST, stream);
+}
+#endif  // !SN_PREC_TU

@@ -107,7 +107,9 @@ __device__ __forceinline__ float tile_rowsum(float v) {
 // split-packed [d, d] matrices = 720 KB of LDS-DMA per bin at d = 128, two 4-wave workgroups per CU = two streams; the register-attention
 // variants keep their rows in registers, so ONE 8-wave workgroup per CU could hold the same 8 nodes behind ONE stream.  Built (NW = 8),
 // bit-identical outputs, and measured SLOWER (61.5 -> 72.9 us on the headline batch): see rho_eight_waves() below.  Default: 4.
-template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4>
+// PREC: the product set of the six [d, d] projections of a layer (fused_common.hpp); the attention's score and value products (fp32
+// MFMA), the softmax, the LayerNorms and the slot sum are the same arithmetic in every mode.
+template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST>
 // (the LDS-attention variants hold two 64-row images beside the weight ring: one workgroup per CU fits, so they may use the whole
 //  register file of a SIMD — 512 registers per lane, no private segment)
 __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruct S, sn_rho_params P) {
@@ -342,10 +344,10 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
         // then v (swapped operands: V[key = 4g+r][c = 16ot + li]) with O^T = V^T.P^T in its epilogue (v is never stored).
         constexpr int CPH = NT / 4 > 0 ? NT / 4 : 1;   // 16-channel chunks per head
         f32x4 qf[NT], sc[4];
-        wg_gemm_split<NT, NT, false, false, NW>(ring, Lp.wq, Lp.wk, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { qf[ot] = acc * rtemp; });   // q / sqrt(dk)  (:52), as a multiply by the rounded reciprocal (<= 1 ulp)
+        wg_gemm_split<NT, NT, false, false, NW, SPLIT_RING, PREC>(ring, Lp.wq, Lp.wk, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { qf[ot] = acc * rtemp; });   // q / sqrt(dk)  (:52), as a multiply by the rounded reciprocal (<= 1 ulp)
 #pragma unroll
         for (int h = 0; h < 4; ++h) sc[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-        wg_gemm_split<NT, NT, false, false, NW>(ring, Lp.wk, Lp.wv, wave_live, sp, NoPre(), [&](int ot, f32x4 kf, f32x4, f32x4, f32x4, f32x4) {
+        wg_gemm_split<NT, NT, false, false, NW, SPLIT_RING, PREC>(ring, Lp.wk, Lp.wv, wave_live, sp, NoPre(), [&](int ot, f32x4 kf, f32x4, f32x4, f32x4, f32x4) {
           // lane (query = li, g) accumulates S[query][key = 4g + r] of head ot / CPH
           const int h = ot / CPH < 4 ? ot / CPH : 3;
           sc[h] = mfma16(kf[0], qf[ot][0], sc[h]);
@@ -371,7 +373,7 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
           }
         }
         SN_STAMP(4);
-        wg_gemm_split<NT, NT, true, false, NW>(ring, Lp.wv, Lp.wfc, wave_live, sp, NoPre(), [&](int ot, f32x4 vt, f32x4, f32x4, f32x4, f32x4) {
+        wg_gemm_split<NT, NT, true, false, NW, SPLIT_RING, PREC>(ring, Lp.wv, Lp.wfc, wave_live, sp, NoPre(), [&](int ot, f32x4 vt, f32x4, f32x4, f32x4, f32x4) {
           // O^T[c][query] = sum_key V[key][c] P[query][key]  -> lane (query, g) holds O[query][16*ot + 4g + r]
           const int h = ot / CPH < 4 ? ot / CPH : 3;
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -383,8 +385,8 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
         });
       } else {
         // ======== attention through LDS (nodes of more than 16 slots span several waves' tiles) ========
-        wg_gemm_split<NT, NT, false, false, NW>(ring, Lp.wq, Lp.wk, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(Ar + 16 * ot + 4 * g, acc); });
-        wg_gemm_split<NT, NT, false, false, NW>(ring, Lp.wk, Lp.wv, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(Br + 16 * ot + 4 * g, acc); });
+        wg_gemm_split<NT, NT, false, false, NW, SPLIT_RING, PREC>(ring, Lp.wq, Lp.wk, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(Ar + 16 * ot + 4 * g, acc); });
+        wg_gemm_split<NT, NT, false, false, NW, SPLIT_RING, PREC>(ring, Lp.wk, Lp.wv, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(Br + 16 * ot + 4 * g, acc); });
         lds_barrier();
         float qh[DKMAX];
         const int hc = g * dk;
@@ -392,7 +394,7 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
 #pragma unroll
         for (int c = 0; c < DKMAX; ++c) qh[c] = (c < dk && wave_live) ? Ar[hc + c] / temp : 0.f;
         // (q rows are written and read by the same wave only: no barrier before A is reused for v)
-        wg_gemm_split<NT, NT, false, false, NW>(ring, Lp.wv, Lp.wfc, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(Ar + 16 * ot + 4 * g, acc); });
+        wg_gemm_split<NT, NT, false, false, NW, SPLIT_RING, PREC>(ring, Lp.wv, Lp.wfc, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(Ar + 16 * ot + 4 * g, acc); });
         lds_barrier();
         {
         float m = -INFINITY;
@@ -492,7 +494,7 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
       // fc(o) + x -> LayerNorm                                      (transformer_module.py:99-101)
       if (wave_live) split_rows<NT>(o, sp);
       if (ONE) load_x();   // the residual operand, straight from the input buffer (see ONE above)
-      wg_gemm_split<NT, NT, false, false, NW>(ring, Lp.wfc, Lp.w1, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { x[ot] = acc + x[ot]; });   // residual in place: one row array for the whole layer
+      wg_gemm_split<NT, NT, false, false, NW, SPLIT_RING, PREC>(ring, Lp.wfc, Lp.w1, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { x[ot] = acc + x[ot]; });   // residual in place: one row array for the whole layer
       SN_STAMP(6);
       if (wave_live) {
         int gl = g;
@@ -502,14 +504,14 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
       }
       SN_STAMP(7);
       // FFN: w2(relu(w1 y + b1)) + b2 + y -> LayerNorm               (transformer_module.py:113-127)
-      wg_gemm_split<NT, NT, false, true, NW>(ring, Lp.w1, Lp.w2, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b1, f32x4, f32x4, f32x4) { o[ot] = relu4(acc + b1); });
+      wg_gemm_split<NT, NT, false, true, NW, SPLIT_RING, PREC>(ring, Lp.w1, Lp.w2, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b1, f32x4, f32x4, f32x4) { o[ot] = relu4(acc + b1); });
       SN_STAMP(8);
       if (wave_live) split_rows<NT>(o, sp);
 #ifdef SN_PROFILE
-      asm volatile("" :: "v"(sp[0].h), "v"(sp[NKB - 1].l));
+      asm volatile("" :: "v"(sp[0].h), "v"(last_plane<PREC>(sp[NKB - 1])));
 #endif
       SN_STAMP(14);
-      wg_gemm_split<NT, NT, false, true, NW>(ring, Lp.w2, wafter, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b2, f32x4, f32x4, f32x4) { x[ot] = acc + b2 + x[ot]; });
+      wg_gemm_split<NT, NT, false, true, NW, SPLIT_RING, PREC>(ring, Lp.w2, wafter, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b2, f32x4, f32x4, f32x4) { x[ot] = acc + b2 + x[ot]; });
       SN_STAMP(9);
       if (wave_live) {
         int gl = g;
@@ -577,7 +579,7 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
 //   * the slot sum is a [members x rows] . [rows x channels] product on the fp32 MFMA from the image (exact products by 0 / 1).
 // Reference semantics: model_utils/transformer_module.py:27-127 (post-LN encoder layer, softmax over the node's valid slots).
 // =====================================================================================================
-template <int NT, bool ONE, bool COLS>
+template <int NT, bool ONE, bool COLS, int PREC = PREC_HIGHEST>
 __global__ __launch_bounds__(RHO_R * 4, ONE ? 2 : 1) void k_rho_wide(RhoStruct S, sn_rho_params P) {
   static_assert(NT == 4 || NT == 8, "head width 16 or 32");
   constexpr int D = 16 * NT;
@@ -723,8 +725,8 @@ __global__ __launch_bounds__(RHO_R * 4, ONE ? 2 : 1) void k_rho_wide(RhoStruct S
       if (wave_live) split_rows<NT>(x, sp);
       {
         f32x4 qf[NT];
-        wg_gemm_split<NT, NT, false, false>(ring, Lp.wq, Lp.wk, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { qf[ot] = acc * rtemp; });
-        wg_gemm_split<NT, NT, false, false>(ring, Lp.wk, Lp.wv, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(IMGr + 16 * ot + 4 * g, acc); });
+        wg_gemm_split<NT, NT, false, false, 4, SPLIT_RING, PREC>(ring, Lp.wq, Lp.wk, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { qf[ot] = acc * rtemp; });
+        wg_gemm_split<NT, NT, false, false, 4, SPLIT_RING, PREC>(ring, Lp.wk, Lp.wv, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(IMGr + 16 * ot + 4 * g, acc); });
         lds_barrier();
         // S^T tile = K_tile Q^T on the fp32 MFMA: A[i = key li][k] = k[key][c], B[k][j = query li] = q[query][c], c = 16 ot + 4 g + t
         // (both operands of a lane are values of its own lane row) -> lane (li, g) holds S[query li][key 16 kt + 4 g + t]
@@ -776,7 +778,7 @@ __global__ __launch_bounds__(RHO_R * 4, ONE ? 2 : 1) void k_rho_wide(RhoStruct S
           }
         }
         lds_barrier();   // every wave has read its keys: the image receives v
-        wg_gemm_split<NT, NT, false, false>(ring, Lp.wv, Lp.wfc, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(IMGr + 16 * ot + 4 * g, acc); });
+        wg_gemm_split<NT, NT, false, false, 4, SPLIT_RING, PREC>(ring, Lp.wv, Lp.wfc, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { lds_st4(IMGr + 16 * ot + 4 * g, acc); });
         lds_barrier();
         // O^T tile = V^T P^T: A[i = channel li][k = key 4 g + s] = v[key][16 ot + li], B[k][j = query li] = P[query][key] (my own
         // register s) -> lane (li, g) holds O[query li][16 ot + 4 g + r]: the operand layout of the output projection
@@ -798,7 +800,7 @@ __global__ __launch_bounds__(RHO_R * 4, ONE ? 2 : 1) void k_rho_wide(RhoStruct S
       // fc(o) + x -> LayerNorm                                      (transformer_module.py:99-101)
       if (wave_live) split_rows<NT>(o, sp);
       if (ONE) load_x();   // the residual operand, straight from the input buffer
-      wg_gemm_split<NT, NT, false, false>(ring, Lp.wfc, Lp.w1, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { x[ot] = acc + x[ot]; });
+      wg_gemm_split<NT, NT, false, false, 4, SPLIT_RING, PREC>(ring, Lp.wfc, Lp.w1, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4, f32x4, f32x4, f32x4) { x[ot] = acc + x[ot]; });
       if (wave_live) {
         int gl = g;
         asm volatile("" : "+v"(gl));
@@ -806,9 +808,9 @@ __global__ __launch_bounds__(RHO_R * 4, ONE ? 2 : 1) void k_rho_wide(RhoStruct S
         split_rows<NT>(x, sp);
       }
       // FFN: w2(relu(w1 y + b1)) + b2 + y -> LayerNorm               (transformer_module.py:113-127)
-      wg_gemm_split<NT, NT, false>(ring, Lp.w1, Lp.w2, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b1, f32x4, f32x4, f32x4) { o[ot] = relu4(acc + b1); });
+      wg_gemm_split<NT, NT, false, true, 4, SPLIT_RING, PREC>(ring, Lp.w1, Lp.w2, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b1, f32x4, f32x4, f32x4) { o[ot] = relu4(acc + b1); });
       if (wave_live) split_rows<NT>(o, sp);
-      wg_gemm_split<NT, NT, false>(ring, Lp.w2, wafter, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b2, f32x4, f32x4, f32x4) { x[ot] = acc + b2 + x[ot]; });
+      wg_gemm_split<NT, NT, false, true, 4, SPLIT_RING, PREC>(ring, Lp.w2, wafter, wave_live, sp, NoPre(), [&](int ot, f32x4 acc, f32x4 b2, f32x4, f32x4, f32x4) { x[ot] = acc + b2 + x[ot]; });
       if (wave_live) {
         int gl = g;
         asm volatile("" : "+v"(gl));
@@ -852,7 +854,7 @@ __global__ __launch_bounds__(RHO_R * 4, ONE ? 2 : 1) void k_rho_wide(RhoStruct S
   ring.drain();
 }
 
-template <int NT, bool ONE, bool COLS>
+template <int NT, bool ONE, bool COLS, int PREC = PREC_HIGHEST>
 static int launch_rho_wide(const RhoStruct& S, const sn_rho_params& P, int64_t bins_bound, hipStream_t st) {
   constexpr int LD = 16 * NT + 4;
   const size_t lds_fixed = (size_t)WRing<NT>::BYTES + (size_t)(RHO_R * LD) * sizeof(float);
@@ -861,7 +863,7 @@ static int launch_rho_wide(const RhoStruct& S, const sn_rho_params& P, int64_t b
   static int cus = 0;
   if (cus == 0) {
     if (lds_max > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_rho_wide<NT, ONE, COLS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_rho_wide<NT, ONE, COLS, PREC>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_max) != hipSuccess)
       return fail(SN_ERR_LAUNCH, "sn_rho_fused_f32: cannot raise the dynamic LDS limit to %zu", lds_max);
     int dev = 0, n = 256;
@@ -870,11 +872,11 @@ static int launch_rho_wide(const RhoStruct& S, const sn_rho_params& P, int64_t b
   }
   int64_t grid = bins_bound < (int64_t)2 * cus ? bins_bound : (int64_t)2 * cus;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_rho_wide<NT, ONE, COLS>), dim3((unsigned)grid), dim3(RHO_R * 4), lds, st, S, P);
+  hipLaunchKernelGGL((k_rho_wide<NT, ONE, COLS, PREC>), dim3((unsigned)grid), dim3(RHO_R * 4), lds, st, S, P);
   return SN_OK;
 }
 
-template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4>
+template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST>
 static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_bound, hipStream_t st) {
   constexpr int LD = 16 * NT + 4;
   // (the LayerNorm vectors of the layers the net HAS, not of SN_RHO_MAX_LAYERS: 47 KB instead of 61 for the register-attention variant
@@ -885,7 +887,7 @@ static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_b
   static int cus = 0;
   if (cus == 0) {
     if (lds_max > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_rho_fused<NT, REGATTN, ONE, HP, NW>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_rho_fused<NT, REGATTN, ONE, HP, NW, PREC>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_max) != hipSuccess)
       return fail(SN_ERR_LAUNCH, "sn_rho_fused_f32: cannot raise the dynamic LDS limit to %zu", lds_max);
     int dev = 0, n = 256;
@@ -900,7 +902,7 @@ static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_b
   grid = cus;
 #endif
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_rho_fused<NT, REGATTN, ONE, HP, NW>), dim3((unsigned)grid), dim3(64 * NW), lds, st, S, P);
+  hipLaunchKernelGGL((k_rho_fused<NT, REGATTN, ONE, HP, NW, PREC>), dim3((unsigned)grid), dim3(64 * NW), lds, st, S, P);
   return SN_OK;
 }
 
@@ -914,38 +916,105 @@ static bool rho_eight_waves() {
   return v == 1;
 }
 
-template <bool REGATTN, bool ONE>
+template <bool REGATTN, bool ONE, int PREC = PREC_HIGHEST>
 static int dispatch_rho(int nt, const RhoStruct& S, const sn_rho_params& P, int64_t bound, hipStream_t st) {
-  if constexpr (REGATTN) {
-    // the common widths on 8-wave workgroups (one weight stream per CU)
-    if (rho_eight_waves()) {
-      if (nt == 8) return launch_rho<8, true, ONE, false, 8>(S, P, bound, st);
-      if (nt == 4) return launch_rho<4, true, ONE, false, 8>(S, P, bound, st);
+  if constexpr (PREC != PREC_HIGHEST) {
+    // the reduced product sets: the tile counts of the shipped configurations (hidden 64 / 108 / 128), four-wave workgroups
+    switch (nt) {
+      case 4: return launch_rho<4, REGATTN, ONE, false, 4, PREC>(S, P, bound, st);
+      case 7: return launch_rho<7, REGATTN, ONE, false, 4, PREC>(S, P, bound, st);
+      case 8: return launch_rho<8, REGATTN, ONE, false, 4, PREC>(S, P, bound, st);
     }
-  }
-  switch (nt) {
-    case 1: return launch_rho<1, REGATTN, ONE>(S, P, bound, st);
-    case 2: return launch_rho<2, REGATTN, ONE>(S, P, bound, st);
-    case 3: return launch_rho<3, REGATTN, ONE>(S, P, bound, st);
-    case 4: return launch_rho<4, REGATTN, ONE>(S, P, bound, st);
-    case 5: return launch_rho<5, REGATTN, ONE>(S, P, bound, st);
-    case 6: return launch_rho<6, REGATTN, ONE>(S, P, bound, st);
-    case 7: return launch_rho<7, REGATTN, ONE>(S, P, bound, st);
-    default: return launch_rho<8, REGATTN, ONE>(S, P, bound, st);
+    return fail(SN_ERR_UNSUPPORTED, "sn_rho_fused_prec_f32: matmul precision %d is built for hidden widths with ceil(d/16) in {4, 7, 8} "
+                "(got d = %d); SN_PREC_HIGHEST serves every width", PREC, P.d);
+  } else {
+    if constexpr (REGATTN) {
+      // the common widths on 8-wave workgroups (one weight stream per CU)
+      if (rho_eight_waves()) {
+        if (nt == 8) return launch_rho<8, true, ONE, false, 8>(S, P, bound, st);
+        if (nt == 4) return launch_rho<4, true, ONE, false, 8>(S, P, bound, st);
+      }
+    }
+    switch (nt) {
+      case 1: return launch_rho<1, REGATTN, ONE>(S, P, bound, st);
+      case 2: return launch_rho<2, REGATTN, ONE>(S, P, bound, st);
+      case 3: return launch_rho<3, REGATTN, ONE>(S, P, bound, st);
+      case 4: return launch_rho<4, REGATTN, ONE>(S, P, bound, st);
+      case 5: return launch_rho<5, REGATTN, ONE>(S, P, bound, st);
+      case 6: return launch_rho<6, REGATTN, ONE>(S, P, bound, st);
+      case 7: return launch_rho<7, REGATTN, ONE>(S, P, bound, st);
+      default: return launch_rho<8, REGATTN, ONE>(S, P, bound, st);
+    }
   }
 }
 
+// variant choice + launch of one product set (the arguments are those of sn_rho_fused_prec_f32, already checked)
+template <int PREC>
+static int rho_launch(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st) {
+  // attention in registers when every node has <= 16 slots and the head width is a multiple of 16
+  const bool one = P.n_layers == 1 && !P.has_pos;
+  // most valid slots any node can have: kmax when set, else the dense slot count K (= the largest graph; all eigenvectors)
+  const int kcap = (kmax > 0 && kmax < K) ? kmax : K;
+  SN_REQUIRE(kcap > 16 || bins->node_graph, "sn_rho_fused_f32: sn_plan_bins.node_graph is needed when every node has <= 16 slots");
+  if (P.head_pad > 0 && kcap <= 16) {
+    // head-padded packing: every head occupies head_pad (16 or 32) channels of the q/k/v/attention tensors, so the register
+    // attention applies to any d; all weights / vectors are zero-padded to heads*head_pad channels by the caller
+    SN_REQUIRE((P.head_pad == 16 || P.head_pad == 32) && P.head_pad >= P.d / P.heads,
+               "sn_rho_fused_f32: head_pad must be 16 or 32 and >= d/heads (got %d for d=%d)", P.head_pad, P.d);
+    if constexpr (PREC == PREC_HIGHEST) {
+      if (rho_eight_waves()) {
+        if (P.head_pad == 16) return one ? launch_rho<4, true, true, true, 8>(S, P, bound, st) : launch_rho<4, true, false, true, 8>(S, P, bound, st);
+        return one ? launch_rho<8, true, true, true, 8>(S, P, bound, st) : launch_rho<8, true, false, true, 8>(S, P, bound, st);
+      }
+    }
+    if (P.head_pad == 16) return one ? launch_rho<4, true, true, true, 4, PREC>(S, P, bound, st) : launch_rho<4, true, false, true, 4, PREC>(S, P, bound, st);
+    return one ? launch_rho<8, true, true, true, 4, PREC>(S, P, bound, st) : launch_rho<8, true, false, true, 4, PREC>(S, P, bound, st);
+  }
+  SN_REQUIRE(P.head_pad == 0, "sn_rho_fused_f32: head-padded parameters need <= 16 slots per node (got %d); pass the "
+             "natural-layout parameters for this batch", kcap);
+  const bool regattn = kcap <= 16 && ((P.d / P.heads) & 15) == 0;
+  const int nt = (P.d + 15) / 16;
+  if (!regattn && (P.d == 64 || P.d == 128)) {
+    // more than 16 slots per node, whole 16-channel tiles per head: one-image kernel, unaligned nodes; with all eigenvectors
+    // (kmax == 0) on phi's columns (k_rho_wide)
+    const bool cols = kmax == 0 && bins->phi_bin_mem != nullptr;
+    if (P.d == 128) {
+      if (cols) return one ? launch_rho_wide<8, true, true, PREC>(S, P, bound, st) : launch_rho_wide<8, false, true, PREC>(S, P, bound, st);
+      return one ? launch_rho_wide<8, true, false, PREC>(S, P, bound, st) : launch_rho_wide<8, false, false, PREC>(S, P, bound, st);
+    }
+    if (cols) return one ? launch_rho_wide<4, true, true, PREC>(S, P, bound, st) : launch_rho_wide<4, false, true, PREC>(S, P, bound, st);
+    return one ? launch_rho_wide<4, true, false, PREC>(S, P, bound, st) : launch_rho_wide<4, false, false, PREC>(S, P, bound, st);
+  }
+  return regattn ? (one ? dispatch_rho<true, true, PREC>(nt, S, P, bound, st) : dispatch_rho<true, false, PREC>(nt, S, P, bound, st))
+                 : (one ? dispatch_rho<false, true, PREC>(nt, S, P, bound, st) : dispatch_rho<false, false, PREC>(nt, S, P, bound, st));
+}
+
+// the reduced product sets' launches, one translation unit each (fused_rho_high.hip, fused_rho_medium.hip include this file with
+// SN_PREC_TU set), so that they compile beside the default set
+int rho_launch_high(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st);
+int rho_launch_medium(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st);
+#if defined(SN_PREC_TU) && SN_PREC_TU == SN_PREC_HIGH
+int rho_launch_high(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st) {
+  return rho_launch<PREC_HIGH>(S, P, bins, kmax, K, bound, st);
+}
+#elif defined(SN_PREC_TU) && SN_PREC_TU == SN_PREC_MEDIUM
+int rho_launch_medium(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st) {
+  return rho_launch<PREC_MEDIUM>(S, P, bins, kmax, K, bound, st);
+}
+#endif
+
 }  // namespace sn
 
+#ifndef SN_PREC_TU
 using namespace sn;
 
 #ifdef SN_PROFILE
 extern "C" int sn_prof_read_rho(long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_prof), sizeof(long long) * 64); }
 #endif
 
-extern "C" int sn_rho_fused_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
-                                const int32_t* graph_ptr, int64_t B, int64_t N, const sn_plan_bins* bins, int kmax,
-                                int K, float* out_sum, void* stream) {
+extern "C" int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
+                                     const int32_t* graph_ptr, int64_t B, int64_t N, const sn_plan_bins* bins, int kmax,
+                                     int K, float* out_sum, int precision, void* stream) {
   SN_REQUIRE(params && x && graph_ptr && bins && bins->rho_bin0 && bins->meta && out_sum, "sn_rho_fused_f32: null pointer");
   const sn_rho_params& P = *params;
   SN_REQUIRE(P.d > 0 && P.d <= 128 && (P.d & 3) == 0, "sn_rho_fused_f32: hidden width %d must be a multiple of 4 in (0, 128]", P.d);
@@ -959,49 +1028,28 @@ extern "C" int sn_rho_fused_f32(const sn_rho_params* params, const float* x, con
                "sn_rho_fused_f32: layer %d parameters missing", l);
   }
   SN_REQUIRE(K > 0 && B >= 0 && N >= 0 && B < (1ll << 31), "sn_rho_fused_f32: bad sizes");
+  SN_REQUIRE(precision == SN_PREC_HIGHEST || precision == SN_PREC_HIGH || precision == SN_PREC_MEDIUM,
+             "sn_rho_fused_prec_f32: unknown matmul precision %d (SN_PREC_HIGHEST, SN_PREC_HIGH, SN_PREC_MEDIUM)", precision);
   if (B == 0 || N == 0) return SN_OK;
   SN_REQUIRE(N < (1ll << 31), "sn_rho_fused_f32: too many nodes");
   RhoStruct S{x, eigen_values, graph_ptr, bins->rho_bin0, bins->meta, (int)B, kmax, K, out_sum, bins->node_graph, (int)N,
               bins->phi_bin_mem};
   hipStream_t st = (hipStream_t)stream;
   const int64_t bound = N + B;   // every bin holds at least one node
-  // attention in registers when every node has <= 16 slots and the head width is a multiple of 16
-  const bool one = P.n_layers == 1 && !P.has_pos;
-  // most valid slots any node can have: kmax when set, else the dense slot count K (= the largest graph; all eigenvectors)
-  const int kcap = (kmax > 0 && kmax < K) ? kmax : K;
   int rc;
-  SN_REQUIRE(kcap > 16 || bins->node_graph, "sn_rho_fused_f32: sn_plan_bins.node_graph is needed when every node has <= 16 slots");
-  if (P.head_pad > 0 && kcap <= 16) {
-    // head-padded packing: every head occupies head_pad (16 or 32) channels of the q/k/v/attention tensors, so the register
-    // attention applies to any d; all weights / vectors are zero-padded to heads*head_pad channels by the caller
-    SN_REQUIRE((P.head_pad == 16 || P.head_pad == 32) && P.head_pad >= P.d / P.heads,
-               "sn_rho_fused_f32: head_pad must be 16 or 32 and >= d/heads (got %d for d=%d)", P.head_pad, P.d);
-    if (rho_eight_waves()) {
-      if (P.head_pad == 16) rc = one ? launch_rho<4, true, true, true, 8>(S, P, bound, st) : launch_rho<4, true, false, true, 8>(S, P, bound, st);
-      else rc = one ? launch_rho<8, true, true, true, 8>(S, P, bound, st) : launch_rho<8, true, false, true, 8>(S, P, bound, st);
-    } else if (P.head_pad == 16) rc = one ? launch_rho<4, true, true, true>(S, P, bound, st) : launch_rho<4, true, false, true>(S, P, bound, st);
-    else rc = one ? launch_rho<8, true, true, true>(S, P, bound, st) : launch_rho<8, true, false, true>(S, P, bound, st);
-  } else {
-    SN_REQUIRE(P.head_pad == 0, "sn_rho_fused_f32: head-padded parameters need <= 16 slots per node (got %d); pass the "
-               "natural-layout parameters for this batch", kcap);
-    const bool regattn = kcap <= 16 && ((P.d / P.heads) & 15) == 0;
-    const int nt = (P.d + 15) / 16;
-    if (!regattn && (P.d == 64 || P.d == 128)) {
-      // more than 16 slots per node, whole 16-channel tiles per head: one-image kernel, unaligned nodes; with all eigenvectors
-      // (kmax == 0) on phi's columns (k_rho_wide)
-      const bool cols = kmax == 0 && bins->phi_bin_mem != nullptr;
-      if (P.d == 128) {
-        if (cols) rc = one ? launch_rho_wide<8, true, true>(S, P, bound, st) : launch_rho_wide<8, false, true>(S, P, bound, st);
-        else rc = one ? launch_rho_wide<8, true, false>(S, P, bound, st) : launch_rho_wide<8, false, false>(S, P, bound, st);
-      } else {
-        if (cols) rc = one ? launch_rho_wide<4, true, true>(S, P, bound, st) : launch_rho_wide<4, false, true>(S, P, bound, st);
-        else rc = one ? launch_rho_wide<4, true, false>(S, P, bound, st) : launch_rho_wide<4, false, false>(S, P, bound, st);
-      }
-    } else
-    rc = regattn ? (one ? dispatch_rho<true, true>(nt, S, P, bound, st) : dispatch_rho<true, false>(nt, S, P, bound, st))
-                 : (one ? dispatch_rho<false, true>(nt, S, P, bound, st) : dispatch_rho<false, false>(nt, S, P, bound, st));
+  switch (precision) {
+    case SN_PREC_HIGH: rc = rho_launch_high(S, P, bins, kmax, K, bound, st); break;
+    case SN_PREC_MEDIUM: rc = rho_launch_medium(S, P, bins, kmax, K, bound, st); break;
+    default: rc = rho_launch<PREC_HIGHEST>(S, P, bins, kmax, K, bound, st); break;
   }
   if (rc != SN_OK) return rc;
   SN_CHECK_LAUNCH("sn_rho_fused_f32");
   return SN_OK;
 }
+
+extern "C" int sn_rho_fused_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
+                                const int32_t* graph_ptr, int64_t B, int64_t N, const sn_plan_bins* bins, int kmax,
+                                int K, float* out_sum, void* stream) {
+  return sn_rho_fused_prec_f32(params, x, eigen_values, graph_ptr, B, N, bins, kmax, K, out_sum, SN_PREC_HIGHEST, stream);
+}
+#endif  // !SN_PREC_TU

@@ -234,11 +234,26 @@ class _FusedDeepSigns:
         self.n_rho, self.rp, self.d_in, self.out, self.K, self.masked = len(ws), rp, d_in, out, K, mod.masked
         self.ok = True
 
-    def run(self, plan, x, N):
+    def run(self, plan, x, N, precision=0):
+        """precision: SN_PREC_* of the Linears of both stage kernels (fused.PRECISIONS)."""
         import ctypes as C
         from ._lib import check, lib, ptr, stream
         K, out = self.K, self.out
         z = torch.empty(N * K, out, dtype=torch.float32, device=x.device)
+        if precision:
+            with ops._span("sn_deepsigns_phi_f32"):
+                check(lib().sn_deepsigns_phi_prec_f32(C.byref(self.phi), ptr(x), K, ptr(plan.graph_ptr), ptr(plan.rowptr), ptr(plan.col),
+                                                      C.byref(plan.bins.cstruct), K, ptr(z), int(precision), stream()),
+                      "sn_deepsigns_phi_prec_f32")
+            y = torch.empty(N, K, dtype=torch.float32, device=x.device)
+            with ops._span("sn_mlp_chain_f32"):
+                if self.masked:
+                    check(lib().sn_mlp_chain_prec_f32(ptr(z), out, N, out, ptr(plan.nvalid), K, self.rho_w, self.n_rho, self.rp, ptr(y), K, K,
+                                                      int(precision), stream()), "sn_mlp_chain_prec_f32")
+                else:
+                    check(lib().sn_mlp_chain_prec_f32(ptr(z), K * out, N, K * out, None, 0, self.rho_w, self.n_rho, self.rp, ptr(y), K, K,
+                                                      int(precision), stream()), "sn_mlp_chain_prec_f32")
+            return y, z
         with ops._span("sn_deepsigns_phi_f32"):
             check(lib().sn_deepsigns_phi_f32(C.byref(self.phi), ptr(x), K, ptr(plan.graph_ptr), ptr(plan.rowptr), ptr(plan.col),
                                              C.byref(plan.bins.cstruct), K, ptr(z), stream()), "sn_deepsigns_phi_f32")
@@ -358,6 +373,30 @@ class _DeepSignsBase(nn.Module):
         self.register_load_state_dict_post_hook(lambda m, keys=None: m._invalidate())
 
     fused_stages = True      # eval: the two stage kernels (3 launches); False forces the layer-at-a-time path
+
+    @property
+    def matmul_precision(self):
+        """"highest" (default) | "high" | "medium": how many of the six bf16 partial products every fp32 Linear of the fused eval
+        forward pays for (enc(g, x) + enc(g, -x) and the rho MLP chain: fused.PRECISIONS) — six, three ("bf16x3") or one.
+        The 8-layer encoder has no residual or LayerNorm to damp the error: "high" is 3e-5 .. 2.5e-4 of the output's scale on the
+        shipped shapes, "medium" 7e-3 .. 5e-2.  Not applied in train mode and on the layer path (`fused_stages = False`, shapes the
+        stage kernels do not take).  The reduced modes are built for padded hidden widths 64, 80 and 96 (hidden 49..96: every shipped
+        configuration); elsewhere assigning one raises ValueError — a mode is never replaced by another."""
+        return getattr(self, "_matmul_precision", "highest")
+
+    @matmul_precision.setter
+    def matmul_precision(self, name):
+        from . import fused
+        hidden = self.enc.layers[0].apply_func.lins[0].weight.shape[0]
+        out = self.enc.layers[-1].apply_func.lins[-1].weight.shape[0]
+        dp = max(48, 16 * ((max(hidden, out) + 15) // 16))          # the stage kernel's padded width (_FusedDeepSigns)
+        fused.precision_code(name, dp // 16, fused.REDUCED_TILES_DGL, what=f"this net (hidden width {hidden})")
+        self._matmul_precision = name                                # (nothing is repacked)
+
+    @property
+    def _prec(self):
+        from . import fused
+        return fused.PRECISIONS[self.matmul_precision]
 
     def _invalidate(self):
         self._prep = None
@@ -486,7 +525,7 @@ class _DeepSignsBase(nn.Module):
             # x was converted (dtype / layout) by a kernel queued on the caller's stream a moment ago: the side stream must see it
             side.wait_stream(torch.cuda.current_stream(xin.device))
         with torch.cuda.stream(side), _lib_mod.stream_scope():
-            y, z = self._fused.run(cached_plan(g, N, K), xin, N)
+            y, z = self._fused.run(cached_plan(g, N, K), xin, N, self._prec)
             ev = torch.cuda.Event()
             ev.record(side)
         src, dst = g.edges()
@@ -518,7 +557,7 @@ class _DeepSignsBase(nn.Module):
                 if getattr(self, "overlap", False):
                     self._side_wait = xin.data_ptr() != x.data_ptr()     # a copy / cast was queued on the caller's stream
                     return self._forward_side(g, xin, N, K)
-                y, _ = self._fused.run(cached_plan(g, N, K), xin, N)
+                y, _ = self._fused.run(cached_plan(g, N, K), xin, N, self._prec)
                 return y.view(N, K, 1)
         plan = self._plan(g, N)
         if not train:

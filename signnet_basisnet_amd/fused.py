@@ -11,6 +11,28 @@ from ._lib import check, lib, ptr, stream
 
 PHI_MAX_LAYERS = 16
 
+# Matmul precision of the split-packed Linears of the fused eval stages (SN_PREC_* of include/signnet_hip.h; the names are those of
+# torch.set_float32_matmul_precision): which partial products of the exact bf16 split x = h + m + l are issued, fp32 accumulate.
+#   "highest"  hh + hm + mh + hl + lh + mm   (the default: fp32-class, 1e-5 parity with the CPU reference)
+#   "high"     hh + hm + mh                  (dropped terms <= 2^-13 |x||w| per GEMM)
+#   "medium"   hh                            (dropped terms <= (2^-6 + 2^-14) |x||w| per GEMM: bf16 operands)
+PRECISIONS = ops.PRECISIONS      # {"highest": 0, "high": 1, "medium": 2}
+# tile counts ceil(width / 16) the two reduced modes are built for (csrc/fused_phi.hip, fused_rho.hip): the shipped configurations'
+REDUCED_TILES = (4, 7, 8)          # SignNetGNN: hidden 52..64, 100..128
+REDUCED_TILES_DGL = (4, 5, 6)      # DeepSigns phi: padded hidden width 64, 80, 96
+
+
+def precision_code(name, tiles=None, allowed=REDUCED_TILES, what="this model"):
+    """The SN_PREC_* value of a precision name; ValueError for an unknown name, or for a reduced mode at a width (in 16-channel
+    tiles) the kernels are not built for — a mode is refused, never replaced by another."""
+    if not isinstance(name, str) or name not in PRECISIONS:
+        raise ValueError(f"matmul_precision must be one of {sorted(PRECISIONS)} (got {name!r})")
+    code = PRECISIONS[name]
+    if code and tiles not in allowed:
+        raise ValueError(f"matmul_precision={name!r}: the reduced modes of the fused stages are built for widths of "
+                         f"{', '.join(str(t) for t in allowed)} 16-channel tiles; {what} has {tiles}. 'highest' serves every width")
+    return code
+
 
 class _PhiLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1s", "w2s", "eps")]
@@ -72,9 +94,10 @@ class PhiPlan:
             Lp.eps = hold(c.layer.eps.detach())
         self.params = P
 
-    def run(self, plan: ops.GraphPlan, eigen_vectors, K: int, out=None, zero_invalid=True):
+    def run(self, plan: ops.GraphPlan, eigen_vectors, K: int, out=None, zero_invalid=True, precision=0):
         """phi(x)+phi(-x) -> [N, K, d]; rows of invalid slots are left untouched (zero if `out` is None and
-        zero_invalid; the fused rho stage never reads them, so the forward skips the 24 MB memset)."""
+        zero_invalid; the fused rho stage never reads them, so the forward skips the 24 MB memset).  precision: SN_PREC_* of the
+        [d, d] Linears (PRECISIONS; the same packed weights serve every mode)."""
         ev = eigen_vectors
         if ev.dtype != torch.float32 or not ev.is_contiguous():
             raise ValueError("eigen_vectors must be contiguous float32")
@@ -82,6 +105,11 @@ class PhiPlan:
             alloc = torch.zeros if zero_invalid else torch.empty
             out = alloc(plan.N, K, self.d, dtype=torch.float32, device=ev.device)
         with ops._span("sn_phi_fused_f32"):
+            if precision:
+                check(lib().sn_phi_fused_prec_f32(C.byref(self.params), ptr(ev), ptr(plan.graph_ptr), ptr(plan.evoff),
+                                                  ptr(plan.rowptr), ptr(plan.col), C.byref(plan.bins.cstruct), plan.kmax, K,
+                                                  ptr(out), int(precision), stream()), "sn_phi_fused_prec_f32")
+                return out
             check(lib().sn_phi_fused_f32(C.byref(self.params), ptr(ev), ptr(plan.graph_ptr), ptr(plan.evoff),
                                          ptr(plan.rowptr), ptr(plan.col), C.byref(plan.bins.cstruct), plan.kmax, K,
                                          ptr(out), stream()), "sn_phi_fused_f32")
@@ -173,12 +201,18 @@ class RhoPlan:
             Lp.ln2_g, Lp.ln2_b = hold(vpad(f.norm.ln.weight)), hold(vpad(f.norm.ln.bias))
         return P
 
-    def run(self, plan: ops.GraphPlan, x, eigen_values, K: int):
-        """x [N*K, d] -> sum over valid slots of the encoder output, [N, d]."""
+    def run(self, plan: ops.GraphPlan, x, eigen_values, K: int, precision=0):
+        """x [N*K, d] -> sum over valid slots of the encoder output, [N, d].  precision: SN_PREC_* of the six [d, d] projections
+        of every layer (PRECISIONS)."""
         out = torch.empty(plan.N, self.d, dtype=torch.float32, device=x.device)
         kcap = min(plan.kmax, K) if plan.kmax > 0 else K
         params = self.params_hp if (self.params_hp is not None and kcap <= 16) else self.params
         with ops._span("sn_rho_fused_f32"):
+            if precision:
+                check(lib().sn_rho_fused_prec_f32(C.byref(params), ptr(x), ptr(eigen_values), ptr(plan.graph_ptr), plan.B,
+                                                  plan.N, C.byref(plan.bins.cstruct), plan.kmax, K, ptr(out), int(precision), stream()),
+                      "sn_rho_fused_prec_f32")
+                return out
             check(lib().sn_rho_fused_f32(C.byref(params), ptr(x), ptr(eigen_values), ptr(plan.graph_ptr), plan.B,
                                          plan.N, C.byref(plan.bins.cstruct), plan.kmax, K, ptr(out), stream()),
                   "sn_rho_fused_f32")

@@ -357,6 +357,37 @@ def pack_split(W: torch.Tensor, e0=None, e1=None, e2=None) -> torch.Tensor:
     return out
 
 
+# matmul precision names of the fused eval stages -> SN_PREC_* (include/signnet_hip.h; documented in fused.py)
+PRECISIONS = {"highest": 0, "high": 1, "medium": 2}
+
+
+def mlp_chain(x, weights, d_pad, d_out, nvalid=None, K=0, precision="highest", d_in=None):
+    """A whole MLP over the rows of x in one launch (sn_mlp_chain_prec_f32): y = W_{L-1} relu(... relu(W_0 x + b_0) ...) + b_{L-1}.
+    weights: split-packed Linears (pack_split of the [d_pad, d_pad] zero-padded matrix, e0 = bias), d_pad a multiple of 16 in
+    [48, 128].  x: [R, d_in] rows, or with nvalid (int32 [R]) the [R*K, d_in] slot rows whose first nvalid[r] are summed into row r.
+    precision: "highest" | "high" | "medium", the product set of every Linear of the chain (every width is built).  -> [R, d_out]."""
+    import ctypes as C
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)} (got {precision!r})")
+    require_cuda(x)
+    x = _f32c(x, "mlp_chain x")
+    if x.dim() != 2:
+        raise ValueError("mlp_chain: x must be [rows, d_in]")
+    d_in = x.shape[1] if d_in is None else int(d_in)
+    if nvalid is None:
+        R = x.shape[0]
+    else:
+        if nvalid.dtype != torch.int32 or K <= 0 or x.shape[0] != nvalid.numel() * K:
+            raise ValueError("mlp_chain: nvalid must be int32 [R] with x of R*K rows")
+        R = nvalid.numel()
+    ws = (C.c_void_p * len(weights))(*[ptr(w) for w in weights])
+    y = torch.empty(R, d_out, dtype=torch.float32, device=x.device)
+    with _span("sn_mlp_chain_f32"):
+        check(lib().sn_mlp_chain_prec_f32(ptr(x), x.stride(0), R, d_in, ptr(nvalid), int(K), ws, len(weights), int(d_pad), ptr(y),
+                                          d_out, d_out, PRECISIONS[precision], stream()), "sn_mlp_chain_prec_f32")
+    return y
+
+
 @dataclass
 class PackedLinear:
     wp: torch.Tensor

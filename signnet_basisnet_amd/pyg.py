@@ -306,6 +306,15 @@ class SignNetGNN(nn.Module):
 
     Extra keyword (not in the reference): `max_k` — use only the first `max_k` eigenvectors
     (BASELINE.json's "k=16" reading); None = all eigenvectors as the reference does.
+
+    `matmul_precision` (a property, default "highest"): how many of the six bf16 partial products every fp32 weight GEMM of the
+    fused eval phi and rho stages pays for — "highest" (six: the 1e-5 parity this package is tested at), "high" (three, "bf16x3":
+    ~2e-5 of the output's scale on the shipped configurations) or "medium" (one: bf16 operands, ~3e-3); fused.PRECISIONS,
+    DESIGN.md.  The packed weights are the same for every mode, so assignment costs nothing.  It does NOT apply to: train mode (the
+    differentiable path runs its own kernels at full precision), the layer path (`use_fused = False`, `return_stages`' layer
+    stages, and the graphs beyond the fused limits that strict mode re-runs there: such a batch has its oversize graphs at
+    "highest" and the rest at the chosen mode) and the GINE stage.  The reduced modes are built for hidden widths of 4, 7 or 8
+    16-channel tiles (52..64, 100..128); at any other width assigning one raises ValueError — a mode is never replaced by another.
     """
 
     def __init__(self, node_feat, edge_feat, n_hid, n_out, nl_signnet, nl_gnn, nl_rho=4, ignore_eigval=False,
@@ -321,6 +330,7 @@ class SignNetGNN(nn.Module):
         # nl_rho is fixed by the reference constructors (sign_net.py:123 ignores the argument)
         self.nl_rho = 4 if variant == "alchemy" else 1
         self.use_fused = True       # whole-stage kernels (eval mode); False = layer-at-a-time kernels only
+        self._matmul_precision = "highest"      # see the property below
         self.train_stages = True    # training: the one-pass link kernels of train_stage.py; False = one launch per op (autograd.py)
         # Fused stages require graphs of <= 64 nodes (and <= 192 edges for the GINE stage); a batch that violates this, a
         # malformed batch, or a discrete feature value outside its embedding table raises device-side flags.
@@ -349,6 +359,22 @@ class SignNetGNN(nn.Module):
         # nn.Module.load_state_dict on a PARENT (a wrapper, DDP, a bigger model) recurses through _load_from_state_dict and never
         # calls this module's load_state_dict override — the post hook below does fire for every submodule of that recursion
         self.register_load_state_dict_post_hook(_drop_prepared)
+
+    @property
+    def matmul_precision(self):
+        """"highest" | "high" | "medium": the product set of the fused eval phi / rho weight GEMMs (class docstring)."""
+        return getattr(self, "_matmul_precision", "highest")
+
+    @matmul_precision.setter
+    def matmul_precision(self, name):
+        d = self.cfg["n_hid"]
+        served = 0 < d <= 128 and d % 4 == 0            # the widths the stage kernels take at all (_prepare)
+        fused.precision_code(name, (d + 15) // 16 if served else None, what=f"this model (hidden width {d})")
+        self._matmul_precision = name                   # (nothing is repacked: the prepared parameters stay)
+
+    @property
+    def _prec(self):
+        return fused.PRECISIONS[self.matmul_precision]
 
     def reset_parameters(self):
         self.sign_net.reset_parameters()
@@ -856,12 +882,12 @@ class SignNetGNN(nn.Module):
             # for side A only (the previous forward's rho / GINE keep running)
             K_host = None if self.max_k else host_max_nodes(data)
             K = int(self.max_k) if self.max_k else (int(K_host) if K_host is not None else plan.check()[1])
-            x = P["phi_fused"].run(plan, data.eigen_vectors, K, zero_invalid=False).view(plan.N * K, d)
+            x = P["phi_fused"].run(plan, data.eigen_vectors, K, zero_invalid=False, precision=self._prec).view(plan.N * K, d)
             ev_a = torch.cuda.Event()
             ev_a.record(side_a)
         side_b.wait_event(ev_a)
         with torch.cuda.stream(side_b), _lib_mod.stream_scope():
-            s = P["rho_fused"].run(plan, x, data.eigen_values if want_vals else None, K)
+            s = P["rho_fused"].run(plan, x, data.eigen_values if want_vals else None, K, precision=self._prec)
             ev_b = torch.cuda.Event()
             ev_b.record(side_b)
         cur.wait_event(ev_b)
@@ -938,7 +964,7 @@ class SignNetGNN(nn.Module):
         # ---- phi(x) + phi(-x)      (GNN3d.forward, sign_net.py:28-44)
         phis = None
         if use_phi_fused and not return_stages:
-            x = P["phi_fused"].run(plan, data.eigen_vectors, K, zero_invalid=not use_rho_fused).view(N * K, d)
+            x = P["phi_fused"].run(plan, data.eigen_vectors, K, zero_invalid=not use_rho_fused, precision=self._prec).view(N * K, d)
         else:
             phis = []
             for sign in (0, 1):
@@ -953,12 +979,12 @@ class SignNetGNN(nn.Module):
         if return_stages:
             stages.update(phi_plus=phis[0].view(N, K, d), phi_minus=phis[1].view(N, K, d), phi=x.view(N, K, d))
             if P["phi_fused"] is not None:      # cross-check target for the fused kernel
-                stages["phi_fused"] = P["phi_fused"].run(plan, data.eigen_vectors, K)
+                stages["phi_fused"] = P["phi_fused"].run(plan, data.eigen_vectors, K, precision=self._prec)
                 stages["bins_meta"] = plan.bins.meta
         # ---- rho                    (SetTransformer.forward, sign_net.py:60-72)
         x_phi = x
         if use_rho_fused and not return_stages:
-            s = P["rho_fused"].run(plan, x_phi, data.eigen_values if want_vals else None, K)
+            s = P["rho_fused"].run(plan, x_phi, data.eigen_values if want_vals else None, K, precision=self._prec)
         else:
             if "eig" in P:
                 E_ = P["eig"]
@@ -990,7 +1016,10 @@ class SignNetGNN(nn.Module):
             stages["pos"] = pe
             stages["rho_sum"] = s
             if use_rho_fused:
-                stages["rho_sum_fused"] = P["rho_fused"].run(plan, x_phi, data.eigen_values if want_vals else None, K)
+                # (a reduced matmul_precision: the fused stages as the forward chains them — rho in that mode on phi in that mode;
+                #  "highest": on the layer path's phi, as ever)
+                rho_in = stages["phi_fused"].view(N * K, d) if (self._prec and "phi_fused" in stages) else x_phi
+                stages["rho_sum_fused"] = P["rho_fused"].run(plan, rho_in, data.eigen_values if want_vals else None, K, precision=self._prec)
         # ---- GINE network           (GNN.forward, model.py:36-64)
         xin = data.x.squeeze() if data.x.dim() > 1 and data.x.shape[-1] == 1 else data.x
         if "in_tabs" in P:

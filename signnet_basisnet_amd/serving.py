@@ -23,7 +23,8 @@ class GraphedDGLForward:
 
     Host-side decisions are frozen at capture time: the largest graph (<= 64 nodes for the stage kernels) and, for GatedGCN, the
     largest in-edge count are those of the example batch; a later batch beyond the kernels' limits is flagged on the device (NaN rows,
-    `net.check_last()` raises) instead of being re-routed to the layer path.
+    `net.check_last()` raises) instead of being re-routed to the layer path.  So is the sign-invariant net's `matmul_precision`: the
+    recorded stage launches carry the mode it had at capture time; set it before constructing this object.
 
     THE WEIGHTS ARE FROZEN AT CAPTURE TOO.  The recorded launches carry device pointers into the eval-time packed copies of the
     parameters (the nets' `_cache`, the sign-invariant net's `_prep` / `_fused`), which `train()`, `eval()`, `.to()`,

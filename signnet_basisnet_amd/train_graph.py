@@ -573,7 +573,9 @@ class DGLBucketedStep(_CaptureLRU):
 class GraphedForward:
     """A no-grad forward of FIXED shape captured once as a HIP graph: `fn` is a closure over static device tensors (BasisNet on the one
     grid graph of LearningFilters, a serving loop with a padded batch); `replay()` re-runs its launches with one graph launch and
-    returns the same output tensors, refreshed in place.  Copy new inputs into the tensors `fn` closes over before replaying."""
+    returns the same output tensors, refreshed in place.  Copy new inputs into the tensors `fn` closes over before replaying.
+    A module's `matmul_precision` travels with every stage launch, so the captured graph holds the mode the module had when `fn` was
+    captured; changing the property afterwards affects eager forwards and later captures only."""
 
     def __init__(self, fn, warmup=2):
         side = torch.cuda.Stream()
