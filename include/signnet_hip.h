@@ -387,7 +387,7 @@ int sn_ign_contract_2to1_f32(const float* X, int64_t b, int n, float* ops_out, f
  *          transform.py:14), total >= sum n_b^2 (the buffer doubles as the dense-adjacency scratch);
  *          pos_enc[N,k] (optional, may be NULL) = V[:, skip : skip+k], zero padded (DGL layout: skip = 1).
  * Eigenvector signs / the basis inside a repeated eigenvalue are arbitrary, as with LAPACK.  Graphs of up to 64 nodes
- * (one-sided Jacobi in registers, 16/32/64 lanes per graph).
+ * (one-sided Jacobi in registers, 16/32/64 lanes per graph); those of 65 .. 128 nodes: sn_laplacian_evd_large_f32 below.
  * work: int32[sn_evd_work_ints(B)].  status[4] (zeroed here): status[0] bit 0 = an edge leaves its graph / bad node id,
  * bit 1 = a graph has > 64 nodes (its outputs are left zero), bit 2 = no convergence, bit 3 = `total` too small;
  * status[1] = the largest number of Jacobi sweeps any wave ran (diagnostic). */
@@ -395,6 +395,21 @@ int64_t sn_evd_work_ints(int64_t B);
 int sn_laplacian_evd_f32(const int64_t* edge_index, int64_t E, const int32_t* graph_ptr, int64_t B, int64_t N,
                          int norm, int64_t* evoff, float* eigen_values, float* eigen_vectors, int64_t total,
                          float* pos_enc, int k, int skip, int32_t* work, int32_t* status, void* stream);
+
+/* The graphs of 65 .. sn_evd_large_max_nodes() (= 128) nodes of the same batch, which sn_laplacian_evd_f32 only flags: the same
+ * Jacobi method and numerics, one workgroup per graph, two columns per lane (the pair that rotates in one lane), in ONE launch for
+ * all such graphs.  Same arguments, but `evoff` is an INPUT (as sn_laplacian_evd_f32 laid it out: the prefix of n_b^2) and the
+ * outputs are the SAME eigen_values / eigen_vectors / pos_enc buffers: only the bytes of the graphs with 65 <= n_b <= 128 are
+ * written (their eigenvector blocks are cleared here first: the call does not rely on an earlier memset, and may come before or
+ * after sn_laplacian_evd_f32 on the stream); no byte of a smaller or larger graph is touched.
+ * work: int32[sn_evd_large_work_ints(B)].  status[4] of its own (zeroed here): status[0] value 1 = an edge with an end in a
+ * mid-size graph leaves its graph (or such a graph lies outside [0, N)), 2 = a graph has > 128 nodes (its outputs are not
+ * written), 4 = no convergence, 8 = a mid-size block does not fit `total`;  status[1] = the largest number of Jacobi sweeps. */
+int sn_evd_large_max_nodes(void);
+int64_t sn_evd_large_work_ints(int64_t B);
+int sn_laplacian_evd_large_f32(const int64_t* edge_index, int64_t E, const int32_t* graph_ptr, int64_t B, int64_t N,
+                               int norm, const int64_t* evoff, float* eigen_values, float* eigen_vectors, int64_t total,
+                               float* pos_enc, int k, int skip, int32_t* work, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of the layer-at-a-time train path.  The reference obtains these from torch.autograd over

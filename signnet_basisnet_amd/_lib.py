@@ -66,6 +66,9 @@ SIGNATURES = {
     "sn_segment_pool_f32": [_p, _l, _i, _p, _i, _p, _p],
     "sn_ign_contract_2to1_f32": [_p, _l, _i, _p, _p, _p],
     "sn_laplacian_evd_f32": [_p, _l, _p, _l, _l, _i, _p, _p, _p, _l, _p, _i, _i, _p, _p, _p],
+    "sn_laplacian_evd_large_f32": [_p, _l, _p, _l, _l, _i, _p, _p, _p, _l, _p, _i, _i, _p, _p, _p],
+    "sn_evd_large_max_nodes": [],                        # (returns the node limit, not a status)
+    "sn_evd_large_work_ints": [_l],                      # (int64 count: _SPECIAL_RESTYPE)
     "sn_linear_bn_scratch_floats": [_l, _i, _i],
     "sn_linear_bn_train_f32": [_p, _i, _l, _i, _p, _i, _p, _p, _i, _p, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_bn_train_stats_f32": [_p, _i, _l, _i, _p, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -128,7 +131,7 @@ SIGNATURES = {
     "sn_train_scalar_mlp_apply_f32": [_p, _p, _p],
     "sn_train_scalar_mlp_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p],
 }
-_SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64}
+_SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64}
 
 _lib = None
 
@@ -171,6 +174,7 @@ def lib():
         L.sn_gatedgcn_max_edges.restype = C.c_int
         L.sn_evd_work_ints.argtypes = [_l]
         L.sn_evd_work_ints.restype = C.c_int64
+        L.sn_evd_large_work_ints.restype = _SPECIAL_RESTYPE["sn_evd_large_work_ints"]
         L.sn_ign_contract_scratch_floats.argtypes = [_l, _i]
         L.sn_ign_contract_scratch_floats.restype = C.c_int64
         L.sn_train_linear_bwd_part_floats.argtypes = [_l, _i, _i, _i]

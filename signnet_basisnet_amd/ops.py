@@ -1021,6 +1021,40 @@ def laplacian_evd(edge_index, graph_ptr, N, total, norm=None, pos_enc_dim=0, ski
     return val, vec, evoff, pe, status
 
 
+EVD_LARGE_MAX_NODES = 128          # = sn_evd_large_max_nodes(): graphs of 65 .. 128 nodes go through sn_laplacian_evd_large_f32
+EVD_LARGE_STATUS = {1: EVD_STATUS[1], 2: "a graph has more than 128 nodes", 4: EVD_STATUS[4], 8: EVD_STATUS[8]}
+
+
+def laplacian_evd_large(edge_index, graph_ptr, N, total, evoff, val, vec, pe=None, norm=None, pos_enc_dim=0, skip=1):
+    """The graphs of 65 .. 128 nodes of a batch, into the buffers `laplacian_evd` returned (same val / vec / pe, `evoff` as laid out
+    there): one launch for all of them; no byte of a smaller or larger graph is touched.  Returns status int32[4] of its own."""
+    require_cuda(edge_index, graph_ptr, evoff, val, vec, pe)
+    if norm not in (None, "sym"):
+        raise ValueError(f"unsupported normalization {norm!r} (None or 'sym')")
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: expected int64 [2, E]")
+    if graph_ptr.dtype != torch.int32:
+        raise ValueError("graph_ptr: expected int32 [B+1]")
+    B, E = graph_ptr.numel() - 1, edge_index.shape[1]
+    if evoff.dtype != torch.int64 or evoff.numel() != B + 1 or not evoff.is_contiguous():
+        raise ValueError("evoff: expected contiguous int64 [B+1]")
+    if val.dtype != torch.float32 or vec.dtype != torch.float32 or not (val.is_contiguous() and vec.is_contiguous()):
+        raise ValueError("val / vec: expected contiguous float32")
+    if val.numel() < N or vec.numel() < total:
+        raise ValueError("val / vec: smaller than N / total")
+    if pos_enc_dim > 0 and (pe is None or pe.dtype != torch.float32 or not pe.is_contiguous() or tuple(pe.shape) != (N, pos_enc_dim)):
+        raise ValueError("pe: expected contiguous float32 [N, pos_enc_dim]")
+    edge_index = edge_index.contiguous()
+    dev = edge_index.device
+    work = torch.empty(int(lib().sn_evd_large_work_ints(B)), dtype=torch.int32, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    with _span("sn_laplacian_evd_large_f32"):
+        check(lib().sn_laplacian_evd_large_f32(ptr(edge_index), E, ptr(graph_ptr), B, N, 0 if norm is None else 1, ptr(evoff),
+                                               ptr(val), ptr(vec), total, ptr(pe) if pos_enc_dim > 0 else None, int(pos_enc_dim),
+                                               int(skip), ptr(work), ptr(status), stream()), "sn_laplacian_evd_large_f32")
+    return status
+
+
 def bn_fold_stats(weight, bias, mean, var, eps, c_pad=None):
     """(scale, shift) of a BatchNorm from explicit statistics (batch statistics of the train-mode / no-running-stats case)."""
     Cc = mean.numel()

@@ -45,7 +45,8 @@ class EVDTransform:
 
 # ---------------------------------------------------------------------------------------------------------------
 # Device-side, whole-batch variant: one call per collated batch instead of one eigh per sample in
-# the DataLoader workers.  All arithmetic is sn_laplacian_evd_f32 (csrc/evd.hip); torch only allocates.
+# the DataLoader workers.  All arithmetic is sn_laplacian_evd_f32 (csrc/evd.hip, graphs of up to 64 nodes) and
+# sn_laplacian_evd_large_f32 (csrc/evd_large.hip, 65 .. 128 nodes); torch only allocates.
 
 def _graph_ptr(batch, num_graphs, ptr=None):
     import torch
@@ -58,7 +59,7 @@ def _graph_ptr(batch, num_graphs, ptr=None):
 
 
 def _dense_eigh_on_device(edge_index, n0, n, norm):
-    """Graphs beyond the register kernel's 64 nodes: dense Laplacian + torch.linalg.eigh on the device (library call)."""
+    """Graphs beyond the Jacobi kernels' 128 nodes: dense Laplacian + torch.linalg.eigh on the device (library call)."""
     sel = (edge_index[0] >= n0) & (edge_index[0] < n0 + n) & (edge_index[0] != edge_index[1])
     s, d = edge_index[0][sel] - n0, edge_index[1][sel] - n0
     A = torch.zeros(n, n, dtype=torch.float32, device=edge_index.device)
@@ -79,6 +80,8 @@ def evd_laplacian_batch(edge_index, batch=None, num_graphs=None, norm=None, ptr=
 
     edge_index [2,E] int64 (device), and either `ptr` [B+1] (PyG Batch.ptr) or `batch` [N] ascending + num_graphs.
     `sizes` (host list of node counts) avoids the one host read of the graph sizes.
+    Graphs of up to 128 nodes are decomposed by the package's own kernels; with check=False nothing is read back from the device
+    (no status check, and a graph above 128 nodes, which needs the library route, is left unwritten).
     Returns (eigen_values [N], eigen_vectors [sum n_b^2], pos_enc [N,k] | None) in the reference's wire format
     (transform.py:12-15: ascending eigenvalues, V.reshape(-1) row-major per graph, blocks concatenated)."""
     from . import ops
@@ -89,15 +92,27 @@ def evd_laplacian_batch(edge_index, batch=None, num_graphs=None, norm=None, ptr=
     sizes = [int(v) for v in sizes]
     N, total = sum(sizes), sum(v * v for v in sizes)
     val, vec, evoff, pe, status = ops.laplacian_evd(edge_index, gp, N, total, norm, pos_enc_dim, skip)
+    # the sizes are known on the host: routing needs no device read.  65 .. 128 nodes: the second Jacobi kernel, queued behind the
+    # first on the same buffers; above 128: the library call below (the only part that needs `check`)
+    mid = any(64 < n <= ops.EVD_LARGE_MAX_NODES for n in sizes)
+    status_large = None
+    if mid:
+        status_large = ops.laplacian_evd_large(edge_index, gp, N, total, evoff, val, vec, pe, norm, pos_enc_dim, skip)
     if check:
-        st = int(status[0].item())
+        if mid:
+            st, st_large = (int(v) for v in torch.stack([status[0], status_large[0]]).tolist())      # one read for both words
+        else:
+            st, st_large = int(status[0].item()), 0
         if st & ~2:
             raise RuntimeError("sn_laplacian_evd_f32: " + "; ".join(m for b, m in ops.EVD_STATUS.items() if st & b & ~2))
-        if st & 2:
+        if st_large & ~2:
+            raise RuntimeError("sn_laplacian_evd_large_f32: "
+                               + "; ".join(m for b, m in ops.EVD_LARGE_STATUS.items() if st_large & b & ~2))
+        if st & 2 and any(n > ops.EVD_LARGE_MAX_NODES for n in sizes):
             n0 = 0
             off = 0
             for n in sizes:
-                if n > 64:
+                if n > ops.EVD_LARGE_MAX_NODES:
                     D, V = _dense_eigh_on_device(edge_index, n0, n, norm)
                     val[n0:n0 + n] = D
                     vec[off:off + n * n] = V.reshape(-1)
