@@ -426,8 +426,13 @@ int sn_laplacian_evd_large_f32(const int64_t* edge_index, int64_t E, const int32
  *   dz = scale*(g - d beta/M - xhat*d gamma/M), M = *count.  scratch: float[sn_bn_act_bwd_scratch_floats(R, C)].
  * sn_relu_bwd_f32: dx = dy*[y>0].
  * sn_masked_layernorm_bwd_f32: adjoint of sn_masked_layernorm_f32 (MaskedLN, masked_layers.py:22-32): du (gradient of
- *   both x and residual), d gamma, d beta.  scratch: float[sn_layernorm_bwd_scratch_floats(R, C)].
- * sn_set_attention_bwd_f32: adjoint of sn_set_attention_f32 (softmax recomputed): dq, dk, dv.
+ *   both x and residual), d gamma, d beta.  scratch: float[sn_layernorm_bwd_scratch_floats(R, C)].  C in {32, 64, 128, 256} with
+ *   x, residual, dy and du 16-byte aligned takes the vectorised kernel (a row in the registers of C/4 lanes, every operand read
+ *   once); every other width or alignment the one-wave-per-row kernel.  C <= 2048 (8 C floats of LDS).
+ * sn_set_attention_bwd_f32: adjoint of sn_set_attention_f32 (softmax recomputed): dq, dk, dv.  K <= 16 with dk in {16, 32, 64} and
+ *   q, k, v, dout 16-byte aligned runs on the matrix pipe (attention16.hip: one wave per (node, head), no LDS); every other shape
+ *   or alignment takes the one-wave LDS kernel, which needs (4 K dk + 2 K (K+1)) floats of LDS: above 160 KiB (K = 64 with
+ *   dk = 128) the call is refused with SN_ERR_ARG before anything is launched.
  * sn_gine_aggregate_bwd_f32: adjoint of sn_gine_aggregate_f32 w.r.t. the node features (dh) and the per-edge features
  *   (dee, [E,C] in edge-id order) over the REVERSE CSR (rows = source nodes, rev_col = destination, rev_eperm = edge id:
  *   sn_batch_plan on the flipped edge_index).  (GIN's adjoint is sn_gin_aggregate_f32 itself on the reverse CSR.)
@@ -441,7 +446,8 @@ int sn_laplacian_evd_large_f32(const int64_t* edge_index, int64_t E, const int32
  *   out-of-range indices contribute nothing and set bit 0 of *status (device int32, may be NULL); table_rows as in the forward.
  * sn_dot_f32: out[0] = sum a[i] b[i] (the GIN / GINE eps gradients).  scratch: float[256].
  * sn_adam_step_f32: one torch.optim.Adam step (no amsgrad; weight_decay added to the gradient) on a flat tensor; the gradient is
- *   read as g*grad_scale (1/world_size after a SUM all-reduce of data-parallel ranks). */
+ *   read as g*grad_scale (1/world_size after a SUM all-reduce of data-parallel ranks).  1 - beta2 and its bias correction are
+ *   formed in double from beta2 as the caller wrote it (the shortest decimal of the float), as torch does. */
 int64_t sn_linear_wgrad_scratch_floats(int64_t R, int d_in, int d_out);
 int sn_linear_wgrad_f32(const float* x, int ldx, const float* dy, int ldy, int64_t R, int d_in, int d_out,
                         const int32_t* nvalid, int K, float* dW, float* db, float* scratch, void* stream);

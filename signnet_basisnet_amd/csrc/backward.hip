@@ -5,6 +5,8 @@
 // signnet_hip.h has its hand-written adjoint; the Python side (signnet_basisnet_amd/autograd.py) only wires them
 // into torch.autograd.Function objects.  Same conventions as the forward: fp32 row matrices, a row r = node*K +
 // slot is valid iff slot < nvalid[node], invalid rows carry zero gradient.
+#include <stdlib.h>
+
 #include "common.hpp"
 
 namespace sn {
@@ -631,14 +633,15 @@ __global__ __launch_bounds__(256) void k_dot_partial(const float* __restrict__ a
 
 // ============================================================================ Adam (torch.optim.Adam, no amsgrad)
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                              float* __restrict__ v, int64_t n, float lr, float b1, float b2,
+                                              float omb2 /* 1 - beta2, formed in double on the host */, float eps,
                                               float wd, float bc1, float bc2_sqrt, float gscale) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   float gi = g[i] * gscale;
   if (wd != 0.f) gi += wd * p[i];
   const float mi = b1 * m[i] + (1.0f - b1) * gi;
-  const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+  const float vi = b2 * v[i] + omb2 * gi * gi;
   m[i] = mi;
   v[i] = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -897,13 +900,39 @@ extern "C" int sn_dot_f32(const float* a, const float* b, int64_t n, float* out,
   return SN_OK;
 }
 
+// The ABI carries beta2 as float, the caller wrote it as a decimal double (0.999), and torch.optim.Adam forms 1 - beta2 and the bias
+// correction from that double.  In float, 1 - 0.999f is 0.99998713e-3: the second moment of a step was 1.3e-5 (relative) below torch's
+// and float64's, and so was the bias correction under the update's square root (tests/test_adjoint_grid_gpu.py::test_adam_step, step 1
+// and 10 at the default betas).  The shortest decimal that reads back as the given float IS the caller's double for any beta written
+// with up to 7 significant digits; other values keep the float's own.  The first moment is left as it was: 1 - 0.9f is within 2.4e-7
+// of 0.1, and the eager / captured trajectory comparisons are sensitive to any change of rounding there.
+static double beta_as_written(float f) {
+  thread_local float seen[2] = {-1.f, -1.f};          // (formatted once per value, not once per step)
+  thread_local double as_double[2] = {0.0, 0.0};
+  thread_local int next = 0;
+  for (int i = 0; i < 2; ++i)
+    if (seen[i] == f) return as_double[i];
+  double d = (double)f;
+  char buf[40];
+  for (int digits = 1; digits <= 8; ++digits) {
+    snprintf(buf, sizeof buf, "%.*g", digits, (double)f);
+    const double t = strtod(buf, nullptr);
+    if ((float)t == f) { d = t; break; }
+  }
+  seen[next] = f;
+  as_double[next] = d;
+  next ^= 1;
+  return d;
+}
 extern "C" int sn_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                                 float eps, float weight_decay, int step, float grad_scale, void* stream) {
   SN_REQUIRE(p && g && m && v && n >= 0 && step >= 1, "sn_adam_step_f32: bad arguments");
   if (n == 0) return SN_OK;
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
-                     weight_decay, bc1, sqrtf(bc2), grad_scale);
+  const double b2 = beta_as_written(beta2);
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const double bc2 = 1.0 - pow(b2, (double)step);
+  hipLaunchKernelGGL(k_adam, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2,
+                     (float)(1.0 - b2), eps, weight_decay, bc1, (float)sqrt(bc2), grad_scale);
   SN_CHECK_LAUNCH("sn_adam_step_f32");
   return SN_OK;
 }

@@ -8,8 +8,11 @@ re-run in float64 on the same inputs and weights): the assertion then ATTRIBUTES
 close to the exact value as the fp32 CPU reference is:  max|hip - f64| <= max|ref32 - f64| + 1e-6 * max|f64|  — and it still
 has to be within 1e-5 of the exact value.  Nothing is ever waved through on a looser tolerance.
 """
+import sys
+
 import torch
 
+PU = sys.modules[__name__]          # (attributed() below names the constants as its callers do)
 REL = 1e-5          # north_star
 ATTR = 1e-6         # attribution slack: one part in 1e6 of the tensor's largest entry
 
@@ -39,6 +42,17 @@ def close(a, ref, what, rel=REL, ref64=None):
     assert e_hip <= e_cpu + ATTR * s64, (f"{what}: |hip - cpu32| {err / scale:.2e} exceeds {rel:g} and is not attributable to the fp32 CPU "
                                          f"reference: |hip - f64| {e_hip / s64:.2e} vs |cpu32 - f64| {e_cpu / s64:.2e} (relative)")
     return err / scale
+
+
+# |hip - f64| <= max(REL * scale, 2 |cpu32 - f64| + ATTR * scale), scale = max |f64|: the rule of the op- and stage-level adjoint tests
+# (tests/test_train_stage_gpu.py, tests/test_adjoint_grid_gpu.py).  Only the two CPU evaluations enter the bound.
+def attributed(hip, r32, r64, what):
+    hip, r32, r64 = hip.detach().cpu().double(), r32.detach().double(), r64.detach().double()
+    scale = max(r64.abs().max().item(), 1e-300)
+    e_hip, e_cpu = (hip - r64).abs().max().item(), (r32 - r64).abs().max().item()
+    assert e_hip <= max(PU.REL * scale, 2.0 * e_cpu + PU.ATTR * scale), \
+        f"{what}: |hip - f64| {e_hip / scale:.2e} vs |cpu32 - f64| {e_cpu / scale:.2e} (relative to max |f64| {scale:.3e})"
+    return e_hip / scale, e_cpu / scale
 
 
 def elementwise(a, ref, what, rtol=REL, ref64=None):

@@ -1,5 +1,6 @@
 """-m gpu: every adjoint kernel of csrc/backward.hip against torch.autograd on a float64 CPU restatement
-of the same op (the reference obtains these gradients from torch.autograd, main_alchemy.py:108)."""
+of the same op (the reference obtains these gradients from torch.autograd, main_alchemy.py:108).  One or two shapes per op; every
+dispatch branch of these kernels (widths, row counts, strides, alignment) is in tests/test_adjoint_grid_gpu.py."""
 import pytest
 import torch
 

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import parity_util as PU
+from parity_util import attributed
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -49,15 +50,6 @@ def ref_mlp2(x, p, masks, G, residual, relu_out, has_bn2=True):
             stats.append((mu1, v1))
         ys.append(y)
     return torch.cat(ys, 0), stats
-
-
-def attributed(hip, r32, r64, what):
-    hip, r32, r64 = hip.detach().cpu().double(), r32.detach().double(), r64.detach().double()
-    scale = max(r64.abs().max().item(), 1e-300)
-    e_hip, e_cpu = (hip - r64).abs().max().item(), (r32 - r64).abs().max().item()
-    assert e_hip <= max(PU.REL * scale, 2.0 * e_cpu + PU.ATTR * scale), \
-        f"{what}: |hip - f64| {e_hip / scale:.2e} vs |cpu32 - f64| {e_cpu / scale:.2e} (relative to max |f64| {scale:.3e})"
-    return e_hip / scale, e_cpu / scale
 
 
 CASES = [
