@@ -176,6 +176,57 @@ typedef struct sn_bucket_pack_dgl_args {
   int64_t N_cap, E_cap, B_cap;
 } sn_bucket_pack_dgl_args;
 int sn_bucket_pack_dgl(const sn_bucket_pack_dgl_args* args, void* stream);
+/* Device-resident graph store (data.GraphStore / data.DGLGraphStore): the training batch of B graphs, chosen by B graph indices in
+ * DEVICE memory, gathered straight into the capacity buffers above — what the reference's DataLoader collate (GINESignNetPyG/core/
+ * train.py:55-66, Alchemy/main_alchemy.py:99-110, GraphPrediction/train/train_ZINC_graph_regression.py:54-88) followed by
+ * sn_bucket_pack / sn_bucket_pack_dgl writes, byte for byte, graphs in index order.  ONE launch.
+ * The store: concatenated arrays of G graphs, one segment each, of kind node / edge / eig (n^2 entries per graph) / graph (one row per
+ * graph), and the int64 offset tables node_ptr / edge_ptr / eig_ptr [G + 1] (eig_ptr NULL: no eig segment, S = 0).  Edge endpoints are
+ * stored with graph-LOCAL node ids.  A segment is one destination array [capacity rows of its kind, row_bytes]:
+ *   SN_GATHER_COPY        the selected graphs' source rows; zero padding (graph kind: a zero row for an index out of range)
+ *   SN_GATHER_ENDPOINT    int64 edge endpoints: local id + the graph's first batch node; padding edge E + i = N + i % (N_cap - N)
+ *   SN_GATHER_GRAPH_ID    int64 node -> graph position in the batch (PyG `batch`); padding: the spare graph B_cap - 1
+ *   SN_GATHER_CONST       int32 `val` on valid rows, 0 on padding rows (validity vectors, node_slots)
+ *   SN_GATHER_NODE_COUNT  int64 per-graph node counts [B_cap]: the B real ones, 0, N_cap - N for the spare graph
+ * N, E, S: the totals of the selected graphs as the host computed them from its own copies of the tables (an index outside [0, G)
+ * counts as an empty graph).  exact = 0: N < N_cap, E <= E_cap, B < B_cap, S <= S_cap and the padding convention of sn_bucket_pack;
+ * exact = 1: capacities equal to the totals, no padding, no spare graph (evaluation batches).  counts (may be NULL): [N, E, B, S]
+ * (ncounts = 4) or [N, E, B] (ncounts = 3); count_error (may be NULL): [1], written 0.
+ * status [4]: status[0] = flags — 1: an index lies outside [0, G), that graph is empty; 2: the totals found on the device differ from
+ * N, E, S or exceed a capacity, the WHOLE batch is then written as padding (counts 0) — status[1..3] = the device's N, E, S.
+ * No write lands outside a destination's capacity whatever the indices hold.  B <= sn_store_gather_max_graphs() (1024), else
+ * SN_ERR_UNSUPPORTED.  Rows are whole 4-byte words; int64 segments and tables 8-byte, everything else 4-byte aligned. */
+#define SN_STORE_MAX_SEGS 12
+#define SN_STORE_NODE 0
+#define SN_STORE_EDGE 1
+#define SN_STORE_EIG 2
+#define SN_STORE_GRAPH 3
+#define SN_GATHER_COPY 0
+#define SN_GATHER_ENDPOINT 1
+#define SN_GATHER_GRAPH_ID 2
+#define SN_GATHER_CONST 3
+#define SN_GATHER_NODE_COUNT 4
+typedef struct sn_store_seg {
+  const void* src;                                    /* concatenated rows of all G graphs (COPY, ENDPOINT), else ignored */
+  void* dst;                                          /* [capacity rows, row_bytes] */
+  int64_t row_bytes;
+  int32_t kind, op;
+  int32_t val, reserved;
+} sn_store_seg;
+typedef struct sn_store_gather_args {
+  const int64_t* node_ptr; const int64_t* edge_ptr; const int64_t* eig_ptr;   /* [G + 1] */
+  int64_t G;
+  const int64_t* index; int64_t B;                    /* [B] graph indices (device) */
+  int64_t N, E, S;
+  int64_t N_cap, E_cap, B_cap, S_cap;
+  int32_t exact, nseg;
+  sn_store_seg seg[SN_STORE_MAX_SEGS];
+  int32_t* counts; int64_t ncounts;
+  int32_t* count_error;
+  int32_t* status;                                    /* [4] */
+} sn_store_gather_args;
+int sn_store_gather(const sn_store_gather_args* args, void* stream);
+int sn_store_gather_max_graphs(void);   /* (returns the limit, not a status) */
 /* sn_batch_plan_ex over capacity buffers (B = B_cap), then the padding graphs g >= counts[2] (device): nvalid = 0 on their nodes and
  * empty eigenvector blocks (evoff[g] = evoff[counts[2]] for g > counts[2]).  Padding of sn_bucket_pack raises no malformed-batch flag;
  * status[1..3] (largest graph, in-degree, fused-stage limits) describe the padded batch.  sn_batch_plan_ex itself is unchanged. */

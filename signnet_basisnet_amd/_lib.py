@@ -32,6 +32,8 @@ SIGNATURES = {
     "sn_pack_eig_f32": [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p],
     "sn_bucket_pack": [_p, _p],
     "sn_bucket_pack_dgl": [_p, _p],
+    "sn_store_gather": [_p, _p],
+    "sn_store_gather_max_graphs": [],                    # (returns the limit, not a status)
     "sn_batch_plan_padded": [_p, _l, _l, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_masked_l1_f32": [_p, _p, _l, _i, _p, _p, _p, _p],
     "sn_masked_l1_bwd_f32": [_p, _p, _l, _i, _p, _p, _p, _p, _p],

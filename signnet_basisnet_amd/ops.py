@@ -1240,3 +1240,92 @@ def bucket_pack_dgl(g, h, p, e, snorm_n, target, out):
     with _span("sn_bucket_pack_dgl"):
         check(lib().sn_bucket_pack_dgl(C.byref(a), stream()), "sn_bucket_pack_dgl")
     return N, E, B
+
+
+# ----------------------------------------------------------------------------- device-resident graph store (data.GraphStore)
+STORE_NODE, STORE_EDGE, STORE_EIG, STORE_GRAPH = 0, 1, 2, 3
+GATHER_COPY, GATHER_ENDPOINT, GATHER_GRAPH_ID, GATHER_CONST, GATHER_NODE_COUNT = 0, 1, 2, 3, 4
+STORE_MAX_SEGS = 12
+GATHER_BAD_INDEX, GATHER_MISMATCH = 1, 2          # flags of status[0]
+STORE_INDEX_ERROR = "graph index out of range: a batch index lies outside [0, num_graphs) of the store"
+STORE_TOTALS_ERROR = ("the graphs selected on the device do not have the node / edge / eigenvector totals the host computed "
+                      "(the device index view does not hold the host's indices): the batch was replaced by padding")
+
+
+class _StoreSegC(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("kind", C.c_int32), ("op", C.c_int32),
+                ("val", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _StoreGatherC(C.Structure):
+    _fields_ = [("node_ptr", C.c_void_p), ("edge_ptr", C.c_void_p), ("eig_ptr", C.c_void_p), ("G", C.c_int64),
+                ("index", C.c_void_p), ("B", C.c_int64), ("N", C.c_int64), ("E", C.c_int64), ("S", C.c_int64),
+                ("N_cap", C.c_int64), ("E_cap", C.c_int64), ("B_cap", C.c_int64), ("S_cap", C.c_int64),
+                ("exact", C.c_int32), ("nseg", C.c_int32), ("seg", _StoreSegC * STORE_MAX_SEGS),
+                ("counts", C.c_void_p), ("ncounts", C.c_int64), ("count_error", C.c_void_p), ("status", C.c_void_p)]
+
+
+def store_gather_max_graphs() -> int:
+    return int(lib().sn_store_gather_max_graphs())
+
+
+def store_gather_args(tables, G, caps, segs, status, counts=None, count_error=None, exact=False):
+    """The parameter block of sn_store_gather for one (store, destination) pair, built once and reused every step (store_gather fills
+    in the index view and the totals).  tables: (node_ptr, edge_ptr, eig_ptr or None), int64 [G + 1] on the device; caps: (N_cap,
+    E_cap, B_cap, S_cap); segs: (src or None, dst, kind, op, val) — `dst` one capacity array [rows of its kind, ...], `src` the store's
+    concatenated array of the same dtype and row shape (GATHER_COPY, GATHER_ENDPOINT).  Raises ValueError for a dtype / row-shape
+    mismatch, a table that is not int64 or more than STORE_MAX_SEGS segments; the library checks alignment and capacities."""
+    node_ptr, edge_ptr, eig_ptr = tables
+    for name, t in (("node_ptr", node_ptr), ("edge_ptr", edge_ptr), ("eig_ptr", eig_ptr)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != G + 1 or not t.is_contiguous()):
+            raise ValueError(f"store_gather: {name} must be a contiguous int64 [G + 1] = [{G + 1}] table, got {t.dtype} {tuple(t.shape)}")
+    if len(segs) > STORE_MAX_SEGS:
+        raise ValueError(f"store_gather: {len(segs)} segments (at most {STORE_MAX_SEGS})")
+    if status.dtype != torch.int32 or status.numel() < 4:
+        raise ValueError("store_gather: status must be int32 [4]")
+    if counts is not None and (counts.dtype != torch.int32 or counts.numel() not in (3, 4)):
+        raise ValueError("store_gather: the count block is int32 [3] or [4]")
+    if count_error is not None and (count_error.dtype != torch.int32 or count_error.numel() < 1):
+        raise ValueError("store_gather: count_error is int32 [1]")
+    require_cuda(node_ptr, edge_ptr, eig_ptr, status, counts, count_error)
+    a = _StoreGatherC()
+    a.node_ptr, a.edge_ptr, a.eig_ptr, a.G = ptr(node_ptr), ptr(edge_ptr), ptr(eig_ptr), G
+    a.N_cap, a.E_cap, a.B_cap, a.S_cap = (int(c) for c in caps)
+    a.exact, a.nseg = int(bool(exact)), len(segs)
+    wide = {GATHER_ENDPOINT: "edge endpoints", GATHER_GRAPH_ID: "the batch vector", GATHER_NODE_COUNT: "the node counts"}
+    for i, (src, dst, kind, op, val) in enumerate(segs):
+        require_cuda(src, dst)
+        if not dst.is_contiguous() or (src is not None and not src.is_contiguous()):
+            raise ValueError(f"store_gather: segment {i} is not contiguous")
+        if kind not in (STORE_NODE, STORE_EDGE, STORE_EIG, STORE_GRAPH) or dst.dim() < 1 or \
+                dst.shape[0] != (a.N_cap, a.E_cap, a.S_cap, a.B_cap)[kind]:
+            raise ValueError(f"store_gather: segment {i} (kind {kind}) has {tuple(dst.shape)} rows, the capacities are "
+                             f"N {a.N_cap}, E {a.E_cap}, B {a.B_cap}, S {a.S_cap}")
+        if op in (GATHER_COPY, GATHER_ENDPOINT):
+            if src is None or src.dtype != dst.dtype or tuple(src.shape[1:]) != tuple(dst.shape[1:]):
+                raise ValueError(f"store_gather: segment {i}: the store holds {None if src is None else src.dtype} rows of "
+                                 f"{None if src is None else tuple(src.shape[1:])}, the destination {dst.dtype} rows of {tuple(dst.shape[1:])}")
+        if op in wide and dst.dtype != torch.int64:
+            raise ValueError(f"store_gather: segment {i}: {wide[op]} are int64, the destination is {dst.dtype}")
+        if op == GATHER_CONST and dst.dtype != torch.int32:
+            raise ValueError(f"store_gather: segment {i}: a constant segment is int32, the destination is {dst.dtype}")
+        s = a.seg[i]
+        row = dst.element_size()
+        for d in dst.shape[1:]:
+            row *= int(d)               # (not _row_bytes: an exact-size destination may have no rows)
+        s.src, s.dst, s.row_bytes, s.kind, s.op, s.val = ptr(src), ptr(dst), row, kind, op, int(val)
+    a.counts, a.ncounts = ptr(counts), (0 if counts is None else counts.numel())
+    a.count_error, a.status = ptr(count_error), ptr(status)
+    return a
+
+
+def store_gather(args, index, B, totals):
+    """ONE launch (sn_store_gather): the B graphs `index` (int64, on the device: a view of the epoch's permutation) of the store go into
+    the destination of `args` (store_gather_args).  totals: (N, E, S) of those graphs, from the host's copies of the size tables."""
+    if index.dtype != torch.int64 or not index.is_contiguous() or index.numel() < B:
+        raise ValueError(f"store_gather: index must be contiguous int64 with >= {B} entries, got {index.dtype} {tuple(index.shape)}")
+    require_cuda(index)
+    args.index, args.B = ptr(index), int(B)
+    args.N, args.E, args.S = (int(v) for v in totals)
+    with _span("sn_store_gather"):
+        check(lib().sn_store_gather(C.byref(args), stream()), "sn_store_gather")

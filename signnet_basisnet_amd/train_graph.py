@@ -206,14 +206,19 @@ class _BucketCapture:
     """One bucket's captured forward + masked L1 + backward (the machinery of GraphedStep: warm-up on a side stream, buffers and
     generator restored, the switches scoped to the capture) and its own memory pool."""
 
-    def __init__(self, owner, bucket, data, target, warmup):
+    def __init__(self, owner, bucket, data, target, warmup, fill=None):
+        """`fill(pad)`: the call that fills the capacity buffers (default: ops.bucket_pack of `data` / `target`; a store's gather_into
+        for step_from — `data` / `target` then only give the dtypes and row shapes)."""
         model, optimizer = owner.model, owner.optimizer
         dev = data.batch.device
         self.model, self.bucket = model, bucket
         r0 = torch.cuda.memory_reserved(dev)
         self.pad = PaddedBatch(bucket, owner.B_cap, data, target, dev)
-        from . import ops
-        ops.bucket_pack(data, target, self.pad)
+        if fill is None:
+            from . import ops
+            ops.bucket_pack(data, target, self.pad)
+        else:
+            fill(self.pad)
         self._draw, self._masks = _mask_buffers(model, bucket.N, bucket.K, dev)
         self._status = None
         from .autograd import masked_l1_loss
@@ -254,6 +259,7 @@ class _CaptureLRU:
         self._lru = collections.OrderedDict()       # bucket -> capture, least recently used first
         self.captures = self.hits = 0
         self._last, self._nsteps = None, 0
+        self._from_store = False                    # the last step's batch came through a store's gather (step_from)
 
     @property
     def buckets(self):
@@ -291,9 +297,43 @@ class _CaptureLRU:
 
     def check(self):
         """Reads the status words of the LAST replayed step (one host wait): raises IndexError for a discrete feature outside its
-        embedding table, as nn.Embedding does in the reference's eager step (and, for a DGL GATNet, the eager step's batch errors)."""
+        embedding table, as nn.Embedding does in the reference's eager step (and, for a DGL GATNet, the eager step's batch errors).
+        After step_from also the gather's status block: IndexError for a graph index outside the store."""
         if self._last is not None:
+            if self._from_store:
+                from . import ops
+                flags = int(self._last.pad.gather_status[0])
+                if flags & ops.GATHER_BAD_INDEX:
+                    raise IndexError(ops.STORE_INDEX_ERROR)
+                if flags & ops.GATHER_MISMATCH:
+                    raise ValueError(ops.STORE_TOTALS_ERROR)
             self._last.check()
+
+    def _step_from(self, store, idx, bucket, bucket_type, capture):
+        """step_from of both step classes: the bucket from the store's host sizes, the batch through store.gather_into, then the LRU,
+        capture and replay of step()."""
+        from .data import _resolve
+        idx = _resolve(idx, store.device)
+        B = int(idx[0].size)
+        if B > self.max_graphs:
+            raise ValueError(f"{type(self).__name__}: a batch of {B} graphs exceeds max_graphs={self.max_graphs}")
+        totals = store.totals(idx[0])
+        b = store.bucket_of(idx[0], self.granule, getattr(self.model, "max_k", None), _totals=totals) if bucket is None \
+            else bucket_type(*bucket)
+        fill = lambda pad: store.gather_into(idx, pad, _totals=totals)
+        if self._admit(b):
+            cap = self._lru[b]
+            fill(cap.pad)
+            self.hits += 1
+        else:
+            from . import train_stage
+            train_stage.flush_deferred()      # (nothing of an earlier eager backward may be left for the captured one to reduce)
+            self.model.train()
+            cap = capture(b, fill)
+            self._lru[b] = cap
+            self.captures += 1
+        self._from_store = True
+        return self._replay(cap)
 
 
 class BucketedStep(_CaptureLRU):
@@ -380,7 +420,18 @@ class BucketedStep(_CaptureLRU):
             cap = _BucketCapture(self, b, data, target, self.warmup)
             self._lru[b] = cap
             self.captures += 1
+        self._from_store = False
         return self._replay(cap)
+
+    def step_from(self, store, idx, bucket=None):
+        """step() on the graphs `idx` of a data.GraphStore: host indices, or the (host indices, device view) pair an IndexLoader
+        yields — then nothing is copied to the device.  The batch reaches the capacity buffers through store.gather_into (ONE
+        sn_store_gather launch in place of the pack launch); same LRU, capture, replay and check().  `bucket`: explicit capacities,
+        e.g. store.covering_bucket(...) — one capture for a whole run."""
+        if getattr(store, "dgl", True):
+            raise TypeError("BucketedStep.step_from needs a data.GraphStore")
+        return self._step_from(store, idx, bucket, Bucket,
+                               lambda b, fill: _BucketCapture(self, b, *store.proto(), self.warmup, fill=fill))
 
 
 # ----------------------------------------------------------------------------- the DGL tree's loop (GraphPrediction)
@@ -436,7 +487,9 @@ class _DGLBucketCapture:
     _masks = None
     _refresh_masks = GraphedStep._refresh_masks
 
-    def __init__(self, owner, bucket, batch, warmup):
+    def __init__(self, owner, bucket, batch, warmup, fill=None):
+        """`fill(pad)`: the call that fills the capacity buffers (default: ops.bucket_pack_dgl of `batch`; a store's gather_into for
+        step_from — `batch` then only tells the device and which optional arrays exist)."""
         net, optimizer = owner.model, owner.optimizer
         g, h, p, e, snorm_n, targets = batch
         dev = h.device
@@ -444,7 +497,10 @@ class _DGLBucketCapture:
         r0 = torch.cuda.memory_reserved(dev)
         self.pad = pad = DGLPaddedBatch(bucket, owner.B_cap, owner.K, e is not None, snorm_n is not None, dev)
         from . import ops
-        ops.bucket_pack_dgl(g, h, p, e, snorm_n, targets, pad)
+        if fill is None:
+            ops.bucket_pack_dgl(g, h, p, e, snorm_n, targets, pad)
+        else:
+            fill(pad)
         self._words = []
         from .autograd import masked_l1_loss
 
@@ -567,7 +623,19 @@ class DGLBucketedStep(_CaptureLRU):
             cap = _DGLBucketCapture(self, b, batch, self.warmup)
             self._lru[b] = cap
             self.captures += 1
+        self._from_store = False
         return self._replay(cap)
+
+    def step_from(self, store, idx, bucket=None):
+        """step() on the graphs `idx` of a data.DGLGraphStore: host indices, or the (host indices, device view) pair an IndexLoader
+        yields — then nothing is copied to the device.  The batch reaches the capacity buffers through store.gather_into (ONE
+        sn_store_gather launch in place of the pack launch); same LRU, capture, replay and check()."""
+        if not getattr(store, "dgl", False):
+            raise TypeError("DGLBucketedStep.step_from needs a data.DGLGraphStore")
+        if store.K != self.K:
+            raise ValueError(f"DGLBucketedStep: the store holds pos_enc of {store.K} columns, the net takes {self.K}")
+        return self._step_from(store, idx, bucket, DGLBucket,
+                               lambda b, fill: _DGLBucketCapture(self, b, store.proto(), self.warmup, fill=fill))
 
 
 class GraphedForward:
