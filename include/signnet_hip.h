@@ -241,6 +241,28 @@ int sn_masked_l1_f32(const float* y, const float* target, int64_t R, int C, cons
 int sn_masked_l1_bwd_f32(const float* y, const float* target, int64_t R, int C, const int32_t* valid, const int32_t* count,
                          const float* dloss, float* dy, void* stream);
 
+/* The network-free branches of the DGL tree's handle_lap (GraphPrediction/train/train_ZINC_graph_regression.py:13-51) on the
+ * Laplacian positional encoding p [N, K] (row stride ldp) -> out [N, K] (row stride ldo): ONE launch, no host read (recordable).
+ *   SN_LAP_NONE       copy (:45-47)
+ *   SN_LAP_SIGN_FLIP  out[i][c] = p[i][c] * (u[c] >= 0.5f ? 1 : -1), u [K] uniforms in [0, 1) (:14-17)
+ *   SN_LAP_ABS_VAL    |p| (:18-19)
+ *   SN_LAP_CANONICAL  (:26-43) per graph g (rows graph_ptr[g] .. graph_ptr[g + 1], graph_ptr [B + 1] int32, the batch plan's) and
+ *                     column c: n_pos = #{p >= 0}, n_neg = #{p < 0}, s_pos = sum p[p >= 0], s_neg = sum |p[p < 0]|; the graph's column
+ *                     is multiplied by -1 if n_pos < n_neg OR s_pos < s_neg (both strict: equality keeps the sign; an all-zero column
+ *                     — the zero padding of a graph with n <= K — is never flipped), else by +1.  Rows at or beyond graph_ptr[B] are
+ *                     copied.  The sums are fp32, accumulated by ONE lane over the graph's rows in node order: they depend on the
+ *                     graph's own rows only — not on the batch around it, the grid or N — so a graph gets the same signs alone, in
+ *                     a batch and in a padded capacity buffer.  Graphs of any size, any K >= 1.
+ * out may be exactly p (in place; a graph's column is read completely before any of it is written); any other overlap is undefined.
+ * graph_ptr must be non-decreasing from 0; offsets are clamped to [0, N], so no access leaves the two buffers whatever it holds.
+ * u is read in SIGN_FLIP only, graph_ptr / B in CANONICAL only (NULL / 0 elsewhere).  N == 0 or K == 0: SN_OK, no launch. */
+#define SN_LAP_NONE 0
+#define SN_LAP_SIGN_FLIP 1
+#define SN_LAP_ABS_VAL 2
+#define SN_LAP_CANONICAL 3
+int sn_lap_pe_transform_f32(const float* p, int ldp, float* out, int ldo, int N, int K, int mode, const float* u,
+                            const int32_t* graph_ptr, int B, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Weight packing: W [d_out, d_in] (nn.Linear layout, row stride ldw) -> MFMA fragment order
  * Wp[ceil(d_out/16)][ceil(d_in/16)][64 lanes][4], zero padded.  Wp needs
@@ -578,7 +600,7 @@ int sn_pointwise_f32(const float* x, int ldx, int64_t R, int C, const float* row
  * negative_slope 0.2, no residual, bias, ReLU) — DGL is absent and unpinned by the reference; semantics restated from its published
  * definition: feat [N, heads*C] = fc(h); e_ij = leaky_relu(feat_j . attn_l[h] + feat_i . attn_r[h], slope) over the in-edges j -> i;
  * a = softmax over a node's in-edges; out[i,h,:] = [relu](sum_j a_ij feat[j,h,:] + bias[h,:]).  attn_l / attn_r: [heads*C]; bias may be
- * NULL; C <= 64; in-edges in edge-id order (no atomics).  lse [N, heads] (may be NULL): log-sum-exp of each (node, head), for a backward. */
+ * NULL; C <= 128; in-edges in edge-id order (no atomics).  lse [N, heads] (may be NULL): log-sum-exp of each (node, head), for a backward. */
 int sn_gat_aggregate_f32(const float* feat, const float* attn_l, const float* attn_r, const float* bias, int64_t N, int heads, int C,
                          float negative_slope, int relu, const int32_t* rowptr, const int32_t* col, float* out, float* lse, void* stream);
 

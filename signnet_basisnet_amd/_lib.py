@@ -37,6 +37,7 @@ SIGNATURES = {
     "sn_batch_plan_padded": [_p, _l, _l, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_masked_l1_f32": [_p, _p, _l, _i, _p, _p, _p, _p],
     "sn_masked_l1_bwd_f32": [_p, _p, _l, _i, _p, _p, _p, _p, _p],
+    "sn_lap_pe_transform_f32": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _i, _p],
     "sn_pack_weight_f32": [_p, _i, _i, _i, _p, _p],
     "sn_pack_weight_t_f32": [_p, _i, _i, _i, _p, _p],
     "sn_pack_split_f32": [_p, _i, _i, _i, _p, _p, _p, _p, _p],

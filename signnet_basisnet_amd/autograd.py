@@ -184,6 +184,23 @@ def masked_add(a, b, nvalid=None, K=0):
     return _MaskedAdd.apply(a, b, nvalid, K)
 
 
+class _MaskRows(Function):
+    @staticmethod
+    def forward(ctx, x, nvalid, K):
+        ctx.meta = (nvalid, K)
+        return ops.masked_affine(_c(x), nvalid, K)
+
+    @staticmethod
+    def backward(ctx, dy):
+        nvalid, K = ctx.meta
+        return ops.masked_affine(_c(dy), nvalid, K), None, None
+
+
+def mask_rows(x, nvalid=None, K=0):
+    """x on valid rows, 0 elsewhere, and the same for its gradient (what masked_add does to a sum); without a validity vector x itself."""
+    return x if nvalid is None else _MaskRows.apply(x, nvalid, K)
+
+
 # ----------------------------------------------------------------------------- GIN / GINE aggregation
 class _GinAgg(Function):
     @staticmethod

@@ -5,6 +5,7 @@
 // atomics and the sums are reproducible.  HBM-bound gathers over small feature rows; one thread per (node, channel) /
 // (node, head).
 #include "common.hpp"
+#include <type_traits>
 
 namespace sn {
 
@@ -341,10 +342,17 @@ __global__ __launch_bounds__(256) void k_pna_aggregate_bwd(const float* __restri
   }
 }
 
-// The same with a WAVE per (node, head): lane c owns channel c (C <= 64), the attention logits el = feat_j . attn_l, er = feat_i . attn_r
-// are wave reductions, the two passes over the in-edges (maximum, then weights and the weighted sum) read coalesced rows.  One THREAD
-// per (node, head) walking 59 channels serially was 176 us per layer on the shipped GAT (11 800 threads on a 256-CU part): 62 % of
-// the net's forward.
+// The same with a WAVE per (node, head): lane c owns channel c — and, for head widths 65 .. 128 (NPL = 2), channel c + 64 —, the attention
+// logits el = feat_j . attn_l, er = feat_i . attn_r are wave reductions, the two passes over the in-edges (maximum, then weights and the
+// weighted sum) read coalesced rows.  One THREAD per (node, head) walking 59 channels serially was 176 us per layer on the shipped GAT
+// (11 800 threads on a 256-CU part): 62 % of the net's forward.  NPL = 1 (C <= 64) is the kernel as it was: the same operations in the
+// same order.  NPL = 2 keeps the attention logits in float64 (type S): a logit of a 65..128-channel head is a sum of up to 128
+// products, its magnitude grows with the width, and an fp32 logit of magnitude 32..64 has an ulp of 4e-6 — which exp() turns into
+// a relative error of the same size in every attention weight; in float64 the weights are good to fp32 rounding again.
+__device__ __forceinline__ float gat_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double gat_max(double a, double b) { return fmax(a, b); }
+
+template <int NPL>
 __global__ __launch_bounds__(256) void k_gat_aggregate_wave(const float* __restrict__ feat, const float* __restrict__ attn_l,
                                                             const float* __restrict__ attn_r, const float* __restrict__ bias, int64_t N,
                                                             int H, int C, float slope, int relu, const int32_t* __restrict__ rowptr,
@@ -356,42 +364,76 @@ __global__ __launch_bounds__(256) void k_gat_aggregate_wave(const float* __restr
   const int64_t n = i / H;
   const int h = (int)(i - n * H);
   const int d = H * C;
-  const bool on = lane < C;
-  const float al = on ? attn_l[h * C + lane] : 0.f, ar = on ? attn_r[h * C + lane] : 0.f;
-  auto wsum = [](float v) {
+  bool on[NPL];
+  float al[NPL], ar[NPL];
+#pragma unroll
+  for (int u = 0; u < NPL; ++u) {
+    const int c = lane + 64 * u;
+    on[u] = c < C;
+    al[u] = on[u] ? attn_l[h * C + c] : 0.f;
+    ar[u] = on[u] ? attn_r[h * C + c] : 0.f;
+  }
+  using S = typename std::conditional<(NPL > 1), double, float>::type;
+  auto wsum = [](S v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
   };
-  const float er = wsum(on ? feat[n * d + h * C + lane] * ar : 0.f);
+  // a feature row's NPL channels of this lane, and their product sum with a per-lane vector (one term for NPL = 1)
+  auto load = [&](const float* row, float* f) {
+#pragma unroll
+    for (int u = 0; u < NPL; ++u) f[u] = on[u] ? row[lane + 64 * u] : 0.f;
+  };
+  auto dotl = [&](const float* f, const float* a) {
+    S v = (S)f[0] * (S)a[0];
+#pragma unroll
+    for (int u = 1; u < NPL; ++u) v += (S)f[u] * (S)a[u];
+    return v;
+  };
+  float fi[NPL];
+  load(feat + n * d + h * C, fi);
+  const S er = wsum(dotl(fi, ar));
   const int lo = rowptr[n], hi = rowptr[n + 1];
-  float m = -INFINITY;
+  S m = -INFINITY;
   for (int e = lo; e < hi; ++e) {
-    const float fj = on ? feat[(int64_t)col[e] * d + h * C + lane] : 0.f;
-    float sc = wsum(fj * al) + er;
-    sc = sc > 0.f ? sc : sc * slope;
-    m = fmaxf(m, sc);
+    float fj[NPL];
+    load(feat + (int64_t)col[e] * d + h * C, fj);
+    S sc = wsum(dotl(fj, al)) + er;
+    sc = sc > (S)0 ? sc : sc * (S)slope;
+    m = gat_max(m, sc);
   }
-  float acc = 0.f, z = 0.f;
+  float acc[NPL], z = 0.f;
+#pragma unroll
+  for (int u = 0; u < NPL; ++u) acc[u] = 0.f;
   for (int e = lo; e < hi; ++e) {
-    const float fj = on ? feat[(int64_t)col[e] * d + h * C + lane] : 0.f;
-    float sc = wsum(fj * al) + er;
-    sc = sc > 0.f ? sc : sc * slope;
-    const float w = expf(sc - m);
+    float fj[NPL];
+    load(feat + (int64_t)col[e] * d + h * C, fj);
+    S sc = wsum(dotl(fj, al)) + er;
+    sc = sc > (S)0 ? sc : sc * (S)slope;
+    const float w = expf((float)(sc - m));
     z += w;
-    acc += w * fj;
+#pragma unroll
+    for (int u = 0; u < NPL; ++u) acc[u] += w * fj[u];
   }
-  if (on) {
-    float v = (hi > lo ? acc / z : 0.f) + (bias ? bias[h * C + lane] : 0.f);
-    if (relu) v = fmaxf(v, 0.f);
-    out[n * d + h * C + lane] = v;
-  }
-  if (lse && lane == 0) lse[i] = hi > lo ? m + logf(z) : 0.f;
+#pragma unroll
+  for (int u = 0; u < NPL; ++u)
+    if (on[u]) {
+      const int c = lane + 64 * u;
+      float v = (hi > lo ? acc[u] / z : 0.f) + (bias ? bias[h * C + c] : 0.f);
+      if (relu) v = fmaxf(v, 0.f);
+      out[n * d + h * C + c] = v;
+    }
+  if (lse && lane == 0) lse[i] = hi > lo ? (float)(m + (S)logf(z)) : 0.f;
 }
 
-// adjoint of k_gat_aggregate, destination side — one thread per (node, head): with go = dout * [out > 0] and a_e = exp(s_e - lse),
+// adjoint of k_gat_aggregate, destination side — one thread per (node, head), its channels in MAXC registers (64; 128 for head widths
+// 65 .. 128): with go = dout * [out > 0] and a_e = exp(s_e - lse),
 //   d s_e = a_e (go . f_src(e) - go . (out - bias)),   d pre_e = d s_e * leaky'(pre_e),   d er_n = sum_e d pre_e.
+// MAXC = 128: the logits in float64, as in the forward, and the weights a_e renormalised to sum to 1 over the node's in-edges (a pass
+// of its own): lse is stored in fp32, and its rounding — again an ulp of a number of magnitude 32..64 — would scale every a_e of
+// the node by the same 1 + delta.  MAXC = 64 is the kernel as it was.
 // Writes go [N, H*C] (the bias gradient's rows, and what the source side needs), a_e and d pre_e per (edge id, head), d er [N, H].
+template <int MAXC>
 __global__ __launch_bounds__(256) void k_gat_bwd_dst(const float* __restrict__ feat, const float* __restrict__ attn_l,
                                                      const float* __restrict__ attn_r, const float* __restrict__ bias,
                                                      const float* __restrict__ out, const float* __restrict__ lse,
@@ -407,10 +449,12 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst(const float* __restrict__ f
   const float* al = attn_l + h * C;
   const float* ar = attn_r + h * C;
   const float* fi = feat + n * d + h * C;
-  float go[64];
-  float gdo = 0.f, er = 0.f;
+  using S = typename std::conditional<(MAXC > 64), double, float>::type;
+  float go[MAXC];
+  float gdo = 0.f;
+  S er = 0;
 #pragma unroll
-  for (int c = 0; c < 64; ++c) {
+  for (int c = 0; c < MAXC; ++c) {
     go[c] = 0.f;
     if (c < C) {
       const float o = out[n * d + h * C + c];
@@ -418,22 +462,37 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst(const float* __restrict__ f
       go[c] = g;
       gob[n * d + h * C + c] = g;
       gdo += g * (o - (bias ? bias[h * C + c] : 0.f));
-      er += fi[c] * ar[c];
+      er += (S)fi[c] * (S)ar[c];
     }
   }
   const float L = lse[n * H + h];
+  float rz = 1.f;
+  if constexpr (MAXC > 64) {
+    float zs = 0.f;
+    for (int e = rowptr[n]; e < rowptr[n + 1]; ++e) {
+      const float* fj = feat + (int64_t)col[e] * d + h * C;
+      S el = 0;
+      for (int c = 0; c < C; ++c) el += (S)fj[c] * (S)al[c];
+      const S pre = el + er;
+      const S sc = pre > (S)0 ? pre : pre * (S)slope;
+      zs += expf((float)(sc - (S)L));
+    }
+    rz = zs > 0.f ? 1.0f / zs : 0.f;
+  }
   float sum = 0.f;
   for (int e = rowptr[n]; e < rowptr[n + 1]; ++e) {
     const int64_t eid = eperm[e];
     const float* fj = feat + (int64_t)col[e] * d + h * C;
-    float el = 0.f, gv = 0.f;
+    S el = 0;
+    float gv = 0.f;
 #pragma unroll
-    for (int c = 0; c < 64; ++c)
-      if (c < C) { el += fj[c] * al[c]; gv += go[c] * fj[c]; }
-    const float pre = el + er;
-    const float sc = pre > 0.f ? pre : pre * slope;
-    const float a = expf(sc - L);
-    const float dp = a * (gv - gdo) * (pre > 0.f ? 1.0f : slope);
+    for (int c = 0; c < MAXC; ++c)
+      if (c < C) { el += (S)fj[c] * (S)al[c]; gv += go[c] * fj[c]; }
+    const S pre = el + er;
+    const S sc = pre > (S)0 ? pre : pre * (S)slope;
+    float a = expf((float)(sc - (S)L));
+    if constexpr (MAXC > 64) a *= rz;
+    const float dp = a * (gv - gdo) * (pre > (S)0 ? 1.0f : slope);
     alpha[eid * H + h] = a;
     dpre[eid * H + h] = dp;
     sum += dp;
@@ -442,6 +501,7 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst(const float* __restrict__ f
 }
 
 // source side: d feat[j] = sum_{e: j -> i} a_e go_i + (sum_e d pre_e) attn_l + d er_j attn_r; d el [N, H] is kept for the attn_l gradient
+template <int MAXC>
 __global__ __launch_bounds__(256) void k_gat_bwd_src(const float* __restrict__ attn_l, const float* __restrict__ attn_r,
                                                      const float* __restrict__ gob, const float* __restrict__ alpha,
                                                      const float* __restrict__ dpre, const float* __restrict__ der, int64_t N, int H, int C,
@@ -453,9 +513,9 @@ __global__ __launch_bounds__(256) void k_gat_bwd_src(const float* __restrict__ a
   const int64_t n = i / H;
   const int h = (int)(i - n * H);
   const int d = H * C;
-  float acc[64];
+  float acc[MAXC];
 #pragma unroll
-  for (int c = 0; c < 64; ++c) acc[c] = 0.f;
+  for (int c = 0; c < MAXC; ++c) acc[c] = 0.f;
   float sum = 0.f;
   for (int e = rev_rowptr[n]; e < rev_rowptr[n + 1]; ++e) {
     const int64_t eid = rev_eperm[e];
@@ -463,13 +523,13 @@ __global__ __launch_bounds__(256) void k_gat_bwd_src(const float* __restrict__ a
     const float a = alpha[eid * H + h];
     sum += dpre[eid * H + h];
 #pragma unroll
-    for (int c = 0; c < 64; ++c)
+    for (int c = 0; c < MAXC; ++c)
       if (c < C) acc[c] += a * g[c];
   }
   const float r = der[n * H + h];
   del[n * H + h] = sum;
 #pragma unroll
-  for (int c = 0; c < 64; ++c)
+  for (int c = 0; c < MAXC; ++c)
     if (c < C) dfeat[n * d + h * C + c] = acc[c] + sum * attn_l[h * C + c] + r * attn_r[h * C + c];
 }
 
@@ -712,10 +772,15 @@ extern "C" int sn_gat_aggregate_f32(const float* feat, const float* attn_l, cons
                                     float negative_slope, int relu, const int32_t* rowptr, const int32_t* col, float* out, float* lse,
                                     void* stream) {
   SN_REQUIRE(feat && attn_l && attn_r && rowptr && out && N >= 0 && heads > 0, "sn_gat_aggregate_f32: bad arguments");
-  SN_REQUIRE(C >= 1 && C <= 64, "sn_gat_aggregate_f32: head width %d not in [1, 64]", C);
+  SN_REQUIRE(C >= 1 && C <= 128, "sn_gat_aggregate_f32: head width %d not in [1, 128]", C);
   if (N == 0) return SN_OK;
-  hipLaunchKernelGGL(k_gat_aggregate_wave, dim3((unsigned)cdiv(N * heads, 4)), dim3(256), 0, (hipStream_t)stream, feat, attn_l, attn_r, bias, N,
-                     heads, C, negative_slope, relu, rowptr, col, out, lse);
+  const dim3 grid((unsigned)cdiv(N * heads, 4));
+  if (C <= 64)
+    hipLaunchKernelGGL(k_gat_aggregate_wave<1>, grid, dim3(256), 0, (hipStream_t)stream, feat, attn_l, attn_r, bias, N, heads, C, negative_slope,
+                       relu, rowptr, col, out, lse);
+  else
+    hipLaunchKernelGGL(k_gat_aggregate_wave<2>, grid, dim3(256), 0, (hipStream_t)stream, feat, attn_l, attn_r, bias, N, heads, C, negative_slope,
+                       relu, rowptr, col, out, lse);
   SN_CHECK_LAUNCH("sn_gat_aggregate_f32");
   return SN_OK;
 }
@@ -728,17 +793,24 @@ extern "C" int sn_gat_aggregate_bwd_f32(const float* feat, const float* attn_l, 
   SN_REQUIRE(feat && attn_l && attn_r && out && lse && dout && rowptr && rev_rowptr && dfeat && dbias_rows && d_el && d_er && scratch &&
                  N >= 0 && E >= 0 && heads > 0,
              "sn_gat_aggregate_bwd_f32: bad arguments");
-  SN_REQUIRE(C >= 1 && C <= 64, "sn_gat_aggregate_bwd_f32: head width %d not in [1, 64]", C);
+  SN_REQUIRE(C >= 1 && C <= 128, "sn_gat_aggregate_bwd_f32: head width %d not in [1, 128]", C);
   if (N == 0) return SN_OK;
   SN_REQUIRE(E == 0 || (col && eperm && rev_col && rev_eperm), "sn_gat_aggregate_bwd_f32: null edge arrays");
   hipStream_t st = (hipStream_t)stream;
   float* alpha = scratch;
   float* dpre = scratch + E * heads;
   const dim3 grid((unsigned)cdiv(N * heads, 256));
-  hipLaunchKernelGGL(k_gat_bwd_dst, grid, dim3(256), 0, st, feat, attn_l, attn_r, bias, out, lse, dout, N, heads, C, negative_slope, relu, rowptr,
-                     col, eperm, dbias_rows, alpha, dpre, d_er);
-  hipLaunchKernelGGL(k_gat_bwd_src, grid, dim3(256), 0, st, attn_l, attn_r, (const float*)dbias_rows, (const float*)alpha, (const float*)dpre,
-                     (const float*)d_er, N, heads, C, rev_rowptr, rev_col, rev_eperm, dfeat, d_el);
+  if (C <= 64) {
+    hipLaunchKernelGGL(k_gat_bwd_dst<64>, grid, dim3(256), 0, st, feat, attn_l, attn_r, bias, out, lse, dout, N, heads, C, negative_slope, relu,
+                       rowptr, col, eperm, dbias_rows, alpha, dpre, d_er);
+    hipLaunchKernelGGL(k_gat_bwd_src<64>, grid, dim3(256), 0, st, attn_l, attn_r, (const float*)dbias_rows, (const float*)alpha,
+                       (const float*)dpre, (const float*)d_er, N, heads, C, rev_rowptr, rev_col, rev_eperm, dfeat, d_el);
+  } else {
+    hipLaunchKernelGGL(k_gat_bwd_dst<128>, grid, dim3(256), 0, st, feat, attn_l, attn_r, bias, out, lse, dout, N, heads, C, negative_slope, relu,
+                       rowptr, col, eperm, dbias_rows, alpha, dpre, d_er);
+    hipLaunchKernelGGL(k_gat_bwd_src<128>, grid, dim3(256), 0, st, attn_l, attn_r, (const float*)dbias_rows, (const float*)alpha,
+                       (const float*)dpre, (const float*)d_er, N, heads, C, rev_rowptr, rev_col, rev_eperm, dfeat, d_el);
+  }
   SN_CHECK_LAUNCH("sn_gat_aggregate_bwd_f32");
   return SN_OK;
 }

@@ -8,6 +8,11 @@ MLPReadout (layers/mlp_readout_layer.py:9-24) — with the same constructor (`ne
 `model(g, h, p, e, snorm_n) -> (scores, g)` and state_dict keys, and `model.sign_inv_net` (GINDeepSigns / MaskedGINDeepSigns)
 attached as in the reference.  Eval, train-mode value and — with gradients enabled — the differentiable path (autograd.py).
 The LSPE / random-walk variants (p_out, Whp, lapeig loss) are not built and raise.
+
+The baseline rows of the same table run on the same nets: pe_init = 'no_pe' (the *_NoPE configs: no embedding_p, `p` is not read and may
+be None) and pe_init = 'lap_pe' behind `handle_lap` with lap_method 'sign_flip' / 'abs_val' / 'canonical' / 'none' (the *_LapPE
+configs); a sign_inv_net is built for lap_method 'sign_inv' only, pe_proj for pe_aggregate 'concat' (GatedGCN, Transformer), as in
+the reference.
 """
 from __future__ import annotations
 
@@ -19,6 +24,53 @@ import torch.nn as nn
 from . import ops
 from ._lib import check, lib, ptr, stream
 from .dgl_deepsigns import MLP, cached_plan, _await_side, _bucket_rows, _max_nodes, _max_in_edges, _node_counts, _BNSite, _GINConv, _pack, _prep_mlp, _run_mlp, get_sign_inv_net
+
+
+def handle_lap(model, batch_pos_enc, batch_graphs, device=None, *, u=None):
+    """train/train_ZINC_graph_regression.py:13-51: the raw Laplacian positional encoding [N, k] as `model.lap_method` hands it to the
+    net — 'sign_inv' through model.sign_inv_net, 'none' unchanged, 'sign_flip' / 'abs_val' / 'canonical' through ONE launch of
+    sn_lap_pe_transform_f32 (no host read: recordable).  'sign_flip' draws torch.rand(k) from the CPU default generator, as the
+    reference does (the same torch.manual_seed gives the same flips), and uploads it through pinned memory without a blocking copy;
+    `u`: the k uniforms instead (host or device; the static buffer of a captured step).  'canonical' reads graph_ptr from
+    cached_plan(batch_graphs, N): the plan the net's value paths use.  `device`: accepted for the reference's signature; the
+    encoding's own device is used.  Any other method: the reference's ValueError."""
+    method = model.lap_method
+    if method == "sign_inv":
+        return model.sign_inv_net(batch_graphs, batch_pos_enc.unsqueeze(-1)).squeeze(-1)          # n x k -> n x k x 1 -> n x k (:20-25)
+    if method == "none":
+        return batch_pos_enc                                                                      # raw eigenvectors (:45-47)
+    if method not in ("sign_flip", "abs_val", "canonical"):
+        raise ValueError("invalid laplacian method")
+    ops.require_cuda(batch_pos_enc)
+    p = batch_pos_enc.detach().contiguous().float()
+    if method == "abs_val":
+        return ops.lap_pe_transform(p, "abs_val")
+    if method == "sign_flip":
+        if u is None:
+            u = torch.rand(p.size(1))                                                             # (:15: the CPU default generator)
+        u = u.detach().reshape(-1).float()
+        if not u.is_cuda:
+            u = u.pin_memory().to(p.device, non_blocking=True)
+        return ops.lap_pe_transform(p, "sign_flip", u=u.contiguous())
+    return ops.lap_pe_transform(p, "canonical", graph_ptr=cached_plan(batch_graphs, p.shape[0]).graph_ptr)
+
+
+def _check_pe_init(name, pe_init, lap_lspe, use_lapeig_loss):
+    """What every net here covers of the PE switches: pe_init 'lap_pe' (the LapPE rows: sign_inv, sign_flip, abs_val, canonical, none)
+    or 'no_pe' (the NoPE rows), without LSPE and without the eigenvector loss."""
+    if pe_init not in ("lap_pe", "no_pe") or lap_lspe or use_lapeig_loss:
+        raise NotImplementedError(f"HIP {name} covers pe_init='lap_pe' / 'no_pe' with lap_lspe=False, use_lapeig_loss=False "
+                                  "(the sign-invariant, LapPE and NoPE configs)")
+
+
+def _zero_pe(net, N, dev):
+    """[>= N, 1] zeros, kept with the eval cache: the positional encoding a NoPE net hands to a one-launch kernel whose input stage
+    adds a projection of it (the projection is zero too: the stage computes embedding_h alone)."""
+    c = net.__dict__.setdefault("_cache", {})
+    z = c.get("zero_pe")
+    if z is None or z.shape[0] < N or z.device != dev:
+        z = c["zero_pe"] = torch.zeros(max(int(N), 256), 1, dtype=torch.float32, device=dev)
+    return z
 
 
 class MLPReadout(nn.Module):
@@ -102,7 +154,8 @@ class _FusedGin:
         from .dgl_deepsigns import _fold_bn_before, _pad_mat
         self.ok = False
         convs, fcs = list(net.layers), list(net.MLP_layer.FC_layers)
-        hid, kp = net.embedding_h.weight.shape[1], net.embedding_p.weight.shape[1]
+        nope = net.pe_init != "lap_pe"       # NoPE: a zero projection of a one-column zero encoding (h = embedding_h(h) + 0)
+        hid, kp = net.embedding_h.weight.shape[1], 1 if nope else net.embedding_p.weight.shape[1]
         widths = [hid] + [w for c in convs for w in (c.apply_func.lins[0].weight.shape[0], c.apply_func.lins[-1].weight.shape[0])] + \
                  [fc.weight.shape[0] for fc in fcs[:-1]]
         dmax = max(widths + [kp])
@@ -128,7 +181,10 @@ class _FusedGin:
         P.ntab[0] = hold(E)
         P.rho_out_w = None
         P.lin_a = hold(ops.pack_split(torch.eye(dp, dtype=torch.float32, device=dev)))
-        P.lin_b = hold(ops.pack_split(_pad_mat(net.embedding_p.weight, dp), ops.pad_vec(net.embedding_p.bias, dp)))
+        if nope:
+            P.lin_b = hold(ops.pack_split(torch.zeros(dp, dp, dtype=torch.float32, device=dev), torch.zeros(dp, dtype=torch.float32, device=dev)))
+        else:
+            P.lin_b = hold(ops.pack_split(_pad_mat(net.embedding_p.weight, dp), ops.pad_vec(net.embedding_p.bias, dp)))
         for l, conv in enumerate(convs):
             m = conv.apply_func
             site = net._bn(m.bns[0], False) if m.use_bn else None        # the BatchNorm between the ReLU and the second Linear: folded
@@ -159,7 +215,7 @@ class GINNet(_PackCache, nn.Module):
     def _fused_gin(self, g):
         """The packed stage-kernel parameters if this batch can take the one-launch path, else None (as GatedGCNNet._fused_gated: graph
         sizes come with the batch object; a batch beyond the kernel's limits that still reaches it gets NaN scores + check_last())."""
-        if self.training or not self.fused_stages or self.pe_init != "lap_pe":
+        if self.training or not self.fused_stages:
             return None
         c = self.__dict__.setdefault("_cache", {})
         if "fused_gin" not in c:
@@ -203,8 +259,7 @@ class GINNet(_PackCache, nn.Module):
         self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
         self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
         self.pos_enc_dim = p["pos_enc_dim"]
-        if self.pe_init == "rand_walk" or self.lap_lspe or self.use_lapeig_loss:
-            raise NotImplementedError("HIP GINNet covers pe_init='lap_pe' / lap_lspe=False (the sign-invariant PE configs)")
+        _check_pe_init("GINNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
         if self.readout == "max":
             raise NotImplementedError("HIP GINNet: readout 'sum' or 'mean'")
         if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
@@ -262,7 +317,9 @@ class GINNet(_PackCache, nn.Module):
         hid = self.embedding_h.weight.shape[1]
         E = torch.zeros(self.embedding_h.weight.shape[0], up(hid), dtype=torch.float32, device=dev)
         E[:, :hid] = self.embedding_h.weight.detach().float()
-        P = {"emb_h": E, "emb_p": padw(self.embedding_p.weight, self.embedding_p.bias, up(hid), self.embedding_p.weight.shape[1])}
+        P = {"emb_h": E}
+        if self.pe_init == "lap_pe":
+            P["emb_p"] = padw(self.embedding_p.weight, self.embedding_p.bias, up(hid), self.embedding_p.weight.shape[1])
         layers, keep = [], []
         for conv in self.layers:
             m = conv.apply_func
@@ -298,11 +355,12 @@ class GINNet(_PackCache, nn.Module):
     def forward(self, g, h, p, e, snorm_n=None):
         _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
         ops.require_cuda(h)
-        if p is None or self.pe_init != "lap_pe":
-            raise NotImplementedError("HIP GINNet needs the positional encoding p (pe_init='lap_pe')")
+        pe = self.pe_init == "lap_pe"
+        if pe and p is None:
+            raise NotImplementedError("HIP GINNet with pe_init='lap_pe' needs the positional encoding p")
         N = h.shape[0]
         hidx = h.long().reshape(N)
-        p = p.contiguous().float()
+        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference — gin_net.py:87-92)
         train = self.training
         if train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
             batch, ei, B = self._plan(g, N)
@@ -317,13 +375,14 @@ class GINNet(_PackCache, nn.Module):
                     # NaN, check_last() raises
                     self._last_plan = plan
                     self.g = g
-                    return fz.run(plan, hidx.contiguous(), p), g
+                    return fz.run(plan, hidx.contiguous(), p if pe else _zero_pe(self, N, h.device)[:N]), g
                 if not train and self.embedding_h.weight.shape[1] % 4:
                     # eval, hidden width not a multiple of 4 (GIN_ZINC_LapPE_signinv_GIN.json: 95): every row would be misaligned and every
                     # Linear on the scalar kernel; run on zero-padded channels instead (`_gin_padded`: 95 -> 96, all rows 16-byte aligned)
                     P = self._gin_padded()
                     x = ops.embedding_sum(hidx, [P["emb_h"]])
-                    x = ops.masked_linear(p, P["emb_p"], residual=x)
+                    if pe:
+                        x = ops.masked_linear(p, P["emb_p"], residual=x)
                     for eps, chain, fused in P["layers"]:
                         a = ops.gin_aggregate(x, plan, eps)
                         if fused is None:
@@ -342,7 +401,8 @@ class GINNet(_PackCache, nn.Module):
                     self.g = g
                     return hg, g
                 x = ops.embedding_sum(hidx, [self.embedding_h.weight])
-                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                              # h + embedding_p(p)   (:87-92)
+                if pe:
+                    x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                          # h + embedding_p(p)   (:87-92)
                 for conv in self.layers:
                     a = ops.gin_aggregate(x, plan, conv.eps)
                     x = _run_mlp(self._mlp(conv.apply_func, train), a, train=train)
@@ -359,7 +419,10 @@ class GINNet(_PackCache, nn.Module):
         vN, _, vB, k1 = _bucket_rows(self)          # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), x, vN, k1)
+        if self.pe_init == "lap_pe":
+            x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), x, vN, k1)
+        else:
+            x = AG.mask_rows(x, vN, k1)
         for conv in self.layers:
             mlp = conv.apply_func
             a = AG.gin_aggregate(x, conv.eps, plan, rplan)
@@ -485,13 +548,13 @@ class GatedGCNNet(_PackCache, nn.Module):
         self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
         self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
         self.pos_enc_dim, self.pe_aggregate = p["pos_enc_dim"], p["pe_aggregate"]
-        if self.pe_init != "lap_pe" or self.lap_lspe or self.use_lapeig_loss:
-            raise NotImplementedError("HIP GatedGCNNet covers pe_init='lap_pe' / lap_lspe=False (the sign-invariant PE configs)")
+        _check_pe_init("GatedGCNNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
         if self.readout == "max" or not self.edge_feat or not self.batch_norm:
             raise NotImplementedError("HIP GatedGCNNet: readout sum/mean, edge_feat=True, batch_norm=True")
         if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
             raise NotImplementedError("HIP GatedGCNNet: dropout 0.0 (as in the shipped configs)")
-        self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
+        if self.pe_init == "lap_pe":
+            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
         self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
         self.embedding_e = nn.Embedding(p["num_bond_type"], hidden)
         self.layers = nn.ModuleList([GatedGCNLayer(hidden, hidden, 0.0, True, residual=self.residual, graph_norm=False)
@@ -505,6 +568,15 @@ class GatedGCNNet(_PackCache, nn.Module):
             self.pe_proj = nn.Linear(2 * hidden, hidden)
 
     _plan = GINNet._plan
+
+    def _encode(self, x, p):
+        """The input encoder of the value paths behind embedding_h (gatedgcn_net.py:93-103): NoPE leaves h alone."""
+        if self.pe_init != "lap_pe":
+            return x
+        if self.pe_aggregate == "concat":
+            pp = ops.masked_linear(p, self._pk(self.embedding_p))
+            return ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))               # (:96-99)
+        return ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                           # (:100-102)
 
     def _forward_behind_side(self, g, h, p, e, fused):
         """The sign-invariant net ran in overlap mode (its event is on the graph): the input encoders (embeddings, PE projection) are
@@ -536,7 +608,7 @@ class GatedGCNNet(_PackCache, nn.Module):
             return fused.run(plan, x, ee)
 
     def forward(self, g, h, p, e, snorm_n=None):
-        if getattr(g, "_sn_side", None) is not None and p is not None and not self.training:
+        if getattr(g, "_sn_side", None) is not None and p is not None and not self.training and self.pe_init == "lap_pe":
             fz = self._fused_gated(g)
             if fz is not None:
                 ops.require_cuda(h)
@@ -545,11 +617,12 @@ class GatedGCNNet(_PackCache, nn.Module):
                 return y, g
         _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
         ops.require_cuda(h)
-        if p is None:
-            raise NotImplementedError("HIP GatedGCNNet needs the positional encoding p")
+        pe = self.pe_init == "lap_pe"
+        if pe and p is None:
+            raise NotImplementedError("HIP GatedGCNNet with pe_init='lap_pe' needs the positional encoding p")
         N = h.shape[0]
         hidx, eidx = h.long().reshape(N), e.long().reshape(-1)
-        p = p.contiguous().float()
+        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
         train = self.training
         if train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
             batch, ei, B = self._plan(g, N)
@@ -607,21 +680,11 @@ class GatedGCNNet(_PackCache, nn.Module):
             # no host sync on this path: out-of-range ids are flagged in the plan's status block, the stage kernel then returns NaN
             # scores, check_last() raises
             st5 = plan.status[5:6]
-            x = ops.embedding_sum(hidx, [self.embedding_h.weight], status=st5)
-            if self.pe_aggregate == "concat":
-                pp = ops.masked_linear(p, self._pk(self.embedding_p))
-                x = ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))
-            else:
-                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight], status=st5), p)
             e = ops.embedding_sum(eidx, [self.embedding_e.weight], status=st5)
             self._last_plan = plan
             return fused.run(plan, x, e)
-        x = ops.embedding_sum(hidx, [self.embedding_h.weight])
-        if self.pe_aggregate == "concat":
-            pp = ops.masked_linear(p, self._pk(self.embedding_p))
-            x = ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))                  # (:96-98)
-        else:
-            x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                         # (:100-101)
+        x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)
         e = ops.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             if not train:
@@ -654,11 +717,14 @@ class GatedGCNNet(_PackCache, nn.Module):
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
-        if self.pe_aggregate == "concat":
-            x = AG.linear(torch.cat([x, pp], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
+        if self.pe_init != "lap_pe":
+            x = AG.mask_rows(x, vN, k1)
         else:
-            x = AG.masked_add(pp, x, vN, k1)
+            pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
+            if self.pe_aggregate == "concat":
+                x = AG.linear(torch.cat([x, pp], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
+            else:
+                x = AG.masked_add(pp, x, vN, k1)
         e = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             Ah, Bh, Dh, Eh = (AG.linear(x, getattr(L, n).weight, getattr(L, n).bias, vN, k1) for n in "ABDE")
@@ -743,8 +809,7 @@ class PNANet(_PackCache, nn.Module):
         self.graph_norm, self.batch_norm, self.residual = p["graph_norm"], p["batch_norm"], p["residual"]
         self.aggregators, self.scalers, self.avg_d, self.towers = p["aggregators"], p["scalers"], p["avg_d"], p["towers"]
         self.edge_feat = p["edge_feat"]
-        if self.pe_init != "lap_pe" or self.lap_lspe or self.use_lapeig_loss:
-            raise NotImplementedError("HIP PNANet covers pe_init='lap_pe' / lap_lspe=False (the sign-invariant PE configs)")
+        _check_pe_init("PNANet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
         if self.aggregators.split() != ["mean", "max", "min", "std"] or self.scalers.split() != ["identity", "amplification", "attenuation"]:
             raise NotImplementedError("HIP PNANet: aggregators 'mean max min std', scalers 'identity amplification attenuation'")
         if not (self.graph_norm and self.batch_norm and self.edge_feat) or p["gru"] or self.readout == "max":
@@ -754,7 +819,8 @@ class PNANet(_PackCache, nn.Module):
         if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
             raise NotImplementedError("HIP PNANet: dropout 0.0 (as in the shipped configs)")
         edge_dim = p["edge_dim"]
-        self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
+        if self.pe_init == "lap_pe":
+            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
         self.in_feat_dropout = nn.Dropout(0.0)
         self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
         self.embedding_e = nn.Embedding(p["num_bond_type"], edge_dim)
@@ -772,8 +838,10 @@ class PNANet(_PackCache, nn.Module):
     def forward(self, g, h, p, e, snorm_n):
         _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
         ops.require_cuda(h)
-        if p is None or snorm_n is None:
-            raise NotImplementedError("HIP PNANet needs the positional encoding p and snorm_n (graph_norm)")
+        pe = self.pe_init == "lap_pe"
+        if (pe and p is None) or snorm_n is None:
+            raise NotImplementedError("HIP PNANet needs snorm_n (graph_norm) and, with pe_init='lap_pe', the positional encoding p")
+        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
         N = h.shape[0]
         train = self.training
         avg_log = float(self.avg_d["log"])
@@ -787,7 +855,7 @@ class PNANet(_PackCache, nn.Module):
             plan = cached_plan(g, N)       # shared with the sign-invariant net: ONE sn_batch_plan per batch
             src, dst = (t.long() for t in g.edges())
         if grad:
-            hg = self._forward_grad(plan, batch, ei, B, h.long().reshape(N), p.contiguous().float(), e.long().reshape(-1), sn, avg_log)
+            hg = self._forward_grad(plan, batch, ei, B, h.long().reshape(N), p, e.long().reshape(-1), sn, avg_log)
             self.g = g
             return hg, g
         with torch.no_grad():
@@ -796,7 +864,8 @@ class PNANet(_PackCache, nn.Module):
                 self.g = g
                 return hg, g
             x = ops.embedding_sum(h.long().reshape(N), [self.embedding_h.weight])
-            x = ops.masked_linear(p.contiguous().float(), self._pk(self.embedding_p), residual=x)                 # h + embedding_p(p)  (:124-126)
+            if pe:
+                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                 # h + embedding_p(p)  (:124-126)
             ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight])
             for L in self.layers:
                 it = L.in_dim // L.n_towers
@@ -854,9 +923,11 @@ class PNANet(_PackCache, nn.Module):
         P = {"pos_in": pos0, "C_in": C0}
         E = z(self.embedding_h.weight.shape[0], C0)
         E[:, pos0] = self.embedding_h.weight.detach().float()
-        Wp_, bp_ = z(C0, self.embedding_p.weight.shape[1]), z(C0)
-        Wp_[pos0], bp_[pos0] = self.embedding_p.weight.detach().float(), self.embedding_p.bias.detach().float()
-        P["emb_h"], P["emb_p"] = E, mk(Wp_, bp_)
+        P["emb_h"] = E
+        if self.pe_init == "lap_pe":
+            Wp_, bp_ = z(C0, self.embedding_p.weight.shape[1]), z(C0)
+            Wp_[pos0], bp_[pos0] = self.embedding_p.weight.detach().float(), self.embedding_p.bias.detach().float()
+            P["emb_p"] = mk(Wp_, bp_)
         layers = []
         for L in self.layers:
             Cin, Cout = L.in_dim, L.out_dim
@@ -909,7 +980,8 @@ class PNANet(_PackCache, nn.Module):
         P = self._pna_padded()
         N = h.shape[0]
         x = ops.embedding_sum(h.long().reshape(N), [P["emb_h"]])
-        x = ops.masked_linear(p.contiguous().float(), P["emb_p"], residual=x)                                    # h + embedding_p(p)  (:124-126)
+        if "emb_p" in P:
+            x = ops.masked_linear(p, P["emb_p"], residual=x)                                                     # h + embedding_p(p)  (:124-126)
         ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight])
         fuse = self.fused_layers
         qe_all = ops.masked_linear(ef, P["e_all"]) if (fuse and P["e_all"] is not None) else None                # [E, L*C]
@@ -942,8 +1014,11 @@ class PNANet(_PackCache, nn.Module):
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE: adjoint of h[src]
         src, dst = ei[0], ei[1]
-        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), AG.embedding_sum(hidx, [self.embedding_h.weight]),
-                          vN, k1)
+        if self.pe_init == "lap_pe":
+            x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1),
+                              AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
+        else:
+            x = AG.mask_rows(AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             it = L.in_dim // L.n_towers
@@ -1013,7 +1088,8 @@ class _FusedTransformer:
         from .dgl_deepsigns import _pad_mat
         self.ok = False
         Ls, fcs = list(net.layers), list(net.MLP_layer.FC_layers)
-        d, kp = net.embedding_h.weight.shape[1], net.embedding_p.weight.shape[1]
+        nope = net.pe_init != "lap_pe"       # NoPE: a zero projection of a one-column zero encoding (h = embedding_h(h) + 0)
+        d, kp = net.embedding_h.weight.shape[1], 1 if nope else net.embedding_p.weight.shape[1]
         if not (d == 64 and net.batch_norm and net.residual and kp <= 64):        # (the net's layer_norm flag is not handed to the layers)
             return
         if len(Ls) > GNN_MAX_LAYERS or len(fcs) != 3 or fcs[2].weight.shape[0] != 1:
@@ -1035,7 +1111,10 @@ class _FusedTransformer:
         P.node_vocab, P.edge_vocab = net.embedding_h.weight.shape[0], 0
         P.ntab[0] = hold(w(net.embedding_h.weight))
         P.rho_out_w = None
-        if net.pe_aggregate == "concat":
+        if nope:
+            P.lin_a = hold(ops.pack_split(torch.eye(64, dtype=torch.float32, device=dev)))
+            P.lin_b = hold(ops.pack_split(torch.zeros(64, 64, dtype=torch.float32, device=dev), torch.zeros(64, dtype=torch.float32, device=dev)))
+        elif net.pe_aggregate == "concat":
             # h = pe_proj(cat[embedding_h, embedding_p(p)]) (transformer_net.py:96-99) = W[:, :d] emb_h + (W[:, d:] W_p) p + (W[:, d:] b_p + b):
             # the two affine maps behind p folded once, in float64 (as the GINE net folds rho.out into its input Linear)
             Wc, bc = net.pe_proj.weight.detach().double(), net.pe_proj.bias.detach().double()
@@ -1091,13 +1170,13 @@ class TransformerNet(_PackCache, nn.Module):
         self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
         self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
         self.pos_enc_dim, self.pe_aggregate = p["pos_enc_dim"], p["pe_aggregate"]
-        if self.pe_init != "lap_pe" or self.lap_lspe or self.use_lapeig_loss:
-            raise NotImplementedError("HIP TransformerNet covers pe_init='lap_pe' / lap_lspe=False (the sign-invariant PE configs)")
+        _check_pe_init("TransformerNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
         if self.readout == "max" or not self.edge_feat:
             raise NotImplementedError("HIP TransformerNet: readout sum / mean, edge_feat True")
         if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
             raise NotImplementedError("HIP TransformerNet: dropout 0.0 (as in the shipped configs)")
-        self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
+        if self.pe_init == "lap_pe":
+            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
         self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
         self.embedding_e = nn.Embedding(p["num_bond_type"], hidden)
         self.in_feat_dropout = nn.Dropout(0.0)
@@ -1164,14 +1243,16 @@ class TransformerNet(_PackCache, nn.Module):
     def forward(self, g, h, p, e, snorm_n=None):
         _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
         ops.require_cuda(h)
-        if p is None:
-            raise NotImplementedError("HIP TransformerNet needs the positional encoding p")
+        pe = self.pe_init == "lap_pe"
+        if pe and p is None:
+            raise NotImplementedError("HIP TransformerNet with pe_init='lap_pe' needs the positional encoding p")
+        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
         N = h.shape[0]
         train = self.training
         if train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
             batch, ei, B = self._plan(g, N)
             plan = ops.build_plan(batch, ei, B, 0)
-            hg = self._forward_grad(plan, batch, ei, B, h.long().reshape(N), p.contiguous().float(), e.long().reshape(-1))
+            hg = self._forward_grad(plan, batch, ei, B, h.long().reshape(N), p, e.long().reshape(-1))
             self.g = g
             return hg, g
         plan = cached_plan(g, N)           # shared with the sign-invariant net: ONE sn_batch_plan per batch
@@ -1184,14 +1265,15 @@ class TransformerNet(_PackCache, nn.Module):
                 Ee_all = ops.masked_linear(ef, self._fused_eval()["E"])
                 self._last_plan = plan
                 self.g = g
-                return fzs.run(plan, h.long().reshape(N).contiguous(), p.contiguous().float(), Ee_all), g
+                return fzs.run(plan, h.long().reshape(N).contiguous(), p if pe else _zero_pe(self, N, h.device)[:N], Ee_all), g
             x = ops.embedding_sum(h.long().reshape(N), [self.embedding_h.weight])
-            pp = p.contiguous().float()
-            if self.pe_aggregate == "concat":
-                pe = ops.masked_linear(pp, self._pk(self.embedding_p))
-                x = ops.masked_linear(torch.cat([x, pe], dim=1), self._pk(self.pe_proj))                              # (:96-99)
+            if not pe:
+                pass                                                                                                  # NoPE: h alone
+            elif self.pe_aggregate == "concat":
+                pq = ops.masked_linear(p, self._pk(self.embedding_p))
+                x = ops.masked_linear(torch.cat([x, pq], dim=1), self._pk(self.pe_proj))                              # (:96-99)
             else:
-                x = ops.masked_linear(pp, self._pk(self.embedding_p), residual=x)                                     # (:101-102)
+                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                      # (:101-102)
             ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight])
             if not train and self._fusable():
                 # eval (round 4): 5 launches per layer instead of 12.  Q | K | V are ONE [3d, d] Linear whose column blocks the attention
@@ -1232,11 +1314,14 @@ class TransformerNet(_PackCache, nn.Module):
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        pe = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
-        if self.pe_aggregate == "concat":
-            x = AG.linear(torch.cat([x, pe], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
+        if self.pe_init != "lap_pe":
+            x = AG.mask_rows(x, vN, k1)
         else:
-            x = AG.masked_add(pe, x, vN, k1)
+            pe = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
+            if self.pe_aggregate == "concat":
+                x = AG.linear(torch.cat([x, pe], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
+            else:
+                x = AG.masked_add(pe, x, vN, k1)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             A = L.attention_h
@@ -1267,8 +1352,9 @@ class GATConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, num_heads, negative_slope=0.2):
         super().__init__()
-        if out_feats > 64:
-            raise ValueError("HIP GATConv: head width <= 64")
+        # (sn_gat_aggregate_f32: one lane per channel up to 64, two up to 128 — GAT_ZINC_NoPE / _LapPE.json have heads of 65)
+        if out_feats > 128:
+            raise ValueError("HIP GATConv: head width <= 128")
         self.in_feats, self.out_feats, self.num_heads, self.negative_slope = in_feats, out_feats, num_heads, negative_slope
         self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
         self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
@@ -1297,8 +1383,7 @@ class GATNet(_PackCache, nn.Module):
         self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
         self.pos_enc_dim, self.device, self.edge_feat = p["pos_enc_dim"], p["device"], p["edge_feat"]
         self.batch_norm, self.residual = p["batch_norm"], p["residual"]              # read and ignored by the reference too
-        if self.pe_init != "lap_pe" or self.lap_lspe or self.use_lapeig_loss:
-            raise NotImplementedError("HIP GATNet covers pe_init='lap_pe' / lap_lspe=False (the sign-invariant PE configs)")
+        _check_pe_init("GATNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
         if self.readout == "max":
             raise NotImplementedError("HIP GATNet: readout sum / mean")
         if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
@@ -1306,7 +1391,8 @@ class GATNet(_PackCache, nn.Module):
         if self.n_layers < 2:
             raise ValueError("GATNet: L >= 2 (gat_net.py:62-66 always builds a first and a last layer)")
         H = self.n_heads
-        self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
+        if self.pe_init == "lap_pe":
+            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
         self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
         self.embedding_e = nn.Embedding(p["num_bond_type"], hidden) if self.edge_feat else nn.Linear(1, hidden)
         self.in_feat_dropout = nn.Dropout(0.0)
@@ -1320,19 +1406,22 @@ class GATNet(_PackCache, nn.Module):
     def forward(self, g, h, p, e, snorm_n=None):
         _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
         ops.require_cuda(h)
-        if p is None:
-            raise NotImplementedError("HIP GATNet needs the positional encoding p")
+        pe = self.pe_init == "lap_pe"
+        if pe and p is None:
+            raise NotImplementedError("HIP GATNet with pe_init='lap_pe' needs the positional encoding p")
+        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
         N = h.shape[0]
         if self.training and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
             batch, ei, B = self._plan(g, N)
-            hg = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, h.long().reshape(N), p.contiguous().float())
+            hg = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, h.long().reshape(N), p)
             self.g = g
             return hg, g
         plan = cached_plan(g, N)
         with torch.no_grad():
             zero_deg = (plan.rowptr[1:] == plan.rowptr[:-1]).any()
             x = ops.embedding_sum(h.long().reshape(N), [self.embedding_h.weight])     # raises IndexError as nn.Embedding (one host read)
-            x = ops.masked_linear(p.contiguous().float(), self._pk(self.embedding_p), residual=x)                 # h + embedding_p(p)  (:97-99)
+            if pe:
+                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                 # h + embedding_p(p)  (:97-99)
             H = self.n_heads
             for i, L in enumerate(self.layers):
                 f = ops.masked_linear(x, self._fc(L))
@@ -1380,8 +1469,11 @@ class GATNet(_PackCache, nn.Module):
                 raise ValueError(zero_msg)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE
         N, H = hidx.shape[0], self.n_heads
-        x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), AG.embedding_sum(hidx, [self.embedding_h.weight]),
-                          vN, k1)
+        if self.pe_init == "lap_pe":
+            x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1),
+                              AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
+        else:
+            x = AG.mask_rows(AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
         for L in self.layers:
             x = AG.gat_aggregate(AG.linear(x, L.fc.weight, None, vN, k1), L.attn_l, L.attn_r, L.bias, plan, rplan, H, L.negative_slope, True)
         x = AG.slot_sum(x.view(N * H, -1), N, H)                               # mean over the heads (:110)
@@ -1407,7 +1499,7 @@ class GATNet(_PackCache, nn.Module):
         c = self.__dict__.setdefault("_cache", {})
         key = ("const", float(v), int(n))
         if key not in c:
-            c[key] = torch.full((n,), float(v), dtype=torch.float32, device=self.embedding_p.weight.device)
+            c[key] = torch.full((n,), float(v), dtype=torch.float32, device=self.embedding_h.weight.device)
         return c[key]
 
     def loss(self, scores, targets):

@@ -879,8 +879,8 @@ def gat_aggregate(feat, attn_l, attn_r, bias, plan: GraphPlan, heads: int, negat
     require_cuda(feat)
     feat = _f32c(feat, "feat")
     d = feat.shape[1]
-    if d % heads or d // heads > 64:
-        raise ValueError("gat_aggregate: heads must divide the width and the head width must be <= 64")
+    if d % heads or d // heads > 128:
+        raise ValueError("gat_aggregate: heads must divide the width and the head width must be <= 128")
     al, ar = _f32c(attn_l.reshape(-1), "attn_l"), _f32c(attn_r.reshape(-1), "attn_r")
     b = None if bias is None else _f32c(bias.reshape(-1), "bias")
     out = torch.empty(plan.N, d, dtype=torch.float32, device=feat.device)
@@ -1329,3 +1329,41 @@ def store_gather(args, index, B, totals):
     args.N, args.E, args.S = (int(v) for v in totals)
     with _span("sn_store_gather"):
         check(lib().sn_store_gather(C.byref(args), stream()), "sn_store_gather")
+
+
+# ----------------------------------------------------------------------------- handle_lap's network-free branches (dgl_nets.handle_lap)
+LAP_NONE, LAP_SIGN_FLIP, LAP_ABS_VAL, LAP_CANONICAL = 0, 1, 2, 3          # SN_LAP_* of include/signnet_hip.h
+LAP_MODES = {"none": LAP_NONE, "sign_flip": LAP_SIGN_FLIP, "abs_val": LAP_ABS_VAL, "canonical": LAP_CANONICAL}
+
+
+def lap_pe_transform(p, mode, u=None, graph_ptr=None, out=None):
+    """ONE launch (sn_lap_pe_transform_f32), no host read: the positional encoding p [N, K] (float32, unit column stride) through
+    `mode` — 'none' (copy), 'sign_flip' (column c times +1 if u[c] >= 0.5 else -1; u [K] float32 on the device), 'abs_val', 'canonical'
+    (per graph and column: times -1 if there are fewer non-negative than negative entries or their sum is smaller than the negatives'
+    absolute sum; graph_ptr [B + 1] int32 node offsets, a GraphPlan's) — or the SN_LAP_* integer.  `out`: the destination (may be p
+    itself), else a new tensor.  Rows at or beyond graph_ptr[B] are copied."""
+    m = LAP_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if m not in (LAP_NONE, LAP_SIGN_FLIP, LAP_ABS_VAL, LAP_CANONICAL):
+        raise ValueError(f"lap_pe_transform: unknown mode {mode!r} (one of {sorted(LAP_MODES)})")
+    require_cuda(p, u, graph_ptr, out)
+    if p.dim() != 2 or p.dtype != torch.float32 or (p.shape[1] > 1 and p.stride(1) != 1):
+        raise ValueError(f"lap_pe_transform: p must be float32 [N, K] with unit column stride, got {p.dtype} {tuple(p.shape)}")
+    N, K = p.shape
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.float32, device=p.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, K) or (K > 1 and out.stride(1) != 1):
+        raise ValueError(f"lap_pe_transform: out must be float32 {(N, K)} with unit column stride, got {out.dtype} {tuple(out.shape)}")
+    B = 0
+    if m == LAP_SIGN_FLIP:
+        if u is None or u.dtype != torch.float32 or u.numel() != K or not u.is_contiguous():
+            raise ValueError(f"lap_pe_transform: sign_flip needs u, contiguous float32 [{K}]")
+    if m == LAP_CANONICAL:
+        if graph_ptr is None or graph_ptr.dtype != torch.int32 or graph_ptr.numel() < 1 or not graph_ptr.is_contiguous():
+            raise ValueError("lap_pe_transform: canonical needs graph_ptr, contiguous int32 [B + 1]")
+        B = graph_ptr.numel() - 1
+    ldp = p.stride(0) if N > 1 else max(K, 1)
+    ldo = out.stride(0) if N > 1 else max(K, 1)
+    with _span("sn_lap_pe_transform_f32"):
+        check(lib().sn_lap_pe_transform_f32(ptr(p), ldp, ptr(out), ldo, N, K, m, ptr(u) if m == LAP_SIGN_FLIP else None,
+                                            ptr(graph_ptr) if m == LAP_CANONICAL else None, B, stream()), "sn_lap_pe_transform_f32")
+    return out

@@ -11,8 +11,11 @@ import torch
 
 
 class GraphedDGLForward:
-    """sign_inv_net + base network of the DGL tree (GraphPrediction/train/train_ZINC_graph_regression.py:20-25,77-80) in eval mode as
-    ONE HIP-graph launch, for batches of a FIXED SHAPE (node, edge and graph counts: a padded or bucketed loader, a serving loop).
+    """handle_lap + base network of the DGL tree (GraphPrediction/train/train_ZINC_graph_regression.py:13-51,109-112) in eval mode as
+    ONE HIP-graph launch — the net's lap_method for pe_init 'lap_pe' (sign_inv_net, or the recorded sn_lap_pe_transform_f32 launch of
+    'sign_flip' / 'abs_val' / 'canonical'; 'none': the raw encoding), nothing for pe_init 'no_pe' (pos_enc may then be None).  For
+    'sign_flip' every call draws fresh uniforms (torch.rand(k), the CPU default generator: the reference flips at evaluation too,
+    :109-110) into the static buffer the recorded launch reads — for batches of a FIXED SHAPE (node, edge and graph counts: a padded or bucketed loader, a serving loop).
 
     Every net of `dgl_nets` but GatedGCN runs its eval forward layer by layer — 50-130 launches of ~12 us of host time each for a few
     us of device work: GIN 0.8, GAT 0.6, PNA 1.0-1.3, Transformer 1.6 ms per 128 graphs, all host-bound.  The launches depend on the
@@ -48,21 +51,37 @@ class GraphedDGLForward:
         self.g = Graph(self.src, self.dst, self.bnn, bne)
         # the two host-side facts the modules read from a graph object, taken from the example batch once (no device read later)
         self.g._sn_node_counts = (int(bnn.max()) if bnn.numel() else 0, int(bnn.sum()))
-        self.h, self.pe = h.clone(), pos_enc.clone()
+        self.lap_method = net.lap_method if net.pe_init == "lap_pe" else None
+        if self.lap_method is None:
+            pos_enc = None                                 # pe_init 'no_pe': not read (:109)
+        elif pos_enc is None:
+            raise ValueError("GraphedDGLForward: pe_init 'lap_pe' needs pos_enc")
+        self.h, self.pe = h.clone(), None if pos_enc is None else pos_enc.clone()
+        self.u = torch.zeros(self.pe.shape[1], dtype=torch.float32, device=dev) if self.lap_method == "sign_flip" else None
         self.e = None if e is None else e.clone()
         self.snorm = None if snorm_n is None else snorm_n.clone()
-        self.shapes = {"src": tuple(self.src.shape), "h": tuple(self.h.shape), "pos_enc": tuple(self.pe.shape), "graphs": int(self.bnn.numel()),
+        self.shapes = {"src": tuple(self.src.shape), "h": tuple(self.h.shape), "pos_enc": None if self.pe is None else tuple(self.pe.shape), "graphs": int(self.bnn.numel()),
                        "e": None if e is None else tuple(e.shape)}
 
         def fwd():
             self.g._sn_plans = {}                          # the batch plan is rebuilt inside the recorded step
-            p = net.sign_inv_net(self.g, self.pe).squeeze(-1)
+            if self.lap_method == "sign_inv":
+                p = net.sign_inv_net(self.g, self.pe).squeeze(-1)
+            elif self.lap_method is None:
+                p = None
+            else:
+                p = handle_lap(net, self.pe, self.g, u=self.u)
             return net(self.g, self.h, p, self.e, self.snorm)[0]
 
         from . import ops
+        from .dgl_nets import handle_lap
+        cpu_rng = torch.get_rng_state() if self.u is not None else None
+        self._draw_flips()
         # (ops that would read their own status word back — the embeddings' index check — hand it over instead: check() reads them)
         with ops.defer_status() as words:
             self._graphed = GraphedForward(fwd, warmup=warmup)
+        if cpu_rng is not None:
+            torch.set_rng_state(cpu_rng)                   # (the draw of the recording does not count)
         self._status_words = list(words)[-max(1, len(words) // (warmup + 1)):] if words else []      # those of the recorded run
         # (a net whose one-launch kernel reports through check_last() remembers the plan of its last forward and forgets it once
         #  checked: the recorded plan's status block is rewritten by every replay, so check() re-arms it)
@@ -71,6 +90,10 @@ class GraphedDGLForward:
         # what the recorded pointers refer to: held here so that the allocator cannot hand the blocks out, and fingerprinted
         self._held = self._cache_objects()
         self._stamp = self._fingerprint()
+
+    def _draw_flips(self):
+        if self.u is not None:
+            self.u.copy_(torch.rand(self.u.numel()).pin_memory(), non_blocking=True)
 
     def _cache_objects(self):
         held = []
@@ -125,13 +148,16 @@ class GraphedDGLForward:
                     raise ValueError(f"GraphedDGLForward: batch_num_nodes sums to {ntot}, the recorded batch has {self.g._sn_node_counts[1]} nodes")
                 if nmax > max(self.g._sn_node_counts[0], 64):
                     raise ValueError(f"GraphedDGLForward: a graph of {nmax} nodes exceeds the recorded batch's largest graph and the stage kernels' 64")
-        put(self.h, h, "h"); put(self.pe, pos_enc, "pos_enc")
+        put(self.h, h, "h")
+        if self.pe is not None:
+            put(self.pe, pos_enc, "pos_enc")
         if self.e is not None:
             put(self.e, e, "e")
         if self.snorm is not None:
             put(self.snorm, snorm_n, "snorm_n")
         for dst, src in todo:
             dst.copy_(src, non_blocking=True)
+        self._draw_flips()
         return self._graphed.replay()
 
 

@@ -480,12 +480,27 @@ class DGLPaddedBatch:
         self.g._sn_node_counts = (self.N_cap, self.N_cap)       # (largest graph: an upper bound; only eval paths read it)
 
 
+_LAP_METHODS = ("sign_inv", "sign_flip", "abs_val", "canonical", "none")
+
+
 class _DGLBucketCapture:
-    """One DGL bucket's captured step — sign_inv_net -> net -> masked L1 over the valid graphs -> backward (the loop body of
-    train_ZINC_graph_regression.py:60-82) — with the host checks of its forward deferred (ops.defer_status) and its own memory pool."""
+    """One DGL bucket's captured step — handle_lap -> net -> masked L1 over the valid graphs -> backward (the loop body of
+    train_ZINC_graph_regression.py:60-82) — with the host checks of its forward deferred (ops.defer_status) and its own memory pool.
+    handle_lap is the net's lap_method (sign_inv_net, or the one recorded sn_lap_pe_transform_f32 launch) for pe_init 'lap_pe' and
+    nothing for 'no_pe'.  For 'sign_flip' the k uniforms live in the static buffer `u`, redrawn before every replay (`_refresh_masks`,
+    as the attention-dropout masks of GraphedStep): on the host (the reference's torch.rand(k) sequence, uploaded through pinned memory)
+    or on the device (owner.flip_rng)."""
 
     _masks = None
-    _refresh_masks = GraphedStep._refresh_masks
+    u = None
+
+    def _refresh_masks(self):
+        if self.u is None:
+            return
+        if self.flip_rng == "device":
+            self.u.copy_(torch.rand(self.u.numel(), device=self.u.device))
+        else:
+            self.u.copy_(torch.rand(self.u.numel()).pin_memory(), non_blocking=True)
 
     def __init__(self, owner, bucket, batch, warmup, fill=None):
         """`fill(pad)`: the call that fills the capacity buffers (default: ops.bucket_pack_dgl of `batch`; a store's gather_into for
@@ -503,25 +518,39 @@ class _DGLBucketCapture:
             fill(pad)
         self._words = []
         from .autograd import masked_l1_loss
+        from .dgl_nets import handle_lap
+        method, self.flip_rng = owner.lap_method, owner.flip_rng
+        if method == "sign_flip":
+            self.u = torch.zeros(owner.K, dtype=torch.float32, device=dev)
+            if self.flip_rng == "device":
+                self._masks = [self.u]               # (_capture then restores the device generator: the warm-up's draws do not count)
 
         def fwd_bwd():
             optimizer.flat_g.zero_()
             # (the embedding index checks and GAT's batch checks hand their device words over instead of reading them: check() does)
             with ops.defer_status() as words:
-                pe = net.sign_inv_net(pad.g, pad.p.unsqueeze(-1)).squeeze(-1)                   # handle_lap, sign_inv (:20-25)
+                if method is None:
+                    pe = None                                                                   # pe_init 'no_pe' (:73)
+                else:
+                    if method == "canonical":
+                        pad.g._sn_plans = {}         # its batch plan (graph_ptr) is rebuilt inside the recorded step
+                    pe = handle_lap(net, pad.p, pad.g, u=self.u)                                # (:13-51; sign_inv: :20-25)
                 y, _ = net(pad.g, pad.h, pe, pad.e, pad.snorm_n)
             self._words = words
             loss = masked_l1_loss(y, pad.target.view_as(y), pad.graph_valid, pad.counts[2:3])
             loss.backward()
             return loss, y
 
+        cpu_rng = torch.get_rng_state() if (self.u is not None and self.flip_rng == "host") else None
         self.graph, self.loss, self.y, _ = _capture(self, fwd_bwd, dev, warmup, check=self.check)
+        if cpu_rng is not None:
+            torch.set_rng_state(cpu_rng)             # the warm-up's draws do not count: the first step draws what an eager one would
         self.memory_reserved = torch.cuda.memory_reserved(dev) - r0
 
     @contextlib.contextmanager
     def _scoped(self):
         """The switch `_bucket` on the net AND its sign_inv_net, set only while this object runs them (warm-up and capture)."""
-        mods = (self.model, self.model.sign_inv_net)
+        mods = [self.model] + ([self.model.sign_inv_net] if getattr(self.model, "sign_inv_net", None) is not None else [])
         saved = [getattr(m, "_bucket", None) for m in mods]
         for m in mods:
             m._bucket = self.pad
@@ -547,12 +576,15 @@ class DGLBucketedStep(_CaptureLRU):
         step = DGLBucketedStep(net, flat_adam, max_graphs=128, granule=dict(N=256, E=512), max_captures=4)
         loss = step.step(g, h, p, e, snorm_n, targets)      # p: the raw pos_enc [N, pos_enc_dim]; e / snorm_n None where unused
 
-    `net`: GINNet, GatedGCNNet, GATNet, PNANet or TransformerNet of dgl_nets with lap_method 'sign_inv' and its sign_inv_net
-    (GINDeepSigns / MaskedGINDeepSigns); `g`: a DGL batched graph or dgl_deepsigns.Graph (only edges() and batch_num_nodes() are
+    `net`: GINNet, GatedGCNNet, GATNet, PNANet or TransformerNet of dgl_nets — pe_init 'lap_pe' with lap_method 'sign_inv' (and its
+    sign_inv_net: GINDeepSigns / MaskedGINDeepSigns), 'sign_flip', 'abs_val', 'canonical' or 'none', or pe_init 'no_pe' (p may then be
+    None in step(); step_from takes a store of any pos_enc width, gathered and ignored).  `flip_rng` ('sign_flip'): "host" — the k
+    uniforms of a step are torch.rand(k) of the CPU default generator, the reference's sequence — or "device" —
+    torch.rand(k, device=...) outside the capture: nothing is copied from the host per step.  `g`: a DGL batched graph or dgl_deepsigns.Graph (only edges() and batch_num_nodes() are
     read).  step(): the bucket is chosen on the HOST from tensor shapes, with no device read (N_cap >= N + 1 and E_cap >= max(E, 1),
     each rounded up to its granule; B_cap = max_graphs + 1: the spare graph holds the padding nodes; K = net.pos_enc_dim); a new bucket
     is captured on first use (`captures`), a known one replayed (`hits`); the captures live in an LRU of `max_captures`, each with its
-    own memory pool.  The captured region is sign_inv_net -> net -> the L1 loss over the valid graphs divided by the device graph count
+    own memory pool.  The captured region is handle_lap -> net -> the L1 loss over the valid graphs divided by the device graph count
     -> backward; a step is then ONE pack launch (sn_bucket_pack_dgl), one graph replay and the one Adam launch of optim.FlatAdam.
     Padding rows enter no batch statistic, no running statistic and no gradient: losses and gradients are those of the eager step on
     the unpadded batch (up to summation order), and the padding content cannot change a bit of them.  The forward's host checks (atom /
@@ -560,7 +592,7 @@ class DGLBucketedStep(_CaptureLRU):
     read by check(), every `check_every` steps, and raise what the eager step raises; host-side node counts that do not sum to N raise
     that ValueError before any launch.  Data-parallel training is not supported (optimizer.dist must be None)."""
 
-    def __init__(self, net, optimizer, max_graphs=128, granule=None, max_captures=4, warmup=2):
+    def __init__(self, net, optimizer, max_graphs=128, granule=None, max_captures=4, warmup=2, flip_rng="host"):
         from . import dgl_nets
         from .optim import FlatAdam
         if not isinstance(optimizer, FlatAdam):
@@ -569,12 +601,20 @@ class DGLBucketedStep(_CaptureLRU):
             raise TypeError("DGLBucketedStep needs a dgl_nets network (" + ", ".join(_DGL_NETS) + ")")
         if optimizer.dist is not None:
             raise ValueError("DGLBucketedStep: data-parallel training (FlatAdam with dist) is not supported; use the eager step")
-        if getattr(net, "lap_method", None) != "sign_inv":
-            raise ValueError(f"DGLBucketedStep: lap_method {getattr(net, 'lap_method', None)!r} is not supported (only 'sign_inv')")
+        method, has_net = getattr(net, "lap_method", None), getattr(net, "sign_inv_net", None) is not None
+        lap = getattr(net, "pe_init", None) == "lap_pe"          # (:73: handle_lap runs for pe_init 'lap_pe' only)
+        if lap and method not in _LAP_METHODS:
+            raise ValueError(f"DGLBucketedStep: lap_method {method!r} is not supported (one of {', '.join(_LAP_METHODS)})")
+        # (a net is built with a sign_inv_net exactly when its lap_method is 'sign_inv': anything else was altered after construction)
+        if method != "sign_inv" and has_net:
+            raise ValueError(f"DGLBucketedStep: lap_method {method!r} on a net that carries a sign_inv_net (built for 'sign_inv')")
         if getattr(net, "use_lapeig_loss", False):
             raise ValueError("DGLBucketedStep: use_lapeig_loss is not supported (the L1 task loss only)")
-        if getattr(net, "sign_inv_net", None) is None:
-            raise ValueError("DGLBucketedStep: the net has no sign_inv_net")
+        if method == "sign_inv" and not has_net:
+            raise ValueError("DGLBucketedStep: lap_method 'sign_inv' but the net has no sign_inv_net")
+        if flip_rng not in ("host", "device"):
+            raise ValueError(f"DGLBucketedStep: flip_rng {flip_rng!r} (\"host\" or \"device\")")
+        self.lap_method, self.flip_rng = (method if lap else None), flip_rng
         if int(max_graphs) < 1 or int(max_captures) < 1:
             raise ValueError("DGLBucketedStep: max_graphs and max_captures must be >= 1")
         self.model, self.optimizer = net, optimizer
@@ -587,6 +627,13 @@ class DGLBucketedStep(_CaptureLRU):
             self.granule[k] = int(v)
         self.warmup = int(warmup)
         self._init_lru(max_captures)                # DGLBucket -> _DGLBucketCapture
+
+    def _zero_p(self, N, dev):
+        """[N, K] zeros for a NoPE step without p (a view of one buffer kept here: no allocation, no launch per step)."""
+        z = getattr(self, "_zeros", None)
+        if z is None or z.shape[0] < N or z.shape[1] != self.K or z.device != dev:
+            z = self._zeros = torch.zeros(max(N, self.granule["N"]), self.K, dtype=torch.float32, device=dev)
+        return z[:N]
 
     def _num_graphs(self, g):
         B = int(g.batch_num_nodes().numel())
@@ -607,8 +654,11 @@ class DGLBucketedStep(_CaptureLRU):
         self._num_graphs(g)
         b = self.bucket_of(g, h) if bucket is None else DGLBucket(*bucket)
         N = int(h.shape[0])
-        if tuple(p.shape) != (N, self.K):
-            raise ValueError(f"DGLBucketedStep: p has shape {tuple(p.shape)}, expected [N, pos_enc_dim] = [{N}, {self.K}] (the raw pos_enc)")
+        if p is None and self.lap_method is None:
+            p = self._zero_p(N, h.device)                # pe_init 'no_pe': the pad keeps its pos_enc columns, all zero and never read
+        if p is None or tuple(p.shape) != (N, self.K):
+            raise ValueError(f"DGLBucketedStep: p has shape {None if p is None else tuple(p.shape)}, expected [N, pos_enc_dim] = "
+                             f"[{N}, {self.K}] (the raw pos_enc)")
         from . import ops
         ops.check_node_total(g.batch_num_nodes(), N)     # (host counts; device counts: the pack flags them, check() raises)
         batch = (g, h, p, e, snorm_n, targets)
@@ -633,7 +683,10 @@ class DGLBucketedStep(_CaptureLRU):
         if not getattr(store, "dgl", False):
             raise TypeError("DGLBucketedStep.step_from needs a data.DGLGraphStore")
         if store.K != self.K:
-            raise ValueError(f"DGLBucketedStep: the store holds pos_enc of {store.K} columns, the net takes {self.K}")
+            if self.lap_method is not None or self._lru:
+                raise ValueError(f"DGLBucketedStep: the store holds pos_enc of {store.K} columns, the net takes {self.K}" +
+                                 ("" if self.lap_method is not None else " in the buckets captured so far (release() them first)"))
+            self.K = int(store.K)                        # pe_init 'no_pe': the stored pos_enc is gathered and ignored
         return self._step_from(store, idx, bucket, DGLBucket,
                                lambda b, fill: _DGLBucketCapture(self, b, store.proto(), self.warmup, fill=fill))
 
