@@ -32,7 +32,8 @@ extern "C" {
 #define SN_ERR_LAUNCH (-2)   /* HIP launch / runtime error */
 #define SN_ERR_UNSUPPORTED (-3)
 
-#define SN_ABI_VERSION 2   /* 2: sn_plan_bins.phi_bin_mem, the fused finishes of the training links (trailing struct fields) */
+#define SN_ABI_VERSION 3   /* 2: sn_plan_bins.phi_bin_mem, trailing fields of the training links' structs;
+                              3: the in-launch finishes of the training links removed (their struct fields, the one-launch BatchNorm backward) */
 
 int sn_version(void);
 const char* sn_last_error(void);
@@ -966,14 +967,6 @@ typedef struct {
   int in_relu, out_relu;
   float* y; int ldy;
   float* stat_part;                               /* NULL: no statistics */
-  /* ABI 2 — the BatchNorm finish inside the same launch (fin_state != NULL; needs stat_part, d_out <= 128): the LAST workgroup to
-   * arrive (an agent-scope ticket behind write-through stores of the partials) merges the moments in block order — the result does
-   * not depend on who is last; the slicing and order of sn_train_bn_finish_f32 (equal up to the compiler's FMA contraction: last-bit
-   * differences) — and writes fin_state / fin_count / the running statistics.  Measured SLOWER than the separate launch in a
-   * replayed HIP graph; the Python side uses it only under SN_TRAIN_FUSE_FINISH=1. */
-  const float* fin_gamma; const float* fin_beta; float fin_eps, fin_momentum;
-  float* fin_running_mean; float* fin_running_var;
-  float* fin_state; float* fin_count;
 } sn_train_linear_args;
 
 typedef struct {
@@ -996,14 +989,7 @@ typedef struct {
   int gx_accumulate;               /* gx += instead of gx =: several Linears share one operand (q, k, v of the attention); excludes x_mean / dot_x */
   const float* dot_x; int lddot;   /* optional [G*R, d_in]: dot_part[g*nblk + blk] = sum over the block's rows of gx . dot_x — summed by the */
   double* dot_part;                /*   caller it is the eps gradient of the GIN / GINE aggregation that produced the operand (float64: a cancelling sum) */
-  /* ABI 2 — what sn_train_post_link_f32 did behind the link, inside the link's own launch by its last-arriving workgroup (same
-   * slicing and order; equal up to FMA contraction): fin_coef != NULL: the BatchNorm-backward finish of the PRODUCER link from sums_part (arguments of
-   * sn_train_bn_bwd_finish_f32; C = d_in <= 128; d gamma / d beta written, or added when fin_accumulate);  fin_dot_out != NULL:
-   * fin_dot_out[0] += the eps gradient (the sum of dot_part). */
-  const float* fin_state; const float* fin_count; const float* fin_gamma;
-  float* fin_coef; float* fin_dgamma; float* fin_dbeta; int fin_accumulate;
-  float* fin_dot_out;
-  /* ABI 2 — the CONSUMER-side form: merge_sums != NULL: coef a | b | c of THIS link's BatchNorm backward are not given (coef_* NULL) but
+  /* The CONSUMER-side BatchNorm-backward finish: merge_sums != NULL: coef a | b | c of THIS link's BatchNorm backward are not given (coef_* NULL) but
    * merged by the link itself, in its prologue, from the column-sum partials of sn_train_bn_bwd_sums_f32 / of the consumer link's
    * sums_part (float[G * merge_nblk * 2 * d_out]) with the statistics merge_state ([5][G][d_out]) / merge_count ([G]) of the forward:
    * no finish launch in front of the link.  Workgroup 0 writes d gamma / d beta (added when merge_accumulate). */
@@ -1047,10 +1033,6 @@ int sn_train_reduce_jobs_f32(const sn_train_reduce_job* jobs, int njobs, void* s
  * aggregation of a step (sn_train_linear_bwd_f32's dot_part), added once at the end of loss.backward(). */
 typedef struct { const double* part; int n; float* out; } sn_train_dot_job;
 int sn_train_dot_jobs_f64(const sn_train_dot_job* jobs, int njobs, void* stream);
-/* sn_train_bn_bwd_sums_f32 + sn_train_bn_bwd_finish_f32 in one launch (C <= 128): the last workgroup to arrive finishes. */
-int sn_train_bn_bwd_f32(const float* dy, int lddy, const float* z, int ldz, int64_t R, int G, int C, const int32_t* nvalid, int K,
-                        const float* state, const float* count, int relu, const float* gamma, float* sums_part, float* coef,
-                        float* dgamma, float* dbeta, int accumulate, void* stream);
 /* out[0] (+)= (float) sum of n float64 partials (dot_part of sn_train_linear_bwd_f32: the eps gradient), one launch */
 int sn_train_dot_finish_f64(const double* part, int n, float* out, int accumulate, void* stream);
 

@@ -1,8 +1,9 @@
 """A/B of the training step's launch structure (round 6): the same seeded steps of the headline model (hidden 128, k = 16, 128 graphs)
-and of a small ragged model under the environment switches SN_TRAIN_FUSE_FINISH / SN_TRAIN_DEFER_DW, one process per setting:
+and of a small ragged model under the environment switches SN_TRAIN_DEFER_DW / SN_TRAIN_MERGE, one process per setting:
     python profiles/scripts/train_ab_bits.py out.pt        # run under the current environment, save gradients / parameters / losses
     python profiles/scripts/train_ab_bits.py --compare a.pt b.pt
-The in-launch finishes and the deferred dW reduction are required to give the SAME BITS as the launches they replace."""
+The deferred dW reduction is required to give the SAME BITS as the launches it replaces (the consumer-side merge is separately
+compiled: it agrees to 1e-6 of the largest gradient entry).  With no switch set, two builds of the library are compared the same way."""
 import os
 import sys
 

@@ -18,7 +18,7 @@ EPI_RESIDUAL_PRE = 64
 EPI_LEAKY = 128
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-ABI_VERSION = 2          # = SN_ABI_VERSION of include/signnet_hip.h (struct layouts of the parameter blocks included)
+ABI_VERSION = 3          # = SN_ABI_VERSION of include/signnet_hip.h (struct layouts of the parameter blocks included)
 
 # name -> argtypes (restype int unless noted).  Must mirror include/signnet_hip.h exactly;
 # tests/test_abi.py cross-checks the symbol list against the header.
@@ -126,7 +126,6 @@ SIGNATURES = {
     "sn_train_dot_finish_f64": [_p, _i, _p, _i, _p],
     "sn_train_reduce_jobs_f32": [_p, _i, _p],
     "sn_train_dot_jobs_f64": [_p, _i, _p],
-    "sn_train_bn_bwd_f32": [_p, _i, _p, _i, _l, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p],
     "sn_masked_layernorm_bwd_acc_f32": [_p, _p, _p, _l, _i, _p, _f, _p, _i, _p, _p, _p, _p, _p],
     "sn_gin_aggregate_add_f32": [_p, _p, _p, _l, _i, _p, _p, _p, _p],
     "sn_gine_aggregate_bwd_add_f32": [_p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p],

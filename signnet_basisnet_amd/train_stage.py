@@ -14,6 +14,7 @@ buffers; no arithmetic runs in ATen.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 from torch.autograd import Function
@@ -26,9 +27,7 @@ class _LinArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_int), ("R", C.c_int64), ("G", C.c_int), ("d_in", C.c_int), ("d_out", C.c_int),
                 ("W", C.c_void_p), ("ldw", C.c_int), ("bias", C.c_void_p), ("nvalid", C.c_void_p), ("K", C.c_int),
                 ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("in_relu", C.c_int), ("out_relu", C.c_int),
-                ("y", C.c_void_p), ("ldy", C.c_int), ("stat_part", C.c_void_p),
-                ("fin_gamma", C.c_void_p), ("fin_beta", C.c_void_p), ("fin_eps", C.c_float), ("fin_momentum", C.c_float),
-                ("fin_running_mean", C.c_void_p), ("fin_running_var", C.c_void_p), ("fin_state", C.c_void_p), ("fin_count", C.c_void_p)]
+                ("y", C.c_void_p), ("ldy", C.c_int), ("stat_part", C.c_void_p)]
 
 
 class _BwdArgs(C.Structure):
@@ -40,8 +39,6 @@ class _BwdArgs(C.Structure):
                 ("x_mean", C.c_void_p), ("W", C.c_void_p), ("ldw", C.c_int), ("gx", C.c_void_p), ("ldgx", C.c_int),
                 ("sums_part", C.c_void_p), ("dw_part", C.c_void_p), ("want_db", C.c_int), ("gx_accumulate", C.c_int),
                 ("dot_x", C.c_void_p), ("lddot", C.c_int), ("dot_part", C.c_void_p),
-                ("fin_state", C.c_void_p), ("fin_count", C.c_void_p), ("fin_gamma", C.c_void_p), ("fin_coef", C.c_void_p),
-                ("fin_dgamma", C.c_void_p), ("fin_dbeta", C.c_void_p), ("fin_accumulate", C.c_int), ("fin_dot_out", C.c_void_p),
                 ("merge_sums", C.c_void_p), ("merge_nblk", C.c_int), ("merge_state", C.c_void_p), ("merge_count", C.c_void_p),
                 ("merge_gamma", C.c_void_p), ("merge_dgamma", C.c_void_p), ("merge_dbeta", C.c_void_p), ("merge_accumulate", C.c_int)]
 
@@ -53,21 +50,15 @@ class _SMlpArgs(C.Structure):
                 ("relu_b", C.c_int), ("scalar_state", C.c_void_p), ("column_state", C.c_void_p)]
 
 
-# Launch structure of a link's reductions (environment, read once; profiles/scripts/train_ab.sh measures all four combinations):
-#   SN_TRAIN_FUSE_FINISH=1  the finishes of a link's batch statistics / BatchNorm backward / eps gradient run INSIDE the link's launch, by
-#                           its last-arriving workgroup (agent-scope ticket behind write-through partials): 175 -> 119 launches per step,
-#                           the same reduction order (last-bit differences from FMA contraction) — and 0.10-0.29 ms SLOWER per replayed
-#                           step (3.10 -> 3.31 ms, 3.22 -> 3.32, 3.08 -> 3.37 on three boxes): one
-#                           workgroup pulling 130-260 KB of partials through one CU's memory path behind an atomic round trip costs more
-#                           than the ~2 us boundary + 8-block finish kernel it replaces.  OFF by default; kept for the A/B and because
-#                           a host-bound EAGER loop gains from it (4.32 -> 3.90 ms).
+# Launch structure of a link's reductions (environment, read once; the non-default settings are the paths that parameters outside a
+# FlatAdam take, and profiles/scripts/train_ab.sh / train_ab_merge.sh measure them against the default):
 #   SN_TRAIN_DEFER_DW=0     the dW / db reduction behind every link instead of one launch at the end of loss.backward().
-import os as _os
 #   SN_TRAIN_MERGE=0        the BatchNorm-backward coefficients from a finish launch in front of the backward link instead of merged by the
 #                           link itself in its prologue (the consumer-side form: removes the finish step instead of moving it).
-FUSE_FINISH = _os.environ.get("SN_TRAIN_FUSE_FINISH", "0") == "1"
-MERGE_COEF = _os.environ.get("SN_TRAIN_MERGE", "1") != "0"
-DEFER_DW = _os.environ.get("SN_TRAIN_DEFER_DW", "1") != "0"
+# (A third form — the finishes INSIDE the link's launch, by its last-arriving workgroup — was 0.10-0.29 ms slower per replayed step and
+#  its hand-off was unsound under concurrent replays; it was removed: DESIGN.md 4.5c.)
+MERGE_COEF = os.environ.get("SN_TRAIN_MERGE", "1") != "0"
+DEFER_DW = os.environ.get("SN_TRAIN_DEFER_DW", "1") != "0"
 
 
 def supported(d_in: int, d_out: int) -> bool:
@@ -205,20 +196,6 @@ def linear_fwd(x, R, G, W, b, nvalid, K, in_state=None, in_relu=False, out_relu=
                  ptr(None if in_state is None else in_state.scale), ptr(None if in_state is None else in_state.shift),
                  int(in_relu), int(out_relu), ptr(y), d_out, ptr(stat))
     st = None
-    if bn is not None and R > 0 and FUSE_FINISH:
-        # the BatchNorm finish inside the link's launch (its last-arriving workgroup): no second launch
-        st = BNState(G, d_out, x.device)
-        mom = 0.1 if bn.momentum is None else float(bn.momentum)
-        track = bn.track_running_stats and bn.running_mean is not None
-        a.fin_gamma, a.fin_beta = ptr(None if bn.weight is None else bn.weight.detach()), ptr(None if bn.bias is None else bn.bias.detach())
-        a.fin_eps, a.fin_momentum = float(bn.eps), mom
-        a.fin_running_mean, a.fin_running_var = ptr(bn.running_mean if track else None), ptr(bn.running_var if track else None)
-        a.fin_state, a.fin_count = ptr(st.state), ptr(st.count)
-        with ops._span("sn_train_linear_f32"):
-            check(lib().sn_train_linear_f32(C.byref(a), stream()), "sn_train_linear_f32")
-        if track and bn.num_batches_tracked is not None:
-            ops._count_batch(bn, G)
-        return y, st
     with ops._span("sn_train_linear_f32"):
         check(lib().sn_train_linear_f32(C.byref(a), stream()), "sn_train_linear_f32")
     if bn is not None and R <= 0:
@@ -249,10 +226,12 @@ def linear_bwd(dy, R, G, W, nvalid, K, x, zo=None, coef=None, mask=None, x_state
     dW_acc / db_acc: accumulate the weight / bias gradient into these buffers (returned dW / db are then None).
     dot_x: also sum gx . dot_x over all rows (per-workgroup partials, left on `linear_bwd.dot_part` for the caller to add up).
     gx_into: ADD the input gradient to this buffer instead of allocating one (several Linears reading one operand).
-    With dW_acc (and db_acc when there is a bias) the reductions behind the kernel are ONE launch (sn_train_post_link_f32), which can also
-    take: finish_bn — the producer's BatchNorm (x_state) whose backward finish these column sums feed, its d gamma / d beta accumulated in
-    place (parameters of a FlatAdam): the (a, b, c) coefficients are left on `linear_bwd.coef`; dot_acc — the buffer the eps gradient
-    (dot_x) is added to (`linear_bwd.dot_part` is then None: nothing left for eps_grad to do)."""
+    With dW_acc (and db_acc when there is a bias) the dW / db reduction waits for flush_deferred() at the end of the backward pass, and
+    with it the eps gradient (dot_x) when dot_acc — the buffer it is added to — is given (`linear_bwd.dot_part` is then None: nothing
+    left for eps_grad to do).  Not deferred (DEFER_DW off, or finish_bn applies) the reductions behind the kernel are ONE launch
+    (sn_train_post_link_f32), which also takes dot_acc and: finish_bn — the producer's BatchNorm (x_state) whose backward finish these
+    column sums feed, its d gamma / d beta accumulated in place (parameters of a FlatAdam): the (a, b, c) coefficients are left on
+    `linear_bwd.coef`."""
     W = _w(W)
     d_out, d_in = W.shape
     dev = dy.device
@@ -290,32 +269,18 @@ def linear_bwd(dy, R, G, W, nvalid, K, x, zo=None, coef=None, mask=None, x_state
         if dg is not None and dbt is not None:
             fuse_bn = (dg, dbt)
     fuse_dot = acc_w and dot_acc is not None and dot_x is not None
-    in_launch = FUSE_FINISH and R > 0 and (fuse_bn is not None or fuse_dot)
-    if in_launch:            # the finishes behind the link run in the link's own launch (its last-arriving workgroup)
-        if fuse_bn is not None:
-            cf = torch.empty(3, x_state.G, x_state.C, dtype=torch.float32, device=dev)
-            a.fin_state, a.fin_count, a.fin_gamma = ptr(x_state.state), ptr(x_state.count), ptr(finish_bn.weight.detach())
-            a.fin_coef, a.fin_dgamma, a.fin_dbeta, a.fin_accumulate = ptr(cf), ptr(fuse_bn[0]), ptr(fuse_bn[1]), 1
-            linear_bwd.coef = cf
-        if fuse_dot:
-            a.fin_dot_out = ptr(dot_acc)
     with ops._span("sn_train_linear_bwd_f32"):
         check(lib().sn_train_linear_bwd_f32(C.byref(a), stream()), "sn_train_linear_bwd_f32")
-    if acc_w and DEFER_DW and (in_launch or fuse_bn is None):
+    if acc_w and DEFER_DW and fuse_bn is None:
         # the dW / db partials — and the eps gradient's — wait for the end of the backward pass (one launch each for all links)
         _defer_reduce(dwp, 0, G * nblk, stride, nw, dW_acc)
         if want_db:
             _defer_reduce(dwp, nw, G * nblk, stride, d_out, db_acc)
         if fuse_dot:
-            if not in_launch:
-                _defer_dot(linear_bwd.dot_part, dot_acc)
+            _defer_dot(linear_bwd.dot_part, dot_acc)
             linear_bwd._dot_keep, linear_bwd.dot_part = linear_bwd.dot_part, None      # (eps_grad has nothing left to do)
         return gx, sums, nblk, None, None
     if acc_w:
-        if in_launch:
-            fuse_bn, fuse_dot = None, False        # (already done; only the dW reduction is left)
-            if linear_bwd.dot_part is not None and dot_acc is not None:
-                linear_bwd._dot_keep, linear_bwd.dot_part = linear_bwd.dot_part, None
         if fuse_bn is not None or fuse_dot or want_db:
             q = _PostArgs(ptr(dwp), G * nblk, stride, nw, ptr(dW_acc), d_out if want_db else 0, ptr(db_acc) if want_db else None,
                           None, 0, 0, 0, None, None, None, None, None, None, 1, None, 0, None)
@@ -384,22 +349,9 @@ def bn_bwd_finish(sums, nblk, st, gamma, dg_acc=None, db_acc=None):
 
 
 def bn_bwd(dy, z, R, G, nvalid, K, st, relu, gamma, dg_acc=None, db_acc=None):
-    """bn_bwd_sums + bn_bwd_finish; ONE launch (the sums kernel's last-arriving workgroup finishes) for widths up to 128."""
-    Cc = z.shape[-1]
-    if not (FUSE_FINISH and R > 0 and Cc <= 128):
-        sums, nblk = bn_bwd_sums(dy, z, R, G, nvalid, K, st, relu)
-        return bn_bwd_finish(sums, nblk, st, gamma, dg_acc, db_acc)
-    nblk = int(lib().sn_train_bn_bwd_blocks(R, G))
-    sums = torch.empty(G * nblk * 2 * Cc, dtype=torch.float32, device=z.device)
-    coef = torch.empty(3, st.G, st.C, dtype=torch.float32, device=z.device)
-    acc = dg_acc is not None and db_acc is not None
-    dgb = None if acc else torch.empty(2, st.C, dtype=torch.float32, device=z.device)
-    with ops._span("sn_train_bn_bwd_f32"):
-        check(lib().sn_train_bn_bwd_f32(ptr(dy), dy.stride(0), ptr(z), z.stride(0), R, G, Cc, ptr(nvalid), int(K), ptr(st.state),
-                                        ptr(st.count), int(relu), ptr(None if gamma is None else gamma.detach()), ptr(sums), ptr(coef),
-                                        ptr(dg_acc if acc else dgb[0]), ptr(db_acc if acc else dgb[1]), int(acc), stream()),
-              "sn_train_bn_bwd_f32")
-    return (coef, None, None) if acc else (coef, dgb[0], dgb[1])
+    """bn_bwd_sums + bn_bwd_finish."""
+    sums, nblk = bn_bwd_sums(dy, z, R, G, nvalid, K, st, relu)
+    return bn_bwd_finish(sums, nblk, st, gamma, dg_acc, db_acc)
 
 
 def bn_apply(z, R, G, nvalid, K, st, relu, residual):

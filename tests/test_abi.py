@@ -50,7 +50,7 @@ def test_version_and_error_string(lib):
     from signnet_basisnet_amd import _lib as L
     hdr = open(os.path.join(ROOT, "include", "signnet_hip.h")).read()
     import re
-    assert lib.sn_version() == L.ABI_VERSION == int(re.search(r"#define SN_ABI_VERSION (\d+)", hdr).group(1)) == 2
+    assert lib.sn_version() == L.ABI_VERSION == int(re.search(r"#define SN_ABI_VERSION (\d+)", hdr).group(1)) == 3
     # argument validation happens on the host before any launch: callable without a GPU
     rc = lib.sn_pack_weight_f32(None, 4, 4, 4, None, None)
     assert rc == -1 and b"sn_pack_weight_f32" in lib.sn_last_error()
@@ -98,7 +98,6 @@ def test_round2_entry_points_validate_their_arguments_on_the_host(lib):
     }
     cases.update({      # round 6
         "sn_train_reduce_jobs_f32": (None, 0, None),
-        "sn_train_bn_bwd_f32": (None, 4, None, 4, 2, 1, 4, None, 0, None, None, 0, None, None, None, None, None, 0, None),
         "sn_clock_probe": (0, None, None),
     })
     for name, args in cases.items():
@@ -132,9 +131,7 @@ int main(void) {
          offsetof(sn_train_linear_bwd_args, dot_part), sizeof(sn_train_scalar_mlp_args), offsetof(sn_train_scalar_mlp_args, w2),
          offsetof(sn_train_scalar_mlp_args, column_state));
   printf("%zu %zu %zu\n", sizeof(sn_train_post_args), offsetof(sn_train_post_args, sums_part), offsetof(sn_train_post_args, dot_part));
-  printf("%zu %zu %zu %zu %zu %zu\n", offsetof(sn_train_linear_args, fin_eps), offsetof(sn_train_linear_args, fin_count),
-         offsetof(sn_train_linear_bwd_args, fin_coef), offsetof(sn_train_linear_bwd_args, fin_dot_out), sizeof(sn_train_reduce_job),
-         offsetof(sn_train_reduce_job, out));
+  printf("%zu %zu\n", sizeof(sn_train_reduce_job), offsetof(sn_train_reduce_job, out));
   printf("%zu %zu\n", offsetof(sn_train_linear_bwd_args, merge_sums), offsetof(sn_train_linear_bwd_args, merge_accumulate));
   printf("%zu %zu %zu %zu\n", sizeof(sn_plan_early), offsetof(sn_plan_early, max_graph_edges), offsetof(sn_plan_early, host), offsetof(sn_plan_bins, phi_bin_mem));
   return 0;
@@ -157,8 +154,7 @@ int main(void) {
             S(train_stage._BwdArgs), train_stage._BwdArgs.x_mean.offset, train_stage._BwdArgs.dot_part.offset,
             S(train_stage._SMlpArgs), train_stage._SMlpArgs.w2.offset, train_stage._SMlpArgs.column_state.offset,
             S(train_stage._PostArgs), train_stage._PostArgs.sums_part.offset, train_stage._PostArgs.dot_part.offset,
-            train_stage._LinArgs.fin_eps.offset, train_stage._LinArgs.fin_count.offset, train_stage._BwdArgs.fin_coef.offset,
-            train_stage._BwdArgs.fin_dot_out.offset, S(train_stage._ReduceJob), train_stage._ReduceJob.out.offset,
+            S(train_stage._ReduceJob), train_stage._ReduceJob.out.offset,
             train_stage._BwdArgs.merge_sums.offset, train_stage._BwdArgs.merge_accumulate.offset,
             S(ops._PlanEarlyC), ops._PlanEarlyC.max_graph_edges.offset, ops._PlanEarlyC.host.offset, ops._PlanBinsC.phi_bin_mem.offset]
     assert got == want

@@ -175,7 +175,7 @@ def test_transform_entry_point_is_declared_bound_and_validates_on_the_host():
     modes = dict(re.findall(r"#define SN_LAP_(\w+) (\d+)", hdr))
     assert {k.lower(): int(v) for k, v in modes.items()} == ops.LAP_MODES
     assert len(_lib.SIGNATURES["sn_lap_pe_transform_f32"]) == len(re.search(r"sn_lap_pe_transform_f32\s*\((.*?)\)", hdr, re.S).group(1).split(","))
-    assert int(re.search(r"#define SN_ABI_VERSION (\d+)", hdr).group(1)) == 2 == L.sn_version()
+    assert int(re.search(r"#define SN_ABI_VERSION (\d+)", hdr).group(1)) == 3 == L.sn_version()
     f = L.sn_lap_pe_transform_f32
     buf = (torch.zeros(8).data_ptr())                          # (a host address: every call below is refused or returns before a launch)
     assert f(None, 8, None, 8, 0, 8, 3, None, None, 0, None) == 0           # N == 0: SN_OK without a launch

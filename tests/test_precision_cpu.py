@@ -67,7 +67,7 @@ def test_prec_entry_points_are_declared_and_bound():
         assert name in _lib.SIGNATURES, f"{name} is not bound in _lib.py"
         base = _lib.SIGNATURES[name.replace("_prec_f32", "_f32")]
         assert _lib.SIGNATURES[name] == base[:-1] + [C.c_int, base[-1]]
-    assert re.search(r"#define\s+SN_ABI_VERSION\s+2\b", hdr), "symbols are only added: the ABI version stays 2"
+    assert re.search(r"#define\s+SN_ABI_VERSION\s+3\b", hdr), "the ABI version is 3 since the in-launch finishes of the training links were removed"
     for k, v in (("HIGHEST", 0), ("HIGH", 1), ("MEDIUM", 2)):
         assert re.search(rf"#define\s+SN_PREC_{k}\s+{v}\b", hdr)
     from signnet_basisnet_amd import fused

@@ -166,7 +166,7 @@ def test_the_entry_point_is_declared_bound_and_validates_on_the_host():
     for name in ("sn_store_gather", "sn_store_gather_max_graphs"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert name in _lib.SIGNATURES and hasattr(L, name)
-    assert L.sn_version() == 2
+    assert L.sn_version() == 3
     assert L.sn_store_gather_max_graphs() >= 1024
     # the ctypes mirrors have the header's field order and the C layout
     for cname, mirror in (("sn_store_seg", ops._StoreSegC), ("sn_store_gather_args", ops._StoreGatherC)):

@@ -63,6 +63,9 @@ CASES = [
     (8, 8, 8, 2, 211, 5, True, True, True, True),
     (20, 20, 20, 2, 64, 5, True, True, True, True),
     (64, 64, 64, 2, 739, 5, True, True, True, True),
+    # R = 4112: 257 row tiles x 2 groups = 514, the smallest count past the tile-mode switch (512) — the persistent kernels at a width
+    # below 128 (k_tlin_fwd<8,8,STATS,false>, k_tlin_bwd<8,8,false,4>)
+    (64, 64, 64, 2, 514, 8, True, True, True, True),
 ]
 
 
@@ -274,11 +277,10 @@ def test_scalar_mlp_closed_form_vs_float64(d, N, K, G):
 
 
 # ----------------------------------------------------------------------------- round 6: the launch structures of a link's reductions
-def _train_step_grads(fuse_finish, defer_dw, monkeypatch):
+def _train_step_grads(defer_dw, monkeypatch):
     """Gradients, loss and running statistics of one training step of a small ragged model under the given launch structure."""
     from signnet_basisnet_amd import optim, synth, train_stage
     from signnet_basisnet_amd.pyg import SignNetGNN
-    monkeypatch.setattr(train_stage, "FUSE_FINISH", fuse_finish)
     monkeypatch.setattr(train_stage, "DEFER_DW", defer_dw)
     torch.manual_seed(7)
     m = SignNetGNN(None, None, 128, 1, 3, 2, variant="gine", max_k=8).to(DEV).train()
@@ -295,29 +297,10 @@ def _train_step_grads(fuse_finish, defer_dw, monkeypatch):
 def test_deferred_dw_reduction_gives_the_same_bits(monkeypatch):
     """The dW / db partials of every backward link reduced by ONE launch at the end of loss.backward() (sn_train_reduce_jobs_f32, queued
     by autograd's end-of-backward callback) instead of one launch per link: the same arithmetic per parameter, so the same bits."""
-    g0, l0, b0 = _train_step_grads(False, False, monkeypatch)
-    g1, l1, b1 = _train_step_grads(False, True, monkeypatch)
+    g0, l0, b0 = _train_step_grads(False, monkeypatch)
+    g1, l1, b1 = _train_step_grads(True, monkeypatch)
     assert l0 == l1 and torch.equal(g0, g1) and all(torch.equal(x, y) for x, y in zip(b0, b1))
     assert g0.abs().max().item() > 0
-
-
-def test_in_launch_finishes_agree_with_the_separate_launches(monkeypatch):
-    """The opt-in launch structure (SN_TRAIN_FUSE_FINISH=1): batch statistics, BatchNorm-backward coefficients and the eps gradient finished
-    by the LAST-ARRIVING workgroup of the link's own launch (agent-scope ticket behind write-through partials).  Same slicing and order as
-    the finish kernels; the two are compiled separately, so FMA contraction may differ in the last bit: compared at 1e-5 of the largest
-    gradient entry (and the running statistics at 1e-6), far below the 1e-3 two fp32 evaluations of a step differ by."""
-    g0, l0, b0 = _train_step_grads(False, True, monkeypatch)
-    g1, l1, b1 = _train_step_grads(True, True, monkeypatch)
-    assert abs(l0 - l1) <= 1e-6 * abs(l0)
-    assert (g0 - g1).abs().max().item() <= 1e-5 * g0.abs().max().item()
-    for x, y in zip(b0, b1):
-        if x.is_floating_point():
-            assert (x - y).abs().max().item() <= 1e-6 * max(1.0, x.abs().max().item())
-        else:
-            assert torch.equal(x, y)
-    # ... and replayed: tickets are reset by their last arriver, so a second and third step work from the same words
-    g2, _, _ = _train_step_grads(True, True, monkeypatch)
-    assert torch.equal(g1, g2)
 
 
 def test_consumer_side_coefficient_merge_agrees_with_the_finish_launches(monkeypatch):
@@ -326,9 +309,9 @@ def test_consumer_side_coefficient_merge_agrees_with_the_finish_launches(monkeyp
     forward (loss, running statistics) is untouched."""
     from signnet_basisnet_amd import train_stage
     monkeypatch.setattr(train_stage, "MERGE_COEF", False)
-    g0, l0, b0 = _train_step_grads(False, True, monkeypatch)
+    g0, l0, b0 = _train_step_grads(True, monkeypatch)
     monkeypatch.setattr(train_stage, "MERGE_COEF", True)
-    g1, l1, b1 = _train_step_grads(False, True, monkeypatch)
+    g1, l1, b1 = _train_step_grads(True, monkeypatch)
     assert l0 == l1 and all(torch.equal(x, y) for x, y in zip(b0, b1))
     assert (g0 - g1).abs().max().item() <= 1e-6 * g0.abs().max().item()
 
