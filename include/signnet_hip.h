@@ -601,7 +601,10 @@ int sn_pointwise_f32(const float* x, int ldx, int64_t R, int C, const float* row
  * negative_slope 0.2, no residual, bias, ReLU) — DGL is absent and unpinned by the reference; semantics restated from its published
  * definition: feat [N, heads*C] = fc(h); e_ij = leaky_relu(feat_j . attn_l[h] + feat_i . attn_r[h], slope) over the in-edges j -> i;
  * a = softmax over a node's in-edges; out[i,h,:] = [relu](sum_j a_ij feat[j,h,:] + bias[h,:]).  attn_l / attn_r: [heads*C]; bias may be
- * NULL; C <= 128; in-edges in edge-id order (no atomics).  lse [N, heads] (may be NULL): log-sum-exp of each (node, head), for a backward. */
+ * NULL; C <= 128; in-edges in edge-id order (no atomics).  lse [N, heads] (may be NULL): log-sum-exp of each (node, head), for a backward.
+ * A node without in-edges (DGL raises for one unless allow_zero_in_degree; GATNet rejects such graphs before the call) gets the empty sum:
+ * out[i,h,:] = [relu](bias[h,:]) (zeros without a bias) and lse[i,h] = 0; in sn_gat_aggregate_bwd_f32 its d_er is then 0 (it gets a feature
+ * gradient only as a source of other nodes' in-edges) and its cotangent, masked by the ReLU, still reaches the bias gradient. */
 int sn_gat_aggregate_f32(const float* feat, const float* attn_l, const float* attn_r, const float* bias, int64_t N, int heads, int C,
                          float negative_slope, int relu, const int32_t* rowptr, const int32_t* col, float* out, float* lse, void* stream);
 

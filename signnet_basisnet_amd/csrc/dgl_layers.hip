@@ -431,7 +431,13 @@ __global__ __launch_bounds__(256) void k_gat_aggregate_wave(const float* __restr
 //   d s_e = a_e (go . f_src(e) - go . (out - bias)),   d pre_e = d s_e * leaky'(pre_e),   d er_n = sum_e d pre_e.
 // MAXC = 128: the logits in float64, as in the forward, and the weights a_e renormalised to sum to 1 over the node's in-edges (a pass
 // of its own): lse is stored in fp32, and its rounding — again an ulp of a number of magnitude 32..64 — would scale every a_e of
-// the node by the same 1 + delta.  MAXC = 64 is the kernel as it was.
+// the node by the same 1 + delta.  The same pass forms go . (out - bias) as sum_e a_e (go . f_src(e)), from the very sums the loop
+// after it subtracts it from: where one in-edge holds nearly all the weight (logits that large do that) gv_e - go . (out - bias) is a
+// difference of two nearly equal numbers, d er_n is ALL such differences, and the rounding of a 128-term fp32 dot product — 1e-5 here —
+// is common to both sides only when both are the same sum.  Taken from the stored `out` instead, that rounding stayed in d er and put
+// the attn_r gradient 3.6e-5 .. 5.9e-5 of its largest entry off on a 203-node batch with one 128-wide head (now 0.8e-5 .. 1.1e-5; the
+// fp32 CPU autograd of the same inputs: 1.2e-5 .. 1.5e-5 — tests/test_mp_grid_gpu.py).
+// MAXC = 64 is the kernel as it was.
 // Writes go [N, H*C] (the bias gradient's rows, and what the source side needs), a_e and d pre_e per (edge id, head), d er [N, H].
 template <int MAXC>
 __global__ __launch_bounds__(256) void k_gat_bwd_dst(const float* __restrict__ feat, const float* __restrict__ attn_l,
@@ -468,16 +474,22 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst(const float* __restrict__ f
   const float L = lse[n * H + h];
   float rz = 1.f;
   if constexpr (MAXC > 64) {
-    float zs = 0.f;
+    float zs = 0.f, zg = 0.f;
     for (int e = rowptr[n]; e < rowptr[n + 1]; ++e) {
       const float* fj = feat + (int64_t)col[e] * d + h * C;
       S el = 0;
-      for (int c = 0; c < C; ++c) el += (S)fj[c] * (S)al[c];
+      float gv = 0.f;
+#pragma unroll
+      for (int c = 0; c < MAXC; ++c)
+        if (c < C) { el += (S)fj[c] * (S)al[c]; gv += go[c] * fj[c]; }          // (gv: the same sum, term by term, as in the loop below)
       const S pre = el + er;
       const S sc = pre > (S)0 ? pre : pre * (S)slope;
-      zs += expf((float)(sc - (S)L));
+      const float w = expf((float)(sc - (S)L));
+      zs += w;
+      zg += w * gv;
     }
     rz = zs > 0.f ? 1.0f / zs : 0.f;
+    gdo = zg * rz;
   }
   float sum = 0.f;
   for (int e = rowptr[n]; e < rowptr[n + 1]; ++e) {
