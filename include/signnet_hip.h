@@ -1109,6 +1109,25 @@ typedef struct sn_deepsets_tail_params {
 } sn_deepsets_tail_params;
 int sn_deepsets_tail_f32(const float* z, int n, const sn_deepsets_tail_params* P, float* y, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Set2Set(d, processing_steps = T) readout with one LSTM layer (Alchemy/baseline_gin.py:43,58), one launch per direction, one
+ * workgroup per graph running all T steps:  q* = 0, h = c = 0;  per step  gates = W_ih q* + b_ih + W_hh h + b_hh (rows i | f | g | o),
+ * c = s(f) c + s(i) tanh(g), q = h = s(o) tanh(c), e_n = <x_n, q>, a = softmax of e over the graph's nodes (maximum subtracted,
+ * denominator + 1e-16), r = sum a_n x_n, q* = [q, r].  out [B, 2d] = q* after step T; a graph without nodes has r = 0.
+ * x [N, d] (4-byte alignment suffices), graph_ptr [B+1], w_ih [4d, 2d], w_hh [4d, d], b_ih / b_hh [4d] (torch.nn.LSTM's *_l0),
+ * 1 <= d <= 128, any graph size, any B.  work: float[12 d^2 + 4 d] (the transposed weights and summed biases of this call).
+ * Tape (all five or all NULL = eval): tape_in [T, B, 3d] the cell's input (q, r, h of the step before), tape_act [T, B, 4d] activated
+ * gates, tape_cell [T, B, d], tape_e [T, N] attention logits, tape_md [T, B, 2] their maximum and the softmax denominator.
+ * sn_set2set_bwd_f32: dx [N, d] (every node of a graph is written; rows outside every graph are left alone) and dgate [T, B, 4d], the
+ * gradient of the pre-activation gates: d W_ih | d W_hh = dgate^T tape_in (sn_linear_wgrad_f32 over the T*B rows), d b_ih = d b_hh =
+ * its column sums.  No atomics: every sum has one owner and a fixed order. */
+int sn_set2set_f32(const float* x, int64_t N, int d, const int32_t* graph_ptr, int64_t B, const float* w_ih, const float* w_hh,
+                   const float* b_ih, const float* b_hh, int T, float* out, float* work, float* tape_in, float* tape_act,
+                   float* tape_cell, float* tape_e, float* tape_md, void* stream);
+int sn_set2set_bwd_f32(const float* x, int64_t N, int d, const int32_t* graph_ptr, int64_t B, const float* w_ih, const float* w_hh, int T,
+                       const float* out, const float* dout, const float* tape_in, const float* tape_act, const float* tape_cell,
+                       const float* tape_e, const float* tape_md, float* dx, float* dgate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,8 @@ SIGNATURES = {
     "sn_train_scalar_mlp_stats_f32": [_p, _f, _p, _p, _f, _p, _p, _p, _p],
     "sn_train_scalar_mlp_apply_f32": [_p, _p, _p],
     "sn_train_scalar_mlp_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p],
+    "sn_set2set_f32": [_p, _l, _i, _p, _l, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "sn_set2set_bwd_f32": [_p, _l, _i, _p, _l, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 _SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64}
 

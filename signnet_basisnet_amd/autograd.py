@@ -733,3 +733,35 @@ def masked_l1_loss(y, target, valid, count):
     if y.shape != target.shape:
         raise ValueError(f"masked_l1_loss: y {tuple(y.shape)} and target {tuple(target.shape)} differ")
     return _MaskedL1.apply(y, target, valid, count)
+
+
+# ----------------------------------------------------------------------------- Set2Set readout (Alchemy/baseline_gin.py:43,58)
+class _Set2Set(Function):
+    @staticmethod
+    def forward(ctx, x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps):
+        x = _c(x)
+        ws = tuple(_c(t.detach()) for t in (w_ih, w_hh, b_ih, b_hh))
+        out, tape = ops.set2set(x, graph_ptr, *ws, steps, want_tape=True)
+        ctx.save_for_backward(x, graph_ptr, ws[0], ws[1], out, *tape)
+        ctx.steps = int(steps)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, graph_ptr, w_ih, w_hh, out, t_in, t_act, t_cell, t_e, t_md = ctx.saved_tensors
+        T, (N, d), B = ctx.steps, x.shape, out.shape[0]
+        g = _c(g)
+        dx = torch.zeros_like(x)                       # (rows outside every graph keep 0)
+        dgate = torch.empty(T, B, 4 * d, dtype=torch.float32, device=x.device)
+        with ops._span("sn_set2set_bwd_f32"):
+            check(lib().sn_set2set_bwd_f32(ptr(x), N, d, ptr(graph_ptr), B, ptr(w_ih), ptr(w_hh), T, ptr(out), ptr(g), ptr(t_in),
+                                           ptr(t_act), ptr(t_cell), ptr(t_e), ptr(t_md), ptr(dx), ptr(dgate), stream()),
+                  "sn_set2set_bwd_f32")
+        # [4d, T*B] x [T*B, 3d]: the cell's inputs are [q | r] (weight_ih_l0) and h (weight_hh_l0); both biases see the same gate gradient
+        dW, db = linear_wgrad(t_in.view(T * B, 3 * d), dgate.view(T * B, 4 * d), None, 0)
+        return dx, None, dW[:, :2 * d].contiguous(), dW[:, 2 * d:].contiguous(), db, db.clone(), None
+
+
+def set2set(x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps):
+    """Differentiable ops.set2set: gradients of x and of the four LSTM tensors (bit-reproducible: no atomics anywhere)."""
+    return _Set2Set.apply(x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps)

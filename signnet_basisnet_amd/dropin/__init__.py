@@ -51,6 +51,14 @@ ALIASES = {
     },
 }
 
+# Opt-in (`install(tree, baselines=True)`, the runner's `--baselines`): the trees' BASELINE models — competitors of SignNet that the same
+# entry scripts build (Alchemy/main_alchemy.py:24-33, GINESignNetPyG/train/zinc.py:31-46).  Kept apart from ALIASES: they have no shim
+# directory entry, and without the flag both names stay the tree's.
+BASELINE_ALIASES = {
+    "alchemy": {"baseline_gin": "signnet_basisnet_amd.pyg_baselines"},
+    "gine_pyg": {"core.model": _PKG + ".baseline_core_model"},
+}
+
 # entry script (basename) -> tree, for the runner
 SCRIPTS = {
     "main_alchemy.py": "alchemy",
@@ -86,9 +94,11 @@ class _AliasLoader(importlib.abc.Loader):
 class AliasFinder(importlib.abc.MetaPathFinder):
     """Answers the names of `ALIASES[tree]` and nothing else; every other import goes on to the normal finders."""
 
-    def __init__(self, tree: str):
+    def __init__(self, tree: str, baselines: bool = False):
         self.tree = tree
         self.table = dict(ALIASES[tree])
+        if baselines:
+            self.table.update(BASELINE_ALIASES.get(tree, {}))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -97,13 +107,19 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         return importlib.machinery.ModuleSpec(fullname, _AliasLoader(impl), origin=impl)
 
 
-def install(tree: str) -> AliasFinder:
-    """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree."""
+def install(tree: str, baselines: bool = False) -> AliasFinder:
+    """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
+    `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN); a finder installed without them is extended in place."""
     shim_dir(tree)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
+            if baselines:
+                for name, impl in BASELINE_ALIASES.get(tree, {}).items():
+                    if name not in f.table:
+                        f.table[name] = impl
+                        sys.modules.pop(name, None)
             return f
-    finder = AliasFinder(tree)
+    finder = AliasFinder(tree, baselines)
     sys.meta_path.insert(0, finder)
     for name in finder.table:           # a module imported before install() would otherwise stay bound to the tree's file
         sys.modules.pop(name, None)

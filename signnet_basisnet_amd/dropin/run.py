@@ -9,7 +9,9 @@ The script is executed with `runpy` as `__main__` with its own `sys.argv`; `sys.
 `python script.py` (the working directory stays where the caller is: the scripts open `data/...`, `configs/...` relative to it,
 and GINESignNetPyG's README runs `python -m train.zinc` from the tree root, which is why '' stays on the path too).  The only
 difference to a plain run is the finder of `dropin.install(tree)`: the names listed in `dropin.ALIASES[tree]` come from this
-package, everything else from the tree.  `--tree` overrides the guess from the script's file name.
+package, everything else from the tree.  `--tree` overrides the guess from the script's file name.  `--baselines` (before the script)
+also binds the trees' baseline models, `dropin.BASELINE_ALIASES`: `baseline_gin` (NetGINE) and `core.model` (the plain GINE GNN of
+`model.gnn_type GINEConv`); without it both stay the tree's.
 """
 from __future__ import annotations
 
@@ -22,15 +24,20 @@ from . import ALIASES, SCRIPTS, install
 
 def main(argv=None) -> None:
     argv = list(sys.argv[1:] if argv is None else argv)
-    tree = None
-    if argv and argv[0] == "--tree":
-        if len(argv) < 2:
-            raise SystemExit("--tree needs a value: " + ", ".join(sorted(ALIASES)))
-        tree, argv = argv[1], argv[2:]
-    elif argv and argv[0].startswith("--tree="):
-        tree, argv = argv[0].split("=", 1)[1], argv[1:]
+    tree, baselines = None, False
+    while argv and argv[0].startswith("--"):        # the runner's own options come before the script
+        if argv[0] == "--baselines":
+            baselines, argv = True, argv[1:]
+        elif argv[0] == "--tree":
+            if len(argv) < 2:
+                raise SystemExit("--tree needs a value: " + ", ".join(sorted(ALIASES)))
+            tree, argv = argv[1], argv[2:]
+        elif argv[0].startswith("--tree="):
+            tree, argv = argv[0].split("=", 1)[1], argv[1:]
+        else:
+            break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] <entry script> [script arguments ...]\n"
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines] <entry script> [script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
     script = argv[0]
     if not os.path.isfile(script):
@@ -39,7 +46,7 @@ def main(argv=None) -> None:
         tree = SCRIPTS.get(os.path.basename(script))
         if tree is None:
             raise SystemExit(f"cannot tell the reference tree from {os.path.basename(script)!r}; pass --tree " + "|".join(sorted(ALIASES)))
-    install(tree)
+    install(tree, baselines=baselines)
     script_dir = os.path.dirname(os.path.abspath(script))
     for p in (os.getcwd(), script_dir):          # script_dir ends up first, as under `python script.py`
         if p in sys.path:

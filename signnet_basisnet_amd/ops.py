@@ -1367,3 +1367,36 @@ def lap_pe_transform(p, mode, u=None, graph_ptr=None, out=None):
         check(lib().sn_lap_pe_transform_f32(ptr(p), ldp, ptr(out), ldo, N, K, m, ptr(u) if m == LAP_SIGN_FLIP else None,
                                             ptr(graph_ptr) if m == LAP_CANONICAL else None, B, stream()), "sn_lap_pe_transform_f32")
     return out
+
+
+# ----------------------------------------------------------------------------- Set2Set readout (Alchemy/baseline_gin.py:43,58)
+def set2set(x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps, want_tape=False):
+    """PyG's Set2Set(d, processing_steps=steps) with one LSTM layer, one launch: x [N, d], graph_ptr int32 [B+1], the four tensors of
+    torch.nn.LSTM(2d, d) under their state_dict names -> q* [B, 2d].  want_tape: also the tape sn_set2set_bwd_f32 reads
+    (in [T,B,3d], act [T,B,4d], cell [T,B,d], e [T,N], md [T,B,2]).  Graph b owns rows graph_ptr[b] .. graph_ptr[b+1] of x; the entries
+    live on the device, so they are not read here: the kernel clamps them into [0, N] and rows outside every graph belong to none (a batch
+    plan's graph_ptr — ops.build_plan — always ends at N)."""
+    require_cuda(x, graph_ptr, w_ih, w_hh, b_ih, b_hh)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) != x.shape[1]):
+        raise ValueError("set2set: x must be a dense float32 [N, d] block")
+    if graph_ptr.dtype != torch.int32 or not graph_ptr.is_contiguous():
+        raise ValueError("set2set: graph_ptr must be contiguous int32 [B+1]")
+    if graph_ptr.dim() != 1 or graph_ptr.numel() < 1:
+        raise ValueError("set2set: graph_ptr needs at least one entry (B + 1 node offsets, the last one N)")
+    N, d = x.shape
+    B, T = graph_ptr.numel() - 1, int(steps)
+    if tuple(w_ih.shape) != (4 * d, 2 * d) or tuple(w_hh.shape) != (4 * d, d) or b_ih.numel() != 4 * d or b_hh.numel() != 4 * d:
+        raise ValueError(f"set2set: LSTM tensors do not match d = {d}")
+    w_ih, w_hh, b_ih, b_hh = (_f32c(t, n) for t, n in ((w_ih, "weight_ih_l0"), (w_hh, "weight_hh_l0"), (b_ih, "bias_ih_l0"), (b_hh, "bias_hh_l0")))
+    dev = x.device
+    out = torch.empty(B, 2 * d, dtype=torch.float32, device=dev)
+    work = torch.empty(12 * d * d + 4 * d, dtype=torch.float32, device=dev)
+    tape = None
+    if want_tape:
+        tape = tuple(torch.empty(s, dtype=torch.float32, device=dev)
+                     for s in ((T, B, 3 * d), (T, B, 4 * d), (T, B, d), (T, N), (T, B, 2)))
+    tp = [ptr(t) for t in tape] if tape is not None else [None] * 5
+    with _span("sn_set2set_f32"):
+        check(lib().sn_set2set_f32(ptr(x), N, d, ptr(graph_ptr), B, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), T, ptr(out), ptr(work),
+                                   *tp, stream()), "sn_set2set_f32")
+    return (out, tape) if want_tape else out

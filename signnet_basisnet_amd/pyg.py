@@ -213,8 +213,18 @@ class SignNet(nn.Module):
 
 
 class GNN(nn.Module):
-    def __init__(self, nfeat_node, nfeat_edge, nhid, nout, nlayer, variant, pooling="add"):
+    """Parameter holder of the GINE network inside SignNetGNN and — `variant='gine'` — a model of its own: `forward(data,
+    additional_x=None)` is the plain GINE baseline GINESignNetPyG's default run trains (train/zinc.py:31-46 with model.gnn_type GINEConv:
+    GNN(None, None, nhid, 1, nlayer, 'GINEConv', dropout, pool, res=True), core/model.py:44-79), layer at a time on the kernels
+    SignNetGNN's layer path uses (the fused GINE stage is not involved).  dropout > 0 and res=False are not built."""
+
+    def __init__(self, nfeat_node, nfeat_edge, nhid, nout, nlayer, variant, pooling="add", dropout=0, res=True):
         super().__init__()
+        if dropout:
+            raise NotImplementedError("GNN: dropout > 0 is not built on the HIP path (core/config.py's default is 0)")
+        if not res:
+            raise NotImplementedError("GNN: res=False is not built on the HIP path (train/zinc.py builds res=True)")
+        self.variant = variant
         nv = 6 if variant == "alchemy" else 500      # elements.py:22
         self.input_encoder = DiscreteEncoder(nhid, max_num_values=nv) if nfeat_node is None else MLP(nfeat_node, nhid, 1)
         self.edge_encoders = nn.ModuleList([DiscreteEncoder(nhid, max_num_values=nv) if nfeat_edge is None
@@ -238,6 +248,127 @@ class GNN(nn.Module):
             e.reset_parameters()
             c.reset_parameters()
             n.reset_parameters()
+
+    # ------------------------------------------------------------------ the model on its own (core/model.py:44-79)
+    def train(self, mode=True):
+        _drop_eval_cache(self)              # the packed eval-mode weights: parameters may change before the next eval forward
+        return super().train(mode)
+
+    def invalidate(self):
+        """Call after modifying parameters in place while in eval mode (as SignNetGNN.invalidate)."""
+        _drop_eval_cache(self)
+
+    def forward(self, data, additional_x=None):
+        if self.variant != "gine":
+            raise NotImplementedError("GNN.forward: only GINESignNetPyG's GNN is a model of its own (no script builds Alchemy's)")
+        ea = data.edge_attr
+        if ea is None:                      # core/model.py:55-57
+            ea = data.edge_index.new_zeros(data.edge_index.size(-1))
+        ops.require_cuda(data.x, data.edge_index, data.batch, ea, additional_x)
+        grad = self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if self.training:
+            _drop_eval_cache(self)
+        with _lib_mod.stream_scope(), ops.batched_bn_counters():
+            return self._forward_grad(data, ea, additional_x) if grad else self._forward_layers(data, ea, additional_x, self.training)
+
+    @staticmethod
+    def _node_ids(data):
+        return data.x.squeeze() if data.x.dim() > 1 and data.x.shape[-1] == 1 else data.x
+
+    @staticmethod
+    def _graph_sizes(plan):
+        return (plan.graph_ptr[1:] - plan.graph_ptr[:-1]).long()
+
+    def _forward_layers(self, data, ea, additional_x, train):
+        """Eval (BatchNorm folded into the GEMM epilogues) and the train-mode forward without autograd (batch statistics, running-statistics
+        update): one launch per op."""
+        fold = not train
+        plan = ops.build_plan(data.batch, data.edge_index, int(data.num_graphs), 0)
+        status = plan.status[5:6]
+        cache = _eval_cache(self) if fold else {}       # eval: packed weights and folded BatchNorms live until a parameter or buffer changes
+
+        def pack(lin):
+            if id(lin) not in cache:
+                cache[id(lin)] = _pack(lin)
+            return cache[id(lin)]
+
+        def lin_bn(x, lin, norm, relu=True, residual=None):
+            if isinstance(norm, _Identity):
+                return ops.masked_linear(x, pack(lin), relu=relu, residual=residual)
+            if id(norm) not in cache:
+                cache[id(norm)] = _BN(norm, fold)
+            return _lin_bn(x, pack(lin), cache[id(norm)], train, relu=relu, residual=residual)
+
+        def encode(enc, v):
+            if isinstance(enc, DiscreteEncoder):
+                return ops.embedding_sum(v, [e.weight.detach() for e in enc.embeddings], status)
+            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+
+        h = encode(self.input_encoder, self._node_ids(data))
+        if additional_x is not None:
+            h = ops.masked_linear(torch.cat([h, additional_x], dim=-1), pack(self.linear))
+        for enc, conv, norm in zip(self.edge_encoders, self.convs, self.norms):
+            u = ops.gine_aggregate(h, encode(enc, ea), plan, conv.layer.eps.detach())
+            u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
+            h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+        pooled = ops.segment_pool(h, plan, self.pooling)
+        if self.pooling == "mean":
+            size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], status)
+            pooled = ops.masked_affine(pooled, residual=size)
+        oe = self.output_encoder
+        y = ops.masked_linear(lin_bn(pooled, oe.layers[0], oe.norms[0]), pack(oe.layers[1]))
+        plan.check()                        # one host sync: malformed batch, or an id outside its embedding table (nn.Embedding raises too)
+        return y
+
+    def _forward_grad(self, data, ea, additional_x):
+        """Train mode under autograd: the launches and adjoints of SignNetGNN's differentiable GINE network (autograd.py, train_stage.py)."""
+        from . import autograd as AG
+        from . import train_stage as T
+        B = int(data.num_graphs)
+        plan = ops.build_plan(data.batch, data.edge_index, B, 0)
+        rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
+        status = plan.status[5:6]
+        d = self.linear.weight.shape[0]
+        stage = T.supported(d, d)
+
+        def lin_bn(x, lin, norm, relu=True, residual=None):
+            if isinstance(norm, _Identity):
+                y = AG.linear(x, lin.weight, lin.bias, None, 0, relu=relu)
+                return y if residual is None else AG.masked_add(y, residual, None, 0)
+            if stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
+                return T.lin_bn(x, lin, norm, None, 0, relu=relu, residual=residual)
+            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, None, 0, relu=relu, residual=residual)
+
+        def encode(enc, v):
+            if isinstance(enc, DiscreteEncoder):
+                return AG.embedding_sum(v, [e.weight for e in enc.embeddings], status)
+            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+
+        h = encode(self.input_encoder, self._node_ids(data))
+        if additional_x is not None:
+            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, None, 0)
+        staged = stage and all(isinstance(c.nn.norms[0], nn.BatchNorm1d) for c in self.convs)
+        e_all = None
+        if staged and all(isinstance(enc, DiscreteEncoder) for enc in self.edge_encoders) and 1 < len(self.edge_encoders) <= 16:
+            # every layer embeds the same edge_attr with its own tables: one [L, E, C] block, one adjoint launch pair for all layers
+            e_all = AG.embedding_sum_layers(ea, [[t.weight for t in enc.embeddings] for enc in self.edge_encoders], status)
+        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
+            if e_all is not None:
+                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li)
+            elif staged:
+                h = T.gine_layer(h, encode(enc, ea), conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan)
+            else:
+                u = AG.gine_aggregate(h, encode(enc, ea), conv.layer.eps, plan, rplan)
+                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+        pooled = AG.segment_pool(h, plan, self.pooling)
+        if self.pooling == "mean":
+            pooled = AG.masked_add(pooled, AG.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight], status), None, 0)
+        oe = self.output_encoder
+        y = lin_bn(pooled, oe.layers[0], oe.norms[0])
+        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, None, 0)
+        plan.check()
+        return y
 
 
 # ----------------------------------------------------------------------------- prepared (packed) parameters
@@ -273,6 +404,22 @@ def _pack(lin: nn.Linear) -> ops.PackedLinear:
     w = lin.weight.detach()
     return ops.PackedLinear(ops.pack_weight(w), w.shape[0], w.shape[1],
                             None if lin.bias is None else lin.bias.detach().contiguous())
+
+
+def _eval_cache(module):
+    """Per-module dict of eval-mode derived tensors (packed weights, folded BatchNorms).  It is rebuilt when a parameter or buffer is
+    replaced or written through torch (storage address and version counter of each: load_state_dict, .to(), p.data.copy_()) and dropped
+    by `_drop_eval_cache` — train()/eval() and every forward outside eval mode call it, because the device optimisers (optim.Adam,
+    optim.FlatAdam) write parameters through raw pointers, which moves neither."""
+    key = tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
+    ent = module.__dict__.get("_sn_eval_cache")
+    if ent is None or ent[0] != key:
+        ent = module.__dict__["_sn_eval_cache"] = (key, {})
+    return ent[1]
+
+
+def _drop_eval_cache(module):
+    module.__dict__.pop("_sn_eval_cache", None)
 
 
 def _drop_prepared(module, incompatible_keys=None):
