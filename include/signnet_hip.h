@@ -1128,6 +1128,35 @@ int sn_set2set_bwd_f32(const float* x, int64_t N, int d, const int32_t* graph_pt
                        const float* out, const float* dout, const float* tape_in, const float* tape_act, const float* tape_cell,
                        const float* tape_e, const float* tape_md, float* dx, float* dgate, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Polynomial filters of one sparse operator on ONE graph of N nodes (the LearningFilters baselines BernNet / GPRNet / ChebNet / GcnNet,
+ * models.py:138-377): all K propagation steps of a layer in one launch, a workgroup per slice of feature channels, iterates in LDS.
+ *   S = diag_add * I + scale * W,  (W x)_i = sum_{e in [rowptr[i], rowptr[i+1])} w[e] x[col[e]]   (CSR by destination, nnz entries; self
+ *   loops are ordinary entries; entries with a column outside [0, N) are skipped).
+ * mode SN_POLY_MONOMIAL: P_k(S) = S^k;  SN_POLY_CHEBYSHEV: P_0 = I, P_1 = S, P_k = 2 S P_{k-1} - P_{k-2}.
+ * A "stack" argument p with strides (sk, ld) holds element (k, node, channel) at p[k * sk + node * ld + channel], ld >= d; sk = 0 is one
+ * [N, d] block shared by every k; `reverse` reads block K - k where k is meant; `*_f64` != 0: the stack holds doubles (strides in
+ * elements) — for a stack that one launch hands the next, so that nothing is rounded to fp32 in between.  x and y are [N, d] row-major
+ * fp32, any d >= 1.
+ * sn_poly_basis_f32:   B_k = P_k(S) x, k = 0..K, written to the stack B (or B = NULL: not stored).  With g (a stack) and dot_part
+ *                      [sn_poly_filter_launch_shape(N, d, ...), K+1]: dot_part[s][k] = <B_k, g_k> over the channels of slice s; the sum over s in
+ *                      slice order (sn_train_reduce_parts_f32(dot_part, slices, K+1, K+1, out, ...)) is the coefficient gradient.
+ * sn_poly_combine_f32: y = sum_k c[k] P_k(S) a_k by Horner / Clenshaw (K applications of S); c = NULL means ones.
+ * The two are adjoint: with S^T (the transposed CSR) in place of S, d a_k = c_k * basis(g)_k and d x of basis = combine of its dB.
+ * Inputs and outputs are fp32; inside a launch the iterates and every sum are doubles (nothing is rounded to fp32 between the K steps).
+ * N <= sn_poly_filter_max_nodes(K, mode) (8192 for every K and mode; 0 for invalid arguments); a larger N is SN_ERR_ARG before any
+ * launch.  No atomics, one owner and a fixed order per sum: bit-reproducible. */
+#define SN_POLY_MONOMIAL 0
+#define SN_POLY_CHEBYSHEV 1
+int sn_poly_filter_max_nodes(int K, int mode);
+int sn_poly_filter_launch_shape(int64_t N, int d, int* threads, int64_t* lds_bytes);
+int sn_poly_basis_f32(const float* x, int64_t N, int d, int K, int mode, const int32_t* rowptr, const int32_t* col, const float* w,
+                      int64_t nnz, float diag_add, float scale, void* B, int64_t b_sk, int64_t b_ld, int b_f64, const void* g,
+                      int64_t g_sk, int64_t g_ld, int g_reverse, int g_f64, float* dot_part, void* stream);
+int sn_poly_combine_f32(const void* a, int64_t a_sk, int64_t a_ld, int a_reverse, int a_f64, int64_t N, int d, int K, int mode,
+                        const int32_t* rowptr, const int32_t* col, const float* w, int64_t nnz, float diag_add, float scale,
+                        const float* c, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -765,3 +765,143 @@ class _Set2Set(Function):
 def set2set(x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps):
     """Differentiable ops.set2set: gradients of x and of the four LSTM tensors (bit-reproducible: no atomics anywhere)."""
     return _Set2Set.apply(x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps)
+
+
+# ----------------------------------------------------------------------------- polynomial filters of one sparse operator (csrc/poly_filter.hip)
+# y = sum_k c_k P_k(S) a_k (sn_poly_combine_f32) and B_k = P_k(S) x (sn_poly_basis_f32) are adjoint over the transposed operator `op.t`:
+# every backward below is the other entry point, one launch whatever K.
+def _column_sums(dy):
+    """[R, C] -> [C], rows added in order (sn_train_reduce_parts_f32 with one part per row)."""
+    R, Cc = dy.shape
+    out = torch.empty(Cc, dtype=torch.float32, device=dy.device)
+    with ops._span("sn_train_reduce_parts_f32"):
+        check(lib().sn_train_reduce_parts_f32(ptr(dy), R, Cc, Cc, ptr(out), 0, stream()), "sn_train_reduce_parts_f32")
+    return out
+
+
+class _PolyCombineShared(Function):
+    """y = sum_k c_k P_k(S) x with scalar coefficients (GPR_prop: c = temp; GCNConv: c = [0, 1]).  dx = sum_k c_k P_k(S^T) g;
+    dc_k = <g, P_k(S) x>."""
+
+    @staticmethod
+    def forward(ctx, x, c, op, K, mode, diag_add, scale):
+        x = _c(x)
+        cd = None if c is None else _c(c.detach())
+        ctx.save_for_backward(x, cd)
+        ctx.meta = (op, K, mode, diag_add, scale)
+        return ops.poly_combine(x, op, K, mode, diag_add, scale, cd)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, cd = ctx.saved_tensors
+        op, K, mode, diag_add, scale = ctx.meta
+        g = _c(g)
+        dx = ops.poly_combine(g, op.t, K, mode, diag_add, scale, cd) if ctx.needs_input_grad[0] else None
+        dc = None
+        if cd is not None and ctx.needs_input_grad[1]:
+            dc = ops.poly_basis(x, op, K, mode, diag_add, scale, want_stack=False, g=g)
+        return dx, dc, None, None, None, None, None
+
+
+def poly_combine_shared(x, c, op, K, mode="monomial", diag_add=0.0, scale=1.0):
+    return _PolyCombineShared.apply(x, c, op, K, mode, diag_add, scale)
+
+
+class _BernProp(Function):
+    """BernConv's propagation (models.py:316-340) in two launches: with L = I - A (diag_add 1, scale -1) and M = 2I - L = I + A, which
+    commute, out = sum_i c_i L^i M^(K-i) x  =  combine over L of the reversed stack T_k = M^k x.  Adjoint: U_i = (L^T)^i g,
+    dc_i = <U_i, T_(K-i)>, dx = sum_i c_i (M^T)^(K-i) U_i = combine over M^T of the reversed U with the reversed c (`crev`)."""
+
+    @staticmethod
+    def forward(ctx, x, c, crev, op, K):
+        x = _c(x)
+        cd, crev = _c(c.detach()), _c(crev.detach())
+        T = ops.poly_basis(x, op, K, "monomial", 1.0, 1.0, stack_dtype=torch.float64)      # handed to the next launch unrounded
+        ctx.save_for_backward(T, cd, crev)
+        ctx.meta = (op, K)
+        return ops.poly_combine(T, op, K, "monomial", 1.0, -1.0, cd, reverse=True)
+
+    @staticmethod
+    def backward(ctx, g):
+        T, cd, crev = ctx.saved_tensors
+        op, K = ctx.meta
+        U, dc = ops.poly_basis(_c(g), op.t, K, "monomial", 1.0, -1.0, g=T, g_reverse=True, stack_dtype=torch.float64)
+        dx = ops.poly_combine(U, op.t, K, "monomial", 1.0, 1.0, crev, reverse=True) if ctx.needs_input_grad[0] else None
+        return dx, (dc if ctx.needs_input_grad[1] else None), None, None, None
+
+
+def bern_prop(x, c, crev, op, K):
+    """sum_i c[i] L^i (2I - L)^(K-i) x on FilterGraph.lap; c [K+1] = C(K,i) / 2^K * relu(coe[i]), crev = c reversed (not differentiated)."""
+    return _BernProp.apply(x, c, crev, op, K)
+
+
+class _ChebConv(Function):
+    """relu?(sum_k T_k(S) (x W_k^T) + b) — PyG's ChebConv with the K GEMMs first and Clenshaw's recurrence over their outputs a_k (one
+    launch), then the bias / ReLU pass.  Adjoint: d a_k = T_k(S^T) dz from sn_poly_basis_f32, dW_k = d a_k^T x, dx = sum_k d a_k W_k
+    (each GEMM adds the running sum as its residual)."""
+
+    @staticmethod
+    def forward(ctx, x, bias, op, diag_add, scale, relu, *weights):
+        x = _c(x)
+        Kp1, d_out, N = len(weights), weights[0].shape[0], x.shape[0]
+        A = torch.empty(Kp1, N, d_out, dtype=torch.float32, device=x.device)
+        for k, W in enumerate(weights):
+            Wd = _c(W.detach())
+            ops.masked_linear(x, ops.PackedLinear(ops.pack_weight(Wd), d_out, Wd.shape[1], None), out=A[k])
+        z = ops.poly_combine(A, op, Kp1 - 1, "chebyshev", diag_add, scale)
+        y = ops.masked_affine(z, scale=ops.ones_vector(d_out, x.device), shift=_c(bias.detach()), relu=relu)
+        ctx.save_for_backward(x, y if relu else None, *weights)
+        ctx.meta = (op, diag_add, scale, relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, *weights = ctx.saved_tensors
+        op, diag_add, scale, relu = ctx.meta
+        g = _c(g)
+        dz = relu_bwd(y, g, None, 0) if relu else g
+        db = _column_sums(dz) if ctx.needs_input_grad[1] else None
+        dA = ops.poly_basis(dz, op.t, len(weights) - 1, "chebyshev", diag_add, scale)
+        dx, dWs = None, []
+        for k, W in enumerate(weights):
+            dWs.append(linear_wgrad(x, dA[k], None, 0, want_bias=False)[0])
+            if ctx.needs_input_grad[0]:
+                Wd = _c(W.detach())
+                plt = ops.PackedLinear(ops.pack_weight_t(Wd), Wd.shape[1], Wd.shape[0], None)
+                dx = ops.masked_linear(dA[k], plt, use_bias=False, residual=dx)
+        return (dx, db, None, None, None, None, *dWs)
+
+
+def cheb_conv(x, weights, bias, op, diag_add=0.0, scale=-1.0, relu=False):
+    return _ChebConv.apply(x, bias, op, diag_add, scale, relu, *weights)
+
+
+class _LinearIO(Function):
+    """[relu](x @ W + b) for a weight stored [d_in, d_out] (BernConv.weight, models.py:301,342): _Linear without a transposed copy — the
+    forward packs W^T in place, the adjoints swap roles (dx = dy @ W^T reads W as an nn.Linear weight, dW = x^T dy)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, relu):
+        x, Wd = _c(x), _c(W.detach())
+        pl = ops.PackedLinear(ops.pack_weight_t(Wd), Wd.shape[1], Wd.shape[0], None if b is None else _c(b.detach()))
+        y = ops.masked_linear(x, pl, relu=relu)
+        ctx.save_for_backward(x, Wd, y if relu else None)
+        ctx.meta = (relu, b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, Wd, y = ctx.saved_tensors
+        relu, has_b = ctx.meta
+        dy = _c(dy)
+        if relu:
+            dy = relu_bwd(y, dy, None, 0)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.masked_linear(dy, ops.PackedLinear(ops.pack_weight(Wd), Wd.shape[0], Wd.shape[1], None), use_bias=False)
+        dW = linear_wgrad(dy, x, None, 0, want_bias=False)[0]
+        return dx, dW, (_column_sums(dy) if has_b else None), None
+
+
+def linear_io(x, W, b=None, relu=False):
+    return _LinearIO.apply(x, W, b, relu)

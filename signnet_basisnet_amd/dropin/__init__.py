@@ -59,6 +59,14 @@ BASELINE_ALIASES = {
     "gine_pyg": {"core.model": _PKG + ".baseline_core_model"},
 }
 
+# Opt-in with the same flag, for a name ALIASES already answers: the module that answers it INSTEAD.  LearningFilters keeps its baselines
+# in the same `models.py` as the base networks (training.py:9), so `models` cannot move into BASELINE_ALIASES; with baselines=True it is
+# bound to a module that adds the four polynomial-filter baselines (BernNet, GPRNet, ChebNet, GcnNet: filter_baselines.py) and resolves
+# everything else — GatNet and ARMANet included — exactly as `learningfilters/models.py` does.
+BASELINE_OVERRIDES = {
+    "learningfilters": {"models": _PKG + ".baseline_filter_models"},
+}
+
 # entry script (basename) -> tree, for the runner
 SCRIPTS = {
     "main_alchemy.py": "alchemy",
@@ -99,6 +107,7 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         self.table = dict(ALIASES[tree])
         if baselines:
             self.table.update(BASELINE_ALIASES.get(tree, {}))
+            self.table.update(BASELINE_OVERRIDES.get(tree, {}))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -109,13 +118,14 @@ class AliasFinder(importlib.abc.MetaPathFinder):
 
 def install(tree: str, baselines: bool = False) -> AliasFinder:
     """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
-    `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN); a finder installed without them is extended in place."""
+    `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN) and rebinds those of `BASELINE_OVERRIDES[tree]` (LearningFilters' `models`, with
+    the four polynomial-filter baselines); a finder installed without them is extended in place."""
     shim_dir(tree)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
             if baselines:
-                for name, impl in BASELINE_ALIASES.get(tree, {}).items():
-                    if name not in f.table:
+                for name, impl in {**BASELINE_ALIASES.get(tree, {}), **BASELINE_OVERRIDES.get(tree, {})}.items():
+                    if f.table.get(name) != impl:
                         f.table[name] = impl
                         sys.modules.pop(name, None)
             return f

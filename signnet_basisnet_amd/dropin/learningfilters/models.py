@@ -5,6 +5,11 @@
 The six spectral graph-convolution baselines of that import line are competitors of the path, not part of it: they resolve,
 lazily, to the reference's own `models.py` found later on `sys.path` (which needs torch_geometric, as it always did); without
 a reference tree on the path they are placeholders that raise on construction, so the import line itself always succeeds.
+
+Four of the six — BernNet, GPRNet, ChebNet, GcnNet, polynomial filters of the graph operator — also exist on the HIP stack
+(`signnet_basisnet_amd.filter_baselines`).  This module never binds them: `dropin.install('learningfilters', baselines=True)` (the
+runner's `--baselines`) answers `models` with `dropin/baseline_filter_models.py` instead, which adds those four and delegates every
+other name here.
 """
 import os as _os
 

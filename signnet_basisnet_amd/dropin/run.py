@@ -11,7 +11,8 @@ and GINESignNetPyG's README runs `python -m train.zinc` from the tree root, whic
 difference to a plain run is the finder of `dropin.install(tree)`: the names listed in `dropin.ALIASES[tree]` come from this
 package, everything else from the tree.  `--tree` overrides the guess from the script's file name.  `--baselines` (before the script)
 also binds the trees' baseline models, `dropin.BASELINE_ALIASES`: `baseline_gin` (NetGINE) and `core.model` (the plain GINE GNN of
-`model.gnn_type GINEConv`); without it both stay the tree's.
+`model.gnn_type GINEConv`); without it both stay the tree's.  For LearningFilters it rebinds `models`
+(`dropin.BASELINE_OVERRIDES`) so that BernNet, GPRNet, ChebNet and GcnNet are the HIP classes of `filter_baselines.py`.
 """
 from __future__ import annotations
 

@@ -11,8 +11,12 @@ Mirrors, on the device ops of this package:
                                                   FilterArgs and a GridEigen
   training.py:87-130  get_lap_feat             -> get_lap_feat
   training.py:132-150 train                    -> train_step;  :224-246 the epoch loop -> fit
-The graph-convolution baselines of gen_model (ChebNet, BernNet, GcnNet, GatNet, ARMANet, GPRNet) and the 'abs_val' / 'sign_flip'
-feature variants are the paper's comparison rows, not the sign/basis-invariant path: they raise NotImplementedError.
+The graph-convolution baselines of gen_model are the paper's comparison rows.  BernNet, GPRNet, ChebNet and GcnNet are polynomial filters
+of the graph operator and run on this stack (filter_baselines.py, csrc/poly_filter.hip) when asked for: `gen_model(..., baselines=True)`
+builds them, and `train_step` / `GraphedEpoch` / `fit` hand them the graph through `graph=` (a filter_baselines.FilterGraph or the
+edge_index tensor; the reference passes data.edge_index, training.py:140).  Without the flag every name of GRAPH_CONV_BASELINES raises
+NotImplementedError as before; GatNet and ARMANet (PyG's GATConv / ARMAConv: not polynomials of the operator) raise with it too.
+The 'abs_val' / 'sign_flip' feature variants (training.py:94-100) are one launch of ops.lap_pe_transform.
 
 Everything is differentiable in train mode (autograd.py ops; backward kernels in csrc/backward.hip and csrc/dense_attention.hip).
 One thing is done differently on purpose: the reference re-contracts the 2.15 GB projector stack in every epoch
@@ -199,13 +203,18 @@ def gen_rho(args: FilterArgs, eig: GridEigen):
     return rho
 
 
-def gen_model(args: FilterArgs, eig: GridEigen, device="cuda"):
-    """training.py:152-181: the base network, with `sign_inv_net` / `basis_inv_net` and `rho` attached as attributes."""
+def gen_model(args: FilterArgs, eig: GridEigen, device="cuda", baselines=False):
+    """training.py:152-181: the base network, with `sign_inv_net` / `basis_inv_net` and `rho` attached as attributes.
+    baselines=True: BernNet / GPRNet / ChebNet / GcnNet are built (filter_baselines.py); GatNet and ARMANet raise either way."""
     d_in = 1 + eig.pe_dim
-    if args.net in GRAPH_CONV_BASELINES:
+    if args.net in GRAPH_CONV_BASELINES and baselines:
+        from .filter_baselines import gen_baseline
+        model = gen_baseline(args.net, d_in, hidden_channels=args.hidden_channels, num_layers=args.num_layers)
+    elif args.net in GRAPH_CONV_BASELINES:
         raise NotImplementedError(f"{args.net}: the graph-convolution baselines of the filter table are not part of the "
-                                  "sign / basis invariant path (SURVEY.md §8 'out of scope')")
-    if args.net == "MLP":
+                                  "sign / basis invariant path (SURVEY.md §8 'out of scope'); gen_model(..., baselines=True) builds "
+                                  "BernNet, GPRNet, ChebNet and GcnNet")
+    elif args.net == "MLP":
         model = MLP(d_in, hidden_channels=args.hidden_channels, num_layers=args.num_layers)
     elif args.net == "DS":
         model = EqDeepSetsEncoder(d_in, hidden_channels=args.hidden_channels, num_layers=args.num_layers)
@@ -235,15 +244,20 @@ def basis_inv_outputs(model, eig: GridEigen):
     return outs
 
 
-def get_lap_feat(use_eig, eig: GridEigen, feat, lap_method, model):
-    """training.py:87-130 ('none', 'sign_inv', 'basis_inv').  feat [N, 1] -> [N, 1 + PE_DIM]."""
+def get_lap_feat(use_eig, eig: GridEigen, feat, lap_method, model, u=None):
+    """training.py:87-130.  feat [N, 1] -> [N, 1 + PE_DIM].  'abs_val' and 'sign_flip' are one launch of ops.lap_pe_transform;
+    'sign_flip' takes its k uniforms from `u` (float32 [k]) or draws them as the reference does: torch.rand(k) on the host, >= 0.5 -> +1."""
     if not use_eig:
         return feat
     N = eig.N
     if lap_method == "none":
         return torch.cat((feat, eig.eigvecs, eig.eigvals_mat), dim=-1).to(feat)
     if lap_method in ("abs_val", "sign_flip"):
-        raise NotImplementedError(f"lap_method {lap_method}: a baseline of the filter table, not the sign / basis invariant path")
+        if lap_method == "sign_flip":
+            u = torch.rand(eig.eigvecs.shape[1]) if u is None else u
+            u = u.to(device=feat.device, dtype=torch.float32).contiguous()
+        pe = ops.lap_pe_transform(eig.eigvecs, lap_method, u=u if lap_method == "sign_flip" else None)
+        return torch.cat((feat, pe, eig.eigvals_mat), dim=-1).to(feat)
     if "sign_inv" in lap_method:
         if "eigval" in lap_method:
             raise NotImplementedError("Eigval in sign inv not done yet")                       # the reference's own message
@@ -266,14 +280,15 @@ def masked_square_loss(pre, y, m):
     return torch.square(m * (pre - y)).sum()
 
 
-def train_step(model, optimizer, args: FilterArgs, eig: GridEigen, x, y, m):
+def train_step(model, optimizer, args: FilterArgs, eig: GridEigen, x, y, m, graph=None):
     """One epoch of training.py:132-150 for one image: x [N, 1] the signal, y [N, 1] the filtered target, m [N, 1] the boundary
-    mask.  Returns (loss tensor on the device, prediction)."""
+    mask; graph: the model's second argument (data.edge_index in the reference; the filter baselines need it, a FilterGraph or the
+    edge tensor).  Returns (loss tensor on the device, prediction)."""
     model.train()
     optimizer.zero_grad()
     with ops.batched_bn_counters():
         feat = get_lap_feat(args.use_eig, eig, x, args.lap_method, model)
-        pre = model(feat, None)
+        pre = model(feat, graph)
     loss = masked_square_loss(pre, y, m)
     loss.backward()
     optimizer.step()
@@ -288,17 +303,20 @@ class GraphedEpoch:
     device tensors; `step()` returns the same (loss, prediction) tensors every time, refreshed in place.
     Same arithmetic, same kernels, same order as the eager train_step: the loss trajectory is bitwise identical."""
 
-    def __init__(self, model, optimizer, args: FilterArgs, eig: GridEigen, x, y, m, warmup=2):
+    def __init__(self, model, optimizer, args: FilterArgs, eig: GridEigen, x, y, m, warmup=2, graph=None):
         from .optim import FlatAdam
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("GraphedEpoch needs optim.FlatAdam (static flat parameter / gradient buffers)")
+        if args.use_eig and args.lap_method == "sign_flip":
+            raise NotImplementedError("GraphedEpoch: 'sign_flip' draws fresh signs on the host every epoch (training.py:97), which a "
+                                      "captured graph cannot replay; use train_step")
         self.model, self.optimizer = model, optimizer
         model.train()
 
         def fwd_bwd():
             optimizer.flat_g.zero_()
             feat = get_lap_feat(args.use_eig, eig, x, args.lap_method, model)
-            pre = model(feat, None)
+            pre = model(feat, graph)
             loss = masked_square_loss(pre, y, m)
             loss.backward()
             return loss, pre
@@ -334,19 +352,20 @@ def r2_score(target, pred):
     return float(1.0 - ss_res / ss_tot) if ss_tot > 0 else 0.0
 
 
-def fit(args: FilterArgs, eig: GridEigen, x, y, m, epochs=None, model=None, optimizer=None, log=None, use_graph=False):
+def fit(args: FilterArgs, eig: GridEigen, x, y, m, epochs=None, model=None, optimizer=None, log=None, use_graph=False, graph=None):
     """The per-image loop of training.py:229-250: a fresh model, Adam(lr), `epochs` steps; keeps the minimum loss and its r2.
     Returns {'min_loss', 'best_r2', 'epoch', 'model'}.  The loss is read back once per epoch, as the reference's loss.item() does.
-    use_graph: replay the epoch as a captured HIP graph (GraphedEpoch; optimiser = optim.FlatAdam)."""
+    use_graph: replay the epoch as a captured HIP graph (GraphedEpoch; optimiser = optim.FlatAdam).  graph: the model's second argument
+    (the filter baselines' FilterGraph or edge tensor; with it a fresh model is built with baselines=True)."""
     from .optim import Adam, FlatAdam
-    model = model if model is not None else gen_model(args, eig, x.device)
+    model = model if model is not None else gen_model(args, eig, x.device, baselines=graph is not None)
     if optimizer is None:
         optimizer = FlatAdam(model.parameters(), lr=args.lr) if use_graph else Adam(model.parameters(), lr=args.lr)
-    graphed = GraphedEpoch(model, optimizer, args, eig, x, y, m) if use_graph else None
+    graphed = GraphedEpoch(model, optimizer, args, eig, x, y, m, graph=graph) if use_graph else None
     best = {"min_loss": float("inf"), "best_r2": 0.0, "epoch": 0, "model": model}
     keep = m.reshape(-1) == 1
     for epoch in range(args.epochs if epochs is None else epochs):
-        loss, pre = graphed.step() if graphed is not None else train_step(model, optimizer, args, eig, x, y, m)
+        loss, pre = graphed.step() if graphed is not None else train_step(model, optimizer, args, eig, x, y, m, graph)
         lv = loss.item()
         if best["min_loss"] > lv:
             best.update(min_loss=lv, best_r2=r2_score(y[keep], pre[keep]), epoch=epoch)

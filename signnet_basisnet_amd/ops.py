@@ -1400,3 +1400,123 @@ def set2set(x, graph_ptr, w_ih, w_hh, b_ih, b_hh, steps, want_tape=False):
         check(lib().sn_set2set_f32(ptr(x), N, d, ptr(graph_ptr), B, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), T, ptr(out), ptr(work),
                                    *tp, stream()), "sn_set2set_f32")
     return (out, tape) if want_tape else out
+
+
+# ----------------------------------------------------------------------------- polynomial filters of one sparse operator (csrc/poly_filter.hip)
+POLY_MONOMIAL, POLY_CHEBYSHEV = 0, 1
+POLY_MODES = {"monomial": POLY_MONOMIAL, "chebyshev": POLY_CHEBYSHEV}
+
+
+@dataclass
+class SparseOperator:
+    """W of S = diag_add * I + scale * W in CSR by destination, for ONE graph of N nodes: (W x)_i = sum over e in row i of w[e] x[col[e]].
+    `t` is the operator of W^T (the adjoints run over it); filter_baselines.FilterGraph builds both."""
+    rowptr: torch.Tensor      # int32 [N + 1]
+    col: torch.Tensor         # int32 [nnz]
+    w: torch.Tensor           # float32 [nnz]
+    N: int
+    t: "SparseOperator" = None
+
+    @property
+    def nnz(self):
+        return self.col.numel()
+
+
+def poly_filter_max_nodes(K, mode="monomial"):
+    """The LDS-bound node capacity of sn_poly_basis_f32 / sn_poly_combine_f32."""
+    return int(lib().sn_poly_filter_max_nodes(int(K), POLY_MODES.get(mode, mode)))
+
+
+def _poly_check(fn, op, K, mode, x):
+    m = POLY_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if m not in (POLY_MONOMIAL, POLY_CHEBYSHEV):
+        raise ValueError(f"{fn}: unknown mode {mode!r} (one of {sorted(POLY_MODES)})")
+    K = int(K)
+    if K < 0:
+        raise ValueError(f"{fn}: K must be >= 0")
+    cap = poly_filter_max_nodes(K, m)
+    if op.N > cap:                                   # before any launch (and before the tensors are looked at)
+        raise ValueError(f"{fn}: the graph has {op.N} nodes, above the LDS-bound capacity {cap} of the polynomial-filter kernels")
+    require_cuda(x, op.rowptr, op.col, op.w)
+    if op.N < 1 or op.rowptr.dtype != torch.int32 or op.rowptr.numel() != op.N + 1 or op.col.dtype != torch.int32 or \
+            op.w.dtype != torch.float32 or op.w.numel() != op.nnz:
+        raise ValueError(f"{fn}: malformed SparseOperator")
+    return K, m
+
+
+def _stack_strides(fn, t, N, d, K, name):
+    """(sk, ld) of a [N, d] block shared by every k or a [K+1, N, d] stack: unit channel stride, any node / k strides."""
+    if t.dtype not in (torch.float32, torch.float64) or t.stride(-1) != 1 and d > 1:
+        raise ValueError(f"{fn}: {name} must be float32 (or a float64 stack) with unit channel stride")
+    if t.dim() == 2 and tuple(t.shape) == (N, d):
+        return 0, (t.stride(0) if N > 1 else d)
+    if t.dim() == 3 and tuple(t.shape) == (K + 1, N, d):
+        return (t.stride(0) if K > 0 else 0), (t.stride(1) if N > 1 else d)
+    raise ValueError(f"{fn}: {name} must be [N, d] = {(N, d)} or [K+1, N, d] = {(K + 1, N, d)}, got {tuple(t.shape)}")
+
+
+def poly_basis(x, op: SparseOperator, K, mode="monomial", diag_add=0.0, scale=1.0, *, want_stack=True, g=None, g_reverse=False,
+               stack_dtype=torch.float32):
+    """B_k = P_k(S) x, k = 0..K, in ONE launch (sn_poly_basis_f32): x [N, d] -> B [K+1, N, d] (want_stack=False: not
+    stored).  g ([N, d] or a [K+1, N, d] stack, read in reverse order with g_reverse): also
+    dots [K+1] = <B_k, g_k>, the per-slice partials finished in slice order by sn_train_reduce_parts_f32.  Returns B, dots or (B, dots).
+    stack_dtype=torch.float64 (and a float64 `g`): the stack holds the kernel's doubles unrounded — for a stack that goes straight
+    into poly_combine or back into poly_basis as `g` (Bernstein), where an fp32 rounding in between is amplified by the second launch."""
+    K, m = _poly_check("poly_basis", op, K, mode, x)
+    require_cuda(g)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[0] != op.N:
+        raise ValueError(f"poly_basis: x must be contiguous float32 [N = {op.N}, d], got {x.dtype} {tuple(x.shape)}")
+    N, d = x.shape
+    B, bs = None, (0, d)
+    if want_stack:
+        if stack_dtype not in (torch.float32, torch.float64):
+            raise ValueError("poly_basis: stack_dtype must be torch.float32 or torch.float64")
+        B = torch.empty(K + 1, N, d, dtype=stack_dtype, device=x.device)
+        bs = (N * d, d)
+    elif g is None:
+        raise ValueError("poly_basis: nothing to compute (want_stack=False and no g)")
+    part = dots = None
+    gs = (0, d)
+    if g is not None:
+        gs = _stack_strides("poly_basis", g, N, d, K, "g")
+        slices = int(lib().sn_poly_filter_launch_shape(N, d, None, None))
+        part = torch.empty(slices, K + 1, dtype=torch.float32, device=x.device)
+        dots = torch.empty(K + 1, dtype=torch.float32, device=x.device)
+    with _span("sn_poly_basis_f32"):
+        check(lib().sn_poly_basis_f32(ptr(x), N, d, K, m, ptr(op.rowptr), ptr(op.col), ptr(op.w), op.nnz, float(diag_add), float(scale),
+                                      ptr(B), bs[0], bs[1], int(B is not None and B.dtype == torch.float64), ptr(g), gs[0], gs[1],
+                                      int(bool(g_reverse)), int(g is not None and g.dtype == torch.float64), ptr(part), stream()),
+              "sn_poly_basis_f32")
+    if part is not None:
+        with _span("sn_train_reduce_parts_f32"):
+            check(lib().sn_train_reduce_parts_f32(ptr(part), part.shape[0], K + 1, K + 1, ptr(dots), 0, stream()), "sn_train_reduce_parts_f32")
+    return dots if B is None else (B if dots is None else (B, dots))
+
+
+def poly_combine(a, op: SparseOperator, K, mode="monomial", diag_add=0.0, scale=1.0, c=None, reverse=False):
+    """y [N, d] = sum_k c[k] P_k(S) a_k in ONE launch (sn_poly_combine_f32; Horner / Clenshaw, K applications of S).  a: [N, d] shared by
+    every k, or a [K+1, N, d] stack (any k / node strides; float32 or float64), read in reverse order with reverse=True.  c: float32 [K+1] on the device, or
+    None for ones."""
+    K, m = _poly_check("poly_combine", op, K, mode, a)
+    require_cuda(c)
+    N, d = op.N, a.shape[-1]
+    sk, ld = _stack_strides("poly_combine", a, N, d, K, "a")
+    if c is not None and (c.dtype != torch.float32 or c.numel() != K + 1 or not c.is_contiguous()):
+        raise ValueError(f"poly_combine: c must be contiguous float32 [{K + 1}]")
+    y = torch.empty(N, d, dtype=torch.float32, device=a.device)
+    with _span("sn_poly_combine_f32"):
+        check(lib().sn_poly_combine_f32(ptr(a), sk, ld, int(bool(reverse)), int(a.dtype == torch.float64), N, d, K, m, ptr(op.rowptr), ptr(op.col), ptr(op.w), op.nnz,
+                                        float(diag_add), float(scale), ptr(c), ptr(y), stream()), "sn_poly_combine_f32")
+    return y
+
+
+_ONES = {}
+
+
+def ones_vector(n, device):
+    """A cached float32 vector of n ones (the unit scale of a bias-only masked_affine)."""
+    key = (int(n), torch.device(device))
+    t = _ONES.get(key)
+    if t is None:
+        t = _ONES[key] = torch.ones(int(n), dtype=torch.float32, device=device)
+    return t
