@@ -68,11 +68,18 @@ __global__ __launch_bounds__(IGN_T) void k_ign_mlp(IgnMlp p) {
     for (int i = 0; i < TPW; ++i) {
       const int row = (wave + NW * i) * 16 + lr;
       valid[i] = row < n;
-      f32x4 in = zero;
-      if (valid[i]) {
-        const float* op = p.o + (mat * n + row) * 5;
-        if (g == 0) in = f32x4{op[0], op[1], op[2], op[3]};
-        else if (g == 1) in = f32x4{op[4], 0.f, 0.f, 0.f};
+      // No branch around these loads: lane (lr, g) reads basis channels min(4 g + t, 4) of its row (an invalid row reads row 0 — n >= 1 —
+      // and is zeroed below) and keeps those below 5.  With `if (valid[i])` / `if (g == 0)` here a wave whose whole tile is invalid jumped
+      // over the block, straight from the previous tile's last MFMA to the first VALU read of its accumulator: the compiler counts that
+      // MFMA's wait states along the fall-through path only, and channels 4 g + 2, 4 g + 3 of the previous tile were read before they were
+      // written (k_ign_mlp<16, 4>, n = 257 .. 384: wrong column means, every output off by up to its own size).
+      const float* op = p.o + (mat * n + (valid[i] ? row : 0)) * 5;
+      f32x4 in;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int k = 4 * g + t;
+        const float v = op[k < 4 ? k : 4];
+        in[t] = k < 5 ? v : 0.f;
       }
 #pragma unroll
       for (int ot = 0; ot < NT; ++ot) {

@@ -2,6 +2,7 @@
 import pytest
 import torch
 
+import basisnet_cases as BC
 import golden_util as G
 import parity_util as PU
 from parity_util import close      # max|hip - ref| <= 1e-5 * max|ref| (north_star); float64 attribution when `ref64` is given
@@ -1072,15 +1073,7 @@ def test_deepsets_tail_kernel_equals_the_layer_path():
             enc.fused_tail = False
             y0 = enc(x)
             # float64 restatement (models.py:58-113)
-            h = x.double().cpu()
-            for i in range(L):
-                l1, l2 = enc.lins1[i], enc.lins2[i]
-                h = h @ l1.weight.double().cpu().t() + l1.bias.double().cpu() + (h.mean(0, keepdim=True) @ l2.weight.double().cpu().t() + l2.bias.double().cpu())
-                if i < L - 1:
-                    h = torch.relu(h)
-                    if use_bn:
-                        bn = enc.bns[i]
-                        h = (h - h.mean(0)) / torch.sqrt(h.var(0, unbiased=False) + bn.eps) * bn.weight.double().cpu() + bn.bias.double().cpu()
+            h = BC.eq_deepsets(x, BC.layers_of(enc), torch.float64, enc.bns[0].eps if use_bn else BC.BN_EPS)
         assert y1.shape == y0.shape == (n, out)
         close(y1.cpu(), h, f"deepsets tail vs float64 n={n}", 2e-5)
         close(y1.cpu(), y0.cpu(), f"deepsets tail vs layer path n={n}", 2e-5)
