@@ -897,6 +897,29 @@ int sn_gnn_fused_f32(const sn_gnn_params* params, const void* x, int ldx, const 
  * flags_host[n_flags] (so flags_host holds n_flags + 1 ints).  A caller that zeroed that word before the launch can poll
  * it from the host: once it reads 1 the flags are there; no event / marker packet on the stream is needed. */
 
+/* Front records: the part of the stage above that depends on the batch and the weights alone — the graph-local CSR of GNN.forward's
+ * edge_index (model.py:47-55), the (layer, class) rows of the edge encoders, the input encoder and the x half of
+ * Linear(cat[x, pos]) (model.py:37-40) — computed per graph by extra workgroups of the one-launch plan, which runs with the device
+ * nearly empty, instead of behind rho in the stage kernel.  Serves d = 128 with one discrete node and one discrete edge feature
+ * column (sn_gnn_front_bytes returns 0 otherwise) and one-launch plans with bins (sn_batch_plan_early_supported).
+ *   sn_gnn_front_bytes      bytes of one graph's record; `front` holds B of them, 16-byte aligned
+ *   sn_batch_plan_front     sn_batch_plan_ex + one workgroup per graph that writes its record.  A graph the record cannot describe
+ *                           (more than 64 nodes or 192 in-edges, an id outside its table, an edge across graphs, an unsorted batch
+ *                           vector) gets valid = 0 and nothing else; no flag is raised here
+ *   sn_gnn_fused_front_f32  sn_gnn_fused_f32 reading the records: a graph with a valid record starts at the slot sum; any other runs
+ *                           the stage's own prologue, flags included.  Same arithmetic in the same order: bit-identical outputs */
+int64_t sn_gnn_front_bytes(const sn_gnn_params* params);
+int sn_batch_plan_front(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index, int64_t E,
+                        int kmax, int32_t* graph_ptr, int32_t* node_graph, int32_t* nvalid, int64_t* evoff,
+                        int32_t* rowptr, int32_t* col, int32_t* eperm, int32_t* status,
+                        const sn_plan_bins* bins, int32_t* scratch, const sn_plan_early* early,
+                        const sn_gnn_params* gnn, const int64_t* x, int ldx, const int64_t* edge_attr, int lde,
+                        void* front, void* stream);
+int sn_gnn_fused_front_f32(const sn_gnn_params* params, const void* x, int ldx, const void* edge_attr, int lde,
+                           const float* rho_sum, const int32_t* graph_ptr, int64_t B, const int32_t* rowptr,
+                           const int32_t* col, const int32_t* eperm, int32_t* status, float* y,
+                           const int32_t* flags_src, int n_flags, int32_t* flags_host, const void* front, void* stream);
+
 /* The DGL tree's GIN base net, eval mode, one launch on the same per-graph stage kernel (GraphPrediction/nets/ZINC_graph_regression/
  * gin_net.py:83-126 with layers/gin_layer.py and layers/mlp.py:37-56, layers/mlp_readout_layer.py):
  *   h = embedding_h[atom] + embedding_p(p);  L x  h = MLP((1 + eps) h_i + sum_{j -> i} h_j);  readout sum / mean;  MLPReadout.

@@ -56,6 +56,9 @@ SIGNATURES = {
     "sn_phi_fused_prec_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p],
     "sn_rho_fused_prec_f32": [_p, _p, _p, _p, _l, _l, _p, _i, _i, _p, _i, _p],
     "sn_gnn_fused_f32": [_p, _p, _i, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p, _p],
+    "sn_gnn_front_bytes": [_p],                          # (int64 byte count: _SPECIAL_RESTYPE)
+    "sn_batch_plan_front": [_p, _l, _l, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p],
+    "sn_gnn_fused_front_f32": [_p, _p, _i, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p],
     "sn_gin_net_fused_f32": [_p, _p, _i, _p, _p, _i, _i, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p],
     "sn_transformer_net_fused_f32": [_p, _p, _i, _p, _p, _i, _i, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p],
     "sn_masked_colstats_f32": [_p, _i, _l, _i, _p, _i, _p, _p, _p, _p, _p],
@@ -139,7 +142,8 @@ SIGNATURES = {
     "sn_poly_basis_f32": [_p, _l, _i, _i, _i, _p, _p, _p, _l, _f, _f, _p, _l, _l, _i, _p, _l, _l, _i, _i, _p, _p],
     "sn_poly_combine_f32": [_p, _l, _l, _i, _i, _l, _i, _i, _i, _p, _p, _p, _l, _f, _f, _p, _p, _p],
 }
-_SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64}
+_SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64,
+                    "sn_gnn_front_bytes": C.c_int64}
 
 _lib = None
 
@@ -183,6 +187,7 @@ def lib():
         L.sn_evd_work_ints.argtypes = [_l]
         L.sn_evd_work_ints.restype = C.c_int64
         L.sn_evd_large_work_ints.restype = _SPECIAL_RESTYPE["sn_evd_large_work_ints"]
+        L.sn_gnn_front_bytes.restype = _SPECIAL_RESTYPE["sn_gnn_front_bytes"]
         L.sn_ign_contract_scratch_floats.argtypes = [_l, _i]
         L.sn_ign_contract_scratch_floats.restype = C.c_int64
         L.sn_train_linear_bwd_part_floats.argtypes = [_l, _i, _i, _i]

@@ -3,7 +3,7 @@
 // the mask construction of SignNet.forward (sign_net.py:100-102) and PyG's per-call COO gather
 // (torch_geometric MessagePassing) — see include/signnet_hip.h.  Everything runs on the device; the host never
 // learns a graph size.
-#include "common.hpp"
+#include "gnn_front.hpp"
 
 namespace sn {
 
@@ -522,9 +522,13 @@ __global__ __launch_bounds__(PLAN_T) void k_plan_small(const int64_t* __restrict
                                                        int32_t* __restrict__ nvalid, int64_t* __restrict__ evoff,
                                                        int32_t* __restrict__ rowptr, int32_t* __restrict__ col,
                                                        int32_t* __restrict__ eperm, int32_t* __restrict__ status, BinsDev bd,
-                                                       int do_bins, EarlyDev early) {
+                                                       int do_bins, EarlyDev early, FrontDev front) {
   extern __shared__ int sm[];
   const int t = threadIdx.x;
+  if (blockIdx.x >= 4) {               // front workgroups (sn_batch_plan_front): one graph's GINE-stage record each — they read the
+    front_block(batch, N, B, ei, E, front, (int)blockIdx.x - 4, sm);      // raw batch only, nothing the workgroups below write
+    return;
+  }
   PL_STAMP(0);
   if (blockIdx.x == 1) {
     if (!do_bins) return;
@@ -539,6 +543,7 @@ __global__ __launch_bounds__(PLAN_T) void k_plan_small(const int64_t* __restrict
     // fourth workgroup (sn_plan_early with feature ids): every discrete feature id against the rows of its embedding tables — what
     // nn.Embedding would raise IndexError for (model_utils/elements.py:21-37); the fused GINE stage never dereferences such an id,
     // this is the same verdict a forward earlier
+    if (early.node_ids == nullptr && early.edge_ids == nullptr) return;    // (launched only as a place holder in front of the front workgroups)
     int bad = 0;
     for (long long i = t; i < early.n_node_ids; i += PLAN_T) bad |= ((unsigned long long)early.node_ids[i] >= (unsigned long long)early.node_vocab) ? 1 : 0;
     for (long long i = t; i < early.n_edge_ids; i += PLAN_T) bad |= ((unsigned long long)early.edge_ids[i] >= (unsigned long long)early.edge_vocab) ? 1 : 0;
@@ -912,11 +917,11 @@ static bool plan_one_launch(int64_t N, int64_t E, int64_t B) { return N > 0 && N
 
 extern "C" int sn_batch_plan_early_supported(int64_t N, int64_t E, int64_t B) { return plan_one_launch(N, E, B) ? 1 : 0; }
 
-extern "C" int sn_batch_plan_ex(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index,
-                                int64_t E, int kmax, int32_t* graph_ptr, int32_t* node_graph,
-                                int32_t* nvalid, int64_t* evoff, int32_t* rowptr, int32_t* col,
-                                int32_t* eperm, int32_t* status, const sn_plan_bins* bins, int32_t* scratch,
-                                const sn_plan_early* early, void* stream) {
+static int plan_impl(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index,
+                     int64_t E, int kmax, int32_t* graph_ptr, int32_t* node_graph,
+                     int32_t* nvalid, int64_t* evoff, int32_t* rowptr, int32_t* col,
+                     int32_t* eperm, int32_t* status, const sn_plan_bins* bins, int32_t* scratch,
+                     const sn_plan_early* early, const FrontDev& fd, void* stream) {
   SN_REQUIRE(N >= 0 && B >= 0 && E >= 0, "sn_batch_plan: negative size");
   SN_REQUIRE(N < (1ll << 31) && E < (1ll << 31), "sn_batch_plan: N/E exceed int32");
   SN_REQUIRE(graph_ptr && node_graph && nvalid && evoff && rowptr && status && scratch,
@@ -958,11 +963,15 @@ extern "C" int sn_batch_plan_ex(const int64_t* batch, int64_t N, int64_t B, cons
       init = true;
     }
     const bool ids = ed.host != nullptr && (ed.node_ids != nullptr || ed.edge_ids != nullptr);
-    hipLaunchKernelGGL(k_plan_small, dim3(do_bins ? (ids ? 4 : 3) : 1), dim3(PLAN_T), lds, st, batch, (int)N, (int)B, edge_index, (int)E,
-                       kmax, graph_ptr, node_graph, nvalid, evoff, rowptr, col, eperm, status, bd, do_bins ? 1 : 0, ed);
+    SN_REQUIRE(fd.rec == nullptr || do_bins, "sn_batch_plan_front: the front workgroups run beside the bin planner (bins must be given)");
+    const unsigned grid = fd.rec != nullptr ? 4u + (unsigned)B : (do_bins ? (ids ? 4u : 3u) : 1u);
+    hipLaunchKernelGGL(k_plan_small, dim3(grid), dim3(PLAN_T), lds, st, batch, (int)N, (int)B, edge_index, (int)E,
+                       kmax, graph_ptr, node_graph, nvalid, evoff, rowptr, col, eperm, status, bd, do_bins ? 1 : 0, ed, fd);
     SN_CHECK_LAUNCH("sn_batch_plan");
     return SN_OK;
   }
+  SN_REQUIRE(fd.rec == nullptr, "sn_batch_plan_front: needs the one-launch plan (N <= %d, E <= %d, B <= %d): ask "
+             "sn_batch_plan_early_supported first", PS_NMAX, PS_EMAX, PS_BMAX);
   int32_t* deg = scratch;  // [N]
   const int T = 256;
   hipLaunchKernelGGL(k_plan_nodes, dim3((unsigned)cdiv(N > 0 ? N : 1, T)), dim3(T), 0, st, batch, N, B, graph_ptr, node_graph, deg,
@@ -988,6 +997,54 @@ extern "C" int sn_batch_plan_ex(const int64_t* batch, int64_t N, int64_t B, cons
   }
   SN_CHECK_LAUNCH("sn_batch_plan");
   return SN_OK;
+}
+
+extern "C" int sn_batch_plan_ex(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index,
+                                int64_t E, int kmax, int32_t* graph_ptr, int32_t* node_graph,
+                                int32_t* nvalid, int64_t* evoff, int32_t* rowptr, int32_t* col,
+                                int32_t* eperm, int32_t* status, const sn_plan_bins* bins, int32_t* scratch,
+                                const sn_plan_early* early, void* stream) {
+  return plan_impl(batch, N, B, edge_index, E, kmax, graph_ptr, node_graph, nvalid, evoff, rowptr, col, eperm, status, bins, scratch,
+                   early, FrontDev{}, stream);
+}
+
+static bool front_supported(const sn_gnn_params& P) {
+  return P.d == FR_D && P.node_discrete == 1 && P.node_nf == 1 && P.edge_discrete == 1 && P.edge_nf == 1 && P.n_layers >= 1 &&
+         P.n_layers <= SN_GNN_MAX_LAYERS && P.node_vocab > 0 && P.edge_vocab > 0 && P.ntab[0] != nullptr && P.lin_a != nullptr;
+}
+
+extern "C" int64_t sn_gnn_front_bytes(const sn_gnn_params* params) {
+  if (params == nullptr || !front_supported(*params)) return 0;
+  return front_stride(front_ee_cap(*params));
+}
+
+extern "C" int sn_batch_plan_front(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index,
+                                   int64_t E, int kmax, int32_t* graph_ptr, int32_t* node_graph,
+                                   int32_t* nvalid, int64_t* evoff, int32_t* rowptr, int32_t* col,
+                                   int32_t* eperm, int32_t* status, const sn_plan_bins* bins, int32_t* scratch,
+                                   const sn_plan_early* early, const sn_gnn_params* gnn, const int64_t* x, int ldx,
+                                   const int64_t* edge_attr, int lde, void* front, void* stream) {
+  SN_REQUIRE(gnn && front, "sn_batch_plan_front: null pointer");
+  const sn_gnn_params& P = *gnn;
+  SN_REQUIRE(front_supported(P), "sn_batch_plan_front: the front record serves d = 128 with one discrete node and one discrete edge "
+             "feature column (sn_gnn_front_bytes returns 0 otherwise)");
+  SN_REQUIRE((reinterpret_cast<uintptr_t>(front) & 15) == 0, "sn_batch_plan_front: the record buffer must be 16-byte aligned");
+  SN_REQUIRE(N == 0 || (x && ldx >= 1), "sn_batch_plan_front: node ids missing");
+  SN_REQUIRE(E == 0 || (edge_attr && lde >= 1), "sn_batch_plan_front: edge ids missing");
+  FrontDev fd{};
+  fd.x = x; fd.ldx = ldx; fd.edge_attr = edge_attr; fd.lde = lde;
+  fd.ntab = P.ntab[0]; fd.node_vocab = P.node_vocab; fd.edge_vocab = P.edge_vocab; fd.n_layers = P.n_layers;
+  fd.lin_a = P.lin_a;
+  for (int l = 0; l < P.n_layers; ++l) {
+    SN_REQUIRE(P.layers[l].etab[0], "sn_batch_plan_front: layer %d edge table missing", l);
+    fd.etab[l] = P.layers[l].etab[0];
+  }
+  fd.ee_rows = gnn_ee_rows(8, 1);
+  fd.ee_cap = front_ee_cap(P);
+  fd.rec = B > 0 ? reinterpret_cast<unsigned char*>(front) : nullptr;
+  fd.stride = front_stride(fd.ee_cap);
+  return plan_impl(batch, N, B, edge_index, E, kmax, graph_ptr, node_graph, nvalid, evoff, rowptr, col, eperm, status, bins, scratch,
+                   early, fd, stream);
 }
 
 extern "C" int sn_batch_plan(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index,

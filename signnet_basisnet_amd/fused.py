@@ -311,10 +311,30 @@ class GnnPlan:
             Lp.w2s = hold(ops.pack_split(conv.nn.layers[1].weight.detach(), s, h))
             Lp.eps = hold(conv.layer.eps.detach())
         self.params = P
+        self._front_bytes = None
+
+    def front_args(self, x, edge_attr):
+        """What ops.build_plan(front=...) needs to have the plan launch write this stage's front records, or None when the stage
+        cannot use them (width other than 128, float features, several feature columns)."""
+        if not (self.node_discrete and self.edge_discrete and x.dtype == torch.int64 and edge_attr.dtype == torch.int64):
+            return None
+        N = x.shape[0] if x.dim() else 0
+        x2 = x.reshape(N, -1)
+        E = edge_attr.shape[0] if edge_attr.dim() else 0
+        e2 = edge_attr.reshape(E, -1) if E else edge_attr.reshape(0, 1)
+        if N == 0 or x2.shape[1] != 1 or (E and e2.shape[1] != 1) or not x2.is_cuda:
+            return None
+        self.params.node_nf = self.params.edge_nf = 1      # (the column counts are set per call: see run)
+        if self._front_bytes is None:
+            self._front_bytes = int(lib().sn_gnn_front_bytes(C.byref(self.params)))
+        if not self._front_bytes:
+            return None
+        return (self.params, x2.contiguous(), e2.contiguous(), self._front_bytes)
 
     def run(self, plan: ops.GraphPlan, x, edge_attr, rho_sum, flags_host=None):
         """-> model output [B, n_out] (graphs with more than 64 nodes set plan.status[3]).  flags_host: optional pinned
-        int32 host tensor (>= plan.flags.numel()) that the kernel's last workgroup fills with plan.flags."""
+        int32 host tensor (>= plan.flags.numel()) that the kernel's last workgroup fills with plan.flags.  A plan built with this
+        stage's front records (plan.front) runs the entry point that starts from them."""
         P = self.params
         if self.node_discrete:
             if x.dtype != torch.int64:
@@ -337,6 +357,15 @@ class GnnPlan:
         if P.node_nf > (10 if self.node_discrete else 16) or P.edge_nf > (10 if self.edge_discrete else 16):
             raise ValueError("too many feature columns for the fused gnn kernel")
         y = torch.empty(plan.B, self.n_out, dtype=torch.float32, device=rho_sum.device)
+        if plan.front is not None and P.node_nf == 1 and P.edge_nf == 1:
+            with ops._span("sn_gnn_fused_f32"):
+                check(lib().sn_gnn_fused_front_f32(C.byref(P), ptr(x), x.shape[1], ptr(edge_attr),
+                                                   edge_attr.shape[1] if edge_attr.dim() > 1 else 1, ptr(rho_sum),
+                                                   ptr(plan.graph_ptr), plan.B, ptr(plan.rowptr), ptr(plan.col),
+                                                   ptr(plan.eperm), ptr(plan.status), ptr(y),
+                                                   ptr(plan.flags), plan.flags.numel(), ptr(flags_host), ptr(plan.front), stream()),
+                      "sn_gnn_fused_front_f32")
+            return y
         with ops._span("sn_gnn_fused_f32"):
             check(lib().sn_gnn_fused_f32(C.byref(P), ptr(x), x.shape[1], ptr(edge_attr),
                                          edge_attr.shape[1] if edge_attr.dim() > 1 else 1, ptr(rho_sum),

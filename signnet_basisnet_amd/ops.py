@@ -131,6 +131,7 @@ class GraphPlan:
                               #              embedding index out of range (layer path), -, -]
     bins: PlanBins | None
     flags: torch.Tensor = None   # status (+ bins meta) as one contiguous block
+    front: torch.Tensor = None   # int32 view of the batch's GINE-stage front records (sn_batch_plan_front), or None
 
     def check(self):
         """Synchronising validity check (raises on malformed batches)."""
@@ -216,12 +217,14 @@ def early_supported(N: int, E: int, B: int) -> bool:
 
 
 def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, kmax: int = 0, bins: bool = False,
-               early: "EarlyReport | None" = None, columns: bool = False, counts: torch.Tensor = None) -> GraphPlan:
+               early: "EarlyReport | None" = None, columns: bool = False, counts: torch.Tensor = None, front=None) -> GraphPlan:
     """bins=True also lays out the work bins of the fused stages (same launch, no host sync).  early: an armed EarlyReport — the
     batch's flags are also written to its pinned buffer by the plan kernel itself (one-launch plans only: early_supported()).
     columns=True: the planner's column arrays (phi_bin_col, phi_col_bin0, phi_col_mem, phi_col_off) are written too — the stage kernels
     walk the per-bin member records (phi_bin_mem) only, so the forward leaves them out.
-    counts: the device count block of a padded batch (sn_bucket_pack): graphs >= counts[2] get no eigenvector slot (sn_batch_plan_padded)."""
+    counts: the device count block of a padded batch (sn_bucket_pack): graphs >= counts[2] get no eigenvector slot (sn_batch_plan_padded).
+    front: (sn_gnn_params, x [N, F] int64, edge_attr [E, F_e] int64, bytes per record) of the fused GINE stage that will consume this
+    plan (fused.GnnPlan.front_args): the launch also writes the stage's front records (plan.front); needs bins and a one-launch plan."""
     require_cuda(batch, edge_index)
     if batch.dtype != torch.int64 or edge_index.dtype != torch.int64:
         raise ValueError("build_plan: batch and edge_index must be int64 (the reference's index dtype)")
@@ -235,6 +238,11 @@ def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, k
     if bins:
         mb = int(lib().sn_phi_bins_bound(B, int(kmax)))
         sizes += [8, mb if columns else 0, (B + 1) if columns else 0, (8 * B) if columns else 0, (8 * B) if columns else 0, B + 1, 16 * mb]
+    if front is not None:
+        if not bins or counts is not None or not early_supported(N, E, B) or B == 0:
+            front = None
+        else:
+            sizes += [B * (int(front[3]) // 4)]
     offs = [0]
     for s in sizes:
         offs.append(offs[-1] + ((s + 3) // 4) * 4)
@@ -259,6 +267,14 @@ def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, k
                                              C.byref(pb.cstruct) if pb is not None else None, ptr(scratch),
                                              C.byref(early.cstruct) if early is not None else None, ptr(counts), stream()),
                   "sn_batch_plan_padded")
+    elif front is not None:
+        gp, fx, fe, _ = front
+        with _span("sn_batch_plan"):
+            check(lib().sn_batch_plan_front(ptr(batch), N, B, ptr(edge_index), E, int(kmax), ptr(graph_ptr), ptr(node_graph),
+                                            ptr(nvalid), ptr(evoff), ptr(rowptr), ptr(col), ptr(eperm), ptr(status),
+                                            C.byref(pb.cstruct), ptr(scratch), C.byref(early.cstruct) if early is not None else None,
+                                            C.byref(gp), ptr(fx), fx.shape[1], ptr(fe), fe.shape[1], ptr(parts[-1]), stream()),
+                  "sn_batch_plan_front")
     else:
         with _span("sn_batch_plan"):
             check(lib().sn_batch_plan_ex(ptr(batch), N, B, ptr(edge_index), E, int(kmax), ptr(graph_ptr), ptr(node_graph),
@@ -267,6 +283,8 @@ def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, k
                                          C.byref(early.cstruct) if early is not None else None, stream()), "sn_batch_plan")
     plan = GraphPlan(N, B, E, int(kmax), graph_ptr, node_graph, nvalid, evoff, rowptr, col, eperm, status, pb)
     plan.flags = arena[offs[7]:offs[7] + 16] if bins else status      # [status(8) | meta(8)] contiguous
+    if front is not None:
+        plan.front = parts[-1]
     return plan
 
 

@@ -23,6 +23,7 @@ from . import fused, ops
 import os as _os
 MAX_FUSED_GRAPHS = 6144      # sn_batch_plan's work-bin limit per call
 _NO_KERNEL_FLAGS = bool(_os.environ.get("SN_NO_KERNEL_FLAGS"))   # debugging: report flags with a stream copy instead
+_USE_FRONT = not _os.environ.get("SN_NO_GNN_FRONT")              # debugging: the GINE stage runs its own prologue for every graph
 N_HEAD = 4          # TransformerEncoderLayer(nhid, n_head=4): sign_net.py:50 / core/sign_net.py:57
 LN_EPS = 1e-6       # masked_layers.py:25
 
@@ -1079,7 +1080,10 @@ class SignNetGNN(nn.Module):
         K_host = None if self.max_k else host_max_nodes(data)
         if not self.max_k and K_host is None and early is None and not return_stages and not capturing and ops.early_supported(N_, E_n, B):
             early = ops.EarlyReport().arm()          # only for the largest graph: a poll of pinned memory instead of a device read-back
-        plan = ops.build_plan(data.batch, data.edge_index, B, self.max_k or 0, bins=use_phi_fused or use_rho_fused, early=early)
+        # the fused eval forward: the plan launch also writes the GINE stage's front records (what its prologue needs of the batch alone)
+        front = P["gnn_fused"].front_args(data.x, data.edge_attr) if (all_fused and _USE_FRONT) else None
+        plan = ops.build_plan(data.batch, data.edge_index, B, self.max_k or 0, bins=use_phi_fused or use_rho_fused, early=early,
+                              front=front)
         self._last_plan, self._used_fused = plan, (use_phi_fused or use_rho_fused or use_gnn_fused)
         if self.max_k:
             K = int(self.max_k)
