@@ -1180,6 +1180,40 @@ int sn_poly_combine_f32(const void* a, int64_t a_sk, int64_t a_ld, int a_reverse
                         const int32_t* rowptr, const int32_t* col, const float* w, int64_t nnz, float diag_add, float scale,
                         const float* c, float* y, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The two operations of the 'gcn' and 'transformer' sign-invariant encoders of the DGL tree (GraphPrediction/layers/deepsigns.py:13-31
+ * GCNDeepSigns over layers/gnns.py:15-45 GCN; deepsigns.py:89-119 TransformerDeepSigns), restated from DGL's published definitions
+ * (DGL is not pinned by the reference).
+ *
+ * sn_gcn_propagate_f32: dgl.nn.pytorch.GraphConv(norm='both') without its weight (gnns.py:23-29,44):
+ *     out[i, c] = cin[i] * sum_{e in in(i)} cout[col[e]] * x[col[e], c]  (+ bias[c % width])
+ *     cin[i] = max(rowptr[i+1] - rowptr[i], 1)^-1/2,  cout[j] = max(rowptr_t[j+1] - rowptr_t[j], 1)^-1/2
+ *   over the destination-sorted CSR of sn_batch_plan (rowptr, col: in-edges in edge-id order; multi-edges add, self loops count) with
+ *   rowptr_t the rowptr of the plan of the FLIPPED edge list (out-degrees).  x, out: [N, C] with row strides ldx, ldo >= C,
+ *   C = slots * channels floats per node (deepsigns.py:26 runs the encoder on [N, K, c]); bias (may be NULL): [width], width | C.
+ *   A node without in-edges gets the bias (DGL itself raises for such a graph: the modules check).  One owner per output element, no
+ *   atomics, sums in edge order: bit-reproducible.  16-byte vector accesses when C, ldx, ldo (and width) are multiples of 4 and the
+ *   pointers 16-byte aligned, scalar ones otherwise.  The adjoint w.r.t. x is the same entry point on the flipped plan:
+ *   sn_gcn_propagate_f32(dout, ..., rowptr_t, col_t, rowptr, NULL, 0, dx, ...).
+ *
+ * sn_graph_attention_f32 / sn_graph_attention_bwd_f32: the multi-head self-attention of dgl.nn.pytorch.glob.SetTransformerEncoder's
+ *   SetAttentionBlock over the nodes of each graph (deepsigns.py:101,113: one encoder call per eigenvector slot and sign — here every
+ *   graph, slot, sign and head of a layer in ONE launch).  A set is (graph b, slot s), its members the rows node * S + s for
+ *   graph_ptr[b] <= node < graph_ptr[b+1] (clamped to [0, N)); q, k, v: [N*S, heads*dh] blocks with the common row stride ld (column
+ *   blocks of one projection); out: [N*S, heads*dh], row stride ldo; lse: [N*S, heads] contiguous.
+ *     out[i, h, :] = sum_j softmax_j(q_i . k_j / sqrt(dh)) v_j over the members j of i's set;  lse = the row's log-sum-exp.
+ *   A set of up to 64 nodes is staged in LDS once, a larger one walked in tiles of 64 with an online softmax; an empty graph does
+ *   nothing; a one-node set returns its v row.  The backward recomputes the probabilities from lse and writes dq per query and dk, dv
+ *   per key ([N*S, heads*dh] blocks with the common row stride ldg), sums in node order, no atomics: bit-reproducible.  delta:
+ *   scratch [N*S, heads] (dout . out).  Any dh <= 64; dh > 64 returns SN_ERR_UNSUPPORTED before anything is launched. */
+int sn_gcn_propagate_f32(const float* x, int64_t ldx, int64_t N, int C, const int32_t* rowptr, const int32_t* col,
+                         const int32_t* rowptr_t, const float* bias, int width, float* out, int64_t ldo, void* stream);
+int sn_graph_attention_f32(const float* q, const float* k, const float* v, int64_t ld, const int32_t* graph_ptr, int64_t N, int64_t B,
+                           int S, int heads, int dh, float* out, int64_t ldo, float* lse, void* stream);
+int sn_graph_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld, const float* out, int64_t ldo,
+                               const float* lse, const float* dout, int64_t lddo, const int32_t* graph_ptr, int64_t N, int64_t B,
+                               int S, int heads, int dh, float* dq, float* dk, float* dv, int64_t ldg, float* delta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,9 @@ SIGNATURES = {
     "sn_poly_filter_launch_shape": [_l, _i, C.POINTER(_i), C.POINTER(_l)],   # (returns the workgroup count, not a status)
     "sn_poly_basis_f32": [_p, _l, _i, _i, _i, _p, _p, _p, _l, _f, _f, _p, _l, _l, _i, _p, _l, _l, _i, _i, _p, _p],
     "sn_poly_combine_f32": [_p, _l, _l, _i, _i, _l, _i, _i, _i, _p, _p, _p, _l, _f, _f, _p, _p, _p],
+    "sn_gcn_propagate_f32": [_p, _l, _l, _i, _p, _p, _p, _p, _i, _p, _l, _p],
+    "sn_graph_attention_f32": [_p, _p, _p, _l, _p, _l, _l, _i, _i, _i, _p, _l, _p, _p],
+    "sn_graph_attention_bwd_f32": [_p, _p, _p, _l, _p, _l, _p, _p, _l, _p, _l, _l, _i, _i, _i, _p, _p, _p, _l, _p, _p],
 }
 _SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64,
                     "sn_gnn_front_bytes": C.c_int64}

@@ -905,3 +905,53 @@ class _LinearIO(Function):
 
 def linear_io(x, W, b=None, relu=False):
     return _LinearIO.apply(x, W, b, relu)
+
+
+# ----------------------------------------------------------------------------- the 'gcn' / 'transformer' sign-invariant encoders (csrc/deepsigns_variants.hip)
+class _GcnPropagate(Function):
+    """ops.gcn_propagate; dx is the same launch on the flipped plan with the two degree vectors swapped, d bias the column sums of the
+    upstream gradient viewed as rows of `width` channels (rows added in order: reproducible)."""
+
+    @staticmethod
+    def forward(ctx, x, bias, plan, rplan, width):
+        ctx.meta = (plan, rplan, width)
+        return ops.gcn_propagate(x.detach(), plan, rplan, None if bias is None else _c(bias.detach()), width)
+
+    @staticmethod
+    def backward(ctx, g):
+        plan, rplan, width = ctx.meta
+        g = _c(g)
+        dx = ops.gcn_propagate(g, rplan, plan) if ctx.needs_input_grad[0] else None
+        db = _column_sums(g.view(-1, width)) if ctx.needs_input_grad[1] else None
+        return dx, db, None, None, None
+
+
+def gcn_propagate(x, plan, rplan, bias=None, width=0):
+    """cin[i] * sum_{j -> i} cout[j] * x[j] (+ bias per channel) over the node axis of x [N, slots * width]."""
+    return _GcnPropagate.apply(x, bias, plan, rplan, width)
+
+
+class _GraphAttention(Function):
+    """ops.graph_attention on the packed projection qkv [N*S, 3 * heads*dh] (column blocks q | k | v); the backward recomputes the
+    probabilities from the saved log-sum-exp and returns the gradient of the whole projection as one tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, graph_ptr, N, S, heads):
+        qkv = _c(qkv.detach())
+        D = qkv.shape[1] // 3
+        out, lse = ops.graph_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], graph_ptr, N, S, heads)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.meta = (graph_ptr, N, S, heads)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, out, lse = ctx.saved_tensors
+        graph_ptr, N, S, heads = ctx.meta
+        D = qkv.shape[1] // 3
+        return ops.graph_attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], out, lse, _c(g), graph_ptr, N, S, heads), None, None, None, None
+
+
+def graph_attention(qkv, graph_ptr, N, S, heads):
+    """softmax(q k^T / sqrt(dh)) v per head over the nodes of each graph, independently per slot (rows node * S + slot)."""
+    return _GraphAttention.apply(qkv, graph_ptr, N, S, heads)

@@ -1,14 +1,22 @@
 """DGL-tree sign-invariant networks (drop-in `nn.Module` surface, HIP forward).
 
-Mirrors GraphPrediction/layers/deepsigns.py:33-86 (GINDeepSigns, MaskedGINDeepSigns), layers/gnns.py:81-114 (GIN),
-layers/mlp.py:5-56 (MLP) and the factory nets/ZINC_graph_regression/sign_inv_net.py:3-17 — same constructor
-arguments, same `forward(g, x[N,K,1]) -> [N,K,1]`, same state_dict keys (`enc.layers.{l}.apply_func.lins.{i}.*`,
-`enc.layers.{l}.eps`, `enc.bns.{l}.*`, `rho.lins.{i}.*`, `rho.bns.{i}.*`).
+Mirrors GraphPrediction/layers/deepsigns.py:13-119 (GCNDeepSigns, GINDeepSigns, MaskedGINDeepSigns, TransformerDeepSigns),
+layers/gnns.py:15-45 (GCN) and :81-114 (GIN), layers/mlp.py:5-56 (MLP) and the factory
+nets/ZINC_graph_regression/sign_inv_net.py:3-17 — same constructor arguments, same `forward(g, x[N,K,1]) -> [N,K,1]`, same
+state_dict keys (GIN: `enc.layers.{l}.apply_func.lins.{i}.*`, `enc.layers.{l}.eps`, `enc.bns.{l}.*`; GCN: `enc.layers.{l}.weight`,
+`enc.layers.{l}.bias`, `enc.bns.{l}.*`; Transformer: `embed.*`, `enc.layers.{l}.mha.proj_{q,k,v,o}.weight`,
+`enc.layers.{l}.mha.ffn.{0,3}.*`, `enc.layers.{l}.mha.norm_{in,inter}.*`; all: `rho.lins.{i}.*`, `rho.bns.{i}.*`).  DGL's own layers
+(GINConv, GraphConv, SetTransformerEncoder) are restated from their published definitions: the reference does not pin a DGL version.
 
 `g` is duck-typed: anything with `.edges() -> (src, dst)` int64 tensors and `.batch_num_nodes()` (a DGL batched
 graph, or `signnet_basisnet_amd.dgl_deepsigns.Graph`).  Eval mode (BatchNorm with running statistics) runs
-entirely in the HIP kernels of libsignnet_hip.so; there is no CPU path.  Train mode gives the forward VALUE with
-batch-statistic BatchNorm (and updates the running statistics); there is no autograd.
+entirely in the HIP kernels of libsignnet_hip.so; there is no CPU path.  Train mode without autograd gives the forward VALUE with
+batch-statistic BatchNorm (and updates the running statistics); under autograd `_forward_grad` records the same launches as
+torch.autograd.Function nodes whose backward are the hand-written adjoints.
+
+The GIN encoders have one-launch stage kernels (`fused_stages`, `matmul_precision`, `overlap`); the GCN and Transformer encoders run
+layer by layer — one sn_gcn_propagate_f32 / sn_graph_attention_f32 launch per layer for both signs and every slot, everything else
+on the layer-path ops — and offer neither switch (`matmul_precision` accepts "highest" only).
 """
 from __future__ import annotations
 
@@ -600,15 +608,398 @@ class MaskedGINDeepSigns(_DeepSignsBase):
         self._prep = None
 
 
+# ----------------------------------------------------------------------------- the 'gcn' and 'transformer' encoders
+def _cached_rplan(g, N):
+    """The plan of the FLIPPED edge list (rows = source nodes: the out-degrees of GraphConv's norm, the CSR of the aggregation's adjoint),
+    kept on the graph object next to its plans and dropped with them (serving.GraphedDGLForward resets `_sn_plans` inside the recorded
+    step: the flipped plan is then rebuilt there too).  Call after cached_plan(g, N)."""
+    cache = getattr(g, "_sn_plans", None)
+    held = getattr(g, "_sn_rplan", None)
+    if held is not None and held[0] is cache:
+        return held[1]
+    src, dst = g.edges()
+    rg = Graph(dst, src, g.batch_num_nodes())
+    rg._sn_node_counts = _node_counts(g)           # (the same batch: its node counts are not read back a second time)
+    rplan = cached_plan(rg, N)
+    try:
+        g._sn_rplan = (cache, rplan)
+    except Exception:
+        pass
+    return rplan
+
+
+class _GraphConv(nn.Module):
+    """dgl.nn.pytorch.GraphConv(in_feats, out_feats, norm='both', weight=True, bias=True, activation=...), restated from DGL's published
+    definition (DGL is not pinned by the reference): parameters `weight` [in, out] (Glorot uniform) and `bias` [out] (zeros);
+    rst = D_in^-1/2 A D_out^-1/2 h W + bias with degrees clamped to 1, the weight applied BEFORE the aggregation when in > out; a node
+    without in-edges raises (allow_zero_in_degree=False)."""
+
+    def __init__(self, in_feats, out_feats, activation=None):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
+        self.bias = nn.Parameter(torch.zeros(out_feats))
+        nn.init.xavier_uniform_(self.weight)
+        self.relu = activation is not None
+
+
+class GCN(nn.Module):
+    """layers/gnns.py:15-45: GraphConv(in, hidden, act), n_layers - 2 x GraphConv(hidden, hidden, act), GraphConv(hidden, out); before every
+    layer i >= 1 the BatchNorm1d bns[i-1] over all N*K rows.  Parameters only: GCNDeepSigns runs it."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, n_layers, use_bn=True, dropout=0.5, activation="relu"):
+        super().__init__()
+        if activation != "relu":
+            raise ValueError("HIP path: only relu (what every shipped config uses)")
+        self.layers = nn.ModuleList()
+        if use_bn:
+            self.bns = nn.ModuleList()
+        self.use_bn = use_bn
+        self.layers.append(_GraphConv(in_channels, hidden_channels, activation))
+        for _ in range(n_layers - 2):
+            self.layers.append(_GraphConv(hidden_channels, hidden_channels, activation))
+            if use_bn:
+                self.bns.append(nn.BatchNorm1d(hidden_channels))
+        self.layers.append(_GraphConv(hidden_channels, out_channels))
+        if use_bn:
+            self.bns.append(nn.BatchNorm1d(hidden_channels))
+
+
+class _MultiHeadAttention(nn.Module):
+    """dgl.nn.pytorch.glob.MultiHeadAttention (the `mha` of a SetAttentionBlock), restated from DGL's published definition: bias-free
+    q / k / v / o projections, a two-layer ReLU feed-forward net (indices 0 and 3 of the Sequential; 1 and 2 are ReLU and Dropout) and two
+    LayerNorms (eps 1e-5); every parameter with more than one dimension Glorot uniform."""
+
+    def __init__(self, d_model, num_heads, d_head, d_ff):
+        super().__init__()
+        self.d_model, self.num_heads, self.d_head, self.d_ff = d_model, num_heads, d_head, d_ff
+        self.proj_q = nn.Linear(d_model, num_heads * d_head, bias=False)
+        self.proj_k = nn.Linear(d_model, num_heads * d_head, bias=False)
+        self.proj_v = nn.Linear(d_model, num_heads * d_head, bias=False)
+        self.proj_o = nn.Linear(num_heads * d_head, d_model, bias=False)
+        self.ffn = nn.Sequential(nn.Linear(d_model, d_ff), nn.ReLU(), nn.Dropout(0.0), nn.Linear(d_ff, d_model))
+        self.norm_in = nn.LayerNorm(d_model)
+        self.norm_inter = nn.LayerNorm(d_model)
+        for p in self.parameters():
+            if p.dim() > 1:
+                nn.init.xavier_uniform_(p)
+
+
+class _SetAttentionBlock(nn.Module):
+    def __init__(self, d_model, num_heads, d_head, d_ff):
+        super().__init__()
+        self.mha = _MultiHeadAttention(d_model, num_heads, d_head, d_ff)
+
+
+class SetTransformerEncoder(nn.Module):
+    """dgl.nn.pytorch.glob.SetTransformerEncoder(d_model, n_heads, d_head, d_ff, n_layers, block_type='sab', dropouth=0, dropouta=0):
+    n_layers SetAttentionBlocks — x = norm_in(x + proj_o(attention over the nodes of the row's graph)), x = norm_inter(x + ffn(x)).
+    Parameters only: TransformerDeepSigns runs it."""
+
+    def __init__(self, d_model, n_heads, d_head, d_ff, n_layers=1):
+        super().__init__()
+        self.layers = nn.ModuleList([_SetAttentionBlock(d_model, n_heads, d_head, d_ff) for _ in range(n_layers)])
+
+
+class _SignInvBase(nn.Module):
+    """What the sign-invariant nets WITHOUT stage kernels share (nothing here looks into `enc`): the forward contract, the three forward
+    paths (eval / train value / train under autograd), and the cache invalidation of _DeepSignsBase."""
+
+    def __init__(self):
+        super().__init__()
+        self.register_load_state_dict_post_hook(lambda m, keys=None: m._invalidate())
+        self._prep = None
+
+    @property
+    def matmul_precision(self):
+        """"highest" only: these encoders have no stage kernels, every Linear is the fp32 layer-path GEMM.  Assigning "high" or "medium"
+        raises ValueError — a mode is never replaced by another."""
+        return "highest"
+
+    @matmul_precision.setter
+    def matmul_precision(self, name):
+        if name != "highest":
+            raise ValueError(f"{type(self).__name__}: matmul_precision {name!r} is not built for this encoder (it has no stage kernels); "
+                             "only 'highest'")
+
+    def _invalidate(self):
+        self._prep = None
+
+    def train(self, mode=True):
+        self._invalidate()
+        return super().train(mode)
+
+    def _apply(self, fn, *a, **k):
+        self._invalidate()
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self._invalidate()
+        return super().load_state_dict(*a, **k)
+
+    def _neg(self, x2):
+        """-x of a row matrix (one launch; the constants are kept with the prepared parameters' device)."""
+        c = getattr(self, "_neg1", None)
+        if c is None or c[0].device != x2.device:
+            c = self._neg1 = (torch.full((1,), -1.0, device=x2.device), torch.zeros(1, device=x2.device))
+        return ops.masked_affine(x2, scale=c[0], shift=c[1])
+
+    def _grad_plans(self, g, N):
+        """(plan, plan of the flipped edge list), built per call: under train_graph.DGLBucketedStep the graph object is a static buffer
+        whose contents change between replays, so nothing is cached on it."""
+        src, dst = g.edges()
+        bnn = g.batch_num_nodes().to(src.device)
+        B = int(bnn.numel())
+        if _node_counts(g)[1] != N:
+            raise ValueError(ops.NODE_COUNT_ERROR)
+        batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N).long()      # index plumbing only
+        ei = torch.stack([src.long(), dst.long()])
+        return ops.build_plan(batch, ei, B, 0), ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
+
+    def _rho_grad(self, z):
+        """rho under autograd (mlp.py:37-56, dropout 0): padded rows of a bucketed batch enter no statistic and no gradient."""
+        from . import autograd as AG
+        vN, _, _, k1 = _bucket_rows(self)
+        mlp, n = self.rho, len(self.rho.lins)
+        for i, lin in enumerate(mlp.lins):
+            z = AG.linear(z, lin.weight, lin.bias, vN, k1, relu=i < n - 1)
+            if mlp.use_bn and i < n - 1:
+                z = AG.bn_act(z, mlp.bns[i], vN, k1, relu=False)
+        return z
+
+    def forward(self, g, x):
+        train = self.training     # train: batch statistics + running-statistics update (dropout 0)
+        ops.require_cuda(x)
+        if x.dim() != 3 or x.shape[1] != self.k or x.shape[2] != 1:
+            raise ValueError(f"expected x of shape [N, {self.k}, 1]")
+        x = x.contiguous().float()
+        if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._forward_grad(g, x)
+        if train:
+            P = self._prepare(True)          # parameters may change between training-mode calls: nothing is cached
+        else:
+            if self._prep is None:
+                self._prep = self._prepare(False)
+            P = self._prep
+        return self._forward_value(P, g, x, train)
+
+
+_ZERO_IN_DEGREE = ("There are 0-in-degree nodes in the graph: GraphConv's normalised sum is undefined for them (DGL raises DGLError here "
+                   "unless allow_zero_in_degree is set, which layers/gnns.py:23-29 leaves at False)")
+
+
+class GCNDeepSigns(_SignInvBase):
+    """layers/deepsigns.py:13-31: rho(enc(g, x) + enc(g, -x)) with enc = GCN (layers/gnns.py:15-45) over [N, k, c] features and
+    rho = MLP(out * k, hidden, k, num_layers).  state_dict keys `enc.layers.{l}.weight` / `.bias`, `enc.bns.{l}.*`, `rho.lins.{i}.*`,
+    `rho.bns.{i}.*`.  The propagation D_in^-1/2 A D_out^-1/2 h is ONE launch per layer (sn_gcn_propagate_f32; eval: both signs in the
+    slot axis); weight, bias, ReLU and the eval BatchNorm in front of the next layer are the layer-path GEMM and its epilogue (the weight
+    runs first where in > out, as in GraphConv; its bias then rides in the propagation).  A node without in-edges raises ValueError."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, k, use_bn=False, use_ln=False, dropout=0.5,
+                 activation="relu"):
+        super().__init__()
+        _no_dropout(dropout, "GCNDeepSigns")
+        if use_ln:
+            raise ValueError("HIP path: only relu / no LayerNorm / no residual (what every shipped config uses)")
+        self.enc = GCN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.k = k
+
+    def _prepare(self, train=False):
+        enc, L = self.enc, len(self.enc.layers)
+        layers = []
+        for l, conv in enumerate(enc.layers):
+            W = conv.weight.detach()
+            d_in, d_out = W.shape
+            first = d_in > d_out                          # GraphConv: the weight in front of the aggregation
+            b = conv.bias.detach().contiguous()
+            pl = ops.PackedLinear(ops.pack_weight_t(W), d_out, d_in, None if first else b)         # weight [in, out] = Linear weight^T
+            nxt = _BNSite(enc.bns[l], train) if (enc.use_bn and l < L - 1) else None               # applied before layer l + 1 (gnns.py:37-43)
+            layers.append(dict(pl=pl, first=first, bias=b, width=d_out, relu=conv.relu, next_bn=nxt))
+        return dict(layers=layers, rho=_prep_mlp(self.rho, train))
+
+    def _zero_in_degree(self, plan, valid=None):
+        """As dgl_nets.GATNet: checked at once eagerly, handed to the collector of ops.defer_status() in a recorded step; in a padded
+        batch only valid nodes count (the padding self-loops may not reach every padding node)."""
+        z = plan.rowptr[1:] == plan.rowptr[:-1]
+        zero = (z if valid is None else z & (valid != 0)).any()
+        if ops.deferring():
+            ops.defer("plan", plan)
+            ops.defer("flag", zero, _ZERO_IN_DEGREE)
+        elif bool(zero):
+            raise ValueError(_ZERO_IN_DEGREE)
+
+    def _enc_value(self, P, plan, rplan, h, N, S, train):
+        """GCN.forward on [N, S, c] features held as rows node * S + slot (eval: folded BatchNorm in the GEMM epilogue)."""
+        for Lp in P["layers"]:
+            site = Lp["next_bn"]
+            if Lp["first"]:
+                z = ops.masked_linear(h, Lp["pl"])
+                h = ops.gcn_propagate(z.view(N, -1), plan, rplan, Lp["bias"], Lp["width"]).view(N * S, -1)
+                if train:
+                    if Lp["relu"]:
+                        h = ops.masked_affine(h, relu=True)
+                    if site is not None:
+                        sc, sh = site.affine(h, True)
+                        h = ops.masked_affine(h, scale=sc, shift=sh)
+                elif Lp["relu"] or site is not None:
+                    sc, sh = (None, None) if site is None else (site.scale, site.shift)
+                    h = ops.masked_affine(h, relu_pre=Lp["relu"], scale=sc, shift=sh)
+                continue
+            a = ops.gcn_propagate(h.view(N, -1), plan, rplan).view(N * S, -1)
+            if not train:
+                sc, sh = (None, None) if site is None else (site.scale, site.shift)
+                h = ops.masked_linear(a, Lp["pl"], relu_pre=Lp["relu"], scale=sc, shift=sh)
+            else:
+                h = ops.masked_linear(a, Lp["pl"], relu=Lp["relu"])
+                if site is not None:
+                    sc, sh = site.affine(h, True)
+                    h = ops.masked_affine(h, scale=sc, shift=sh)
+        return h
+
+    def _forward_value(self, P, g, x, train):
+        N, K = x.shape[0], self.k
+        plan = cached_plan(g, N)
+        rplan = _cached_rplan(g, N)
+        self._zero_in_degree(plan)
+        x2 = x.view(N * K, 1)
+        if not train:
+            # both signs in the slot axis ([N, 2, K, c]): one propagation launch per layer (folded BatchNorm is row-wise)
+            h = torch.stack([x, self._neg(x2).view(N, K, 1)], dim=1).reshape(N * 2 * K, 1)
+            h = self._enc_value(P, plan, rplan, h, N, 2 * K, False)
+            z = ops.slot_sum(h.view(N * 2, -1), N, 2)                                  # sum over the sign axis -> [N, K * out]
+        else:
+            # enc(g, x) then enc(g, -x): each call normalises with its own batch statistics and moves the running statistics
+            zp = self._enc_value(P, plan, rplan, x2, N, K, True)
+            zm = self._enc_value(P, plan, rplan, self._neg(x2), N, K, True)
+            z = ops.masked_affine(zp, residual=zm).view(N, -1)
+        return _run_mlp(P["rho"], z, train=train).view(N, K, 1)                        # deepsigns.py:27-30
+
+    def _forward_grad(self, g, x):
+        """Differentiable train-mode forward: the launches of the value path as autograd nodes (the propagation's adjoint is the same
+        kernel on the flipped plan).  Under the switch `_bucket` (train_graph.DGLBucketedStep) `g` is a PADDED batch: the ops over the
+        N*K slot rows take the node-slot vector, those over the N rows of rho the node validity, as _DeepSignsBase._forward_grad."""
+        from . import autograd as AG
+        N, K = x.shape[0], self.k
+        pad = getattr(self, "_bucket", None)
+        plan, rplan = self._grad_plans(g, N)
+        self._zero_in_degree(plan, None if pad is None else pad.node_valid)
+        enc, L = self.enc, len(self.enc.layers)
+        sv, sk = (None, 0) if pad is None else (pad.node_slots, K)
+        x2 = x.view(N * K, 1)
+        outs = []
+        for sign in (0, 1):
+            h = x2 if sign == 0 else self._neg(x2)
+            for l, conv in enumerate(enc.layers):
+                d_in, d_out = conv.weight.shape
+                bn = enc.bns[l] if (enc.use_bn and l < L - 1) else None
+                # GraphConv's weight is [in, out]: the Linear weight is its transpose (in = 1: the same floats, viewed as a column)
+                Wt = conv.weight.view(d_out, 1) if d_in == 1 else conv.weight.t()
+                if d_in > d_out:
+                    z = AG.linear(h, Wt, None, sv, sk)
+                    h = AG.gcn_propagate(z.view(N, -1), plan, rplan, conv.bias, d_out).view(N * K, -1)
+                    if conv.relu:
+                        h = AG.act_residual(h, act="relu")
+                else:
+                    a = AG.gcn_propagate(h.view(N, -1), plan, rplan).view(N * K, -1)
+                    h = AG.linear(a, Wt, conv.bias, sv, sk, relu=conv.relu)
+                if bn is not None:
+                    h = AG.bn_act(h, bn, sv, sk, relu=False)
+            outs.append(h)
+        z = AG.masked_add(outs[0], outs[1], sv, sk)
+        return self._rho_grad(z.view(N, -1)).view(N, K, 1)
+
+
+class TransformerDeepSigns(_SignInvBase):
+    """layers/deepsigns.py:89-119: embed = Linear(1, hidden); enc = SetTransformerEncoder(hidden, 2 heads of hidden // 2, d_ff =
+    2 * (hidden // 2), num_layers blocks); rho = MLP(hidden * k, hidden, k, 4); forward = rho(cat_i [enc(g, embed(x)[:, i]) +
+    enc(g, embed(-x)[:, i])]).  `out_channels` is unused, as in the reference.  state_dict keys `embed.*`,
+    `enc.layers.{l}.mha.proj_{q,k,v,o}.weight`, `enc.layers.{l}.mha.ffn.{0,3}.*`, `enc.layers.{l}.mha.norm_{in,inter}.*`, `rho.*`.
+    The reference calls the encoder 2 k times per forward, each a padded dense attention per graph; here the 2 k (sign, slot) pairs ride
+    in the row axis and one sn_graph_attention_f32 launch per block serves every graph, slot, sign and head."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, k, use_bn=False, use_ln=False, dropout=0.5,
+                 activation="relu"):
+        super().__init__()
+        _no_dropout(dropout, "TransformerDeepSigns")
+        if use_ln:
+            raise ValueError("HIP path: only relu / no LayerNorm / no residual (what every shipped config uses)")
+        heads = 2
+        d_head = hidden_channels // heads
+        if d_head < 1 or d_head > ops.GRAPH_ATTENTION_MAX_HEAD:
+            raise ValueError(f"TransformerDeepSigns: head width {d_head} outside 1..{ops.GRAPH_ATTENTION_MAX_HEAD} (sn_graph_attention_f32)")
+        self.enc = SetTransformerEncoder(d_model=hidden_channels, n_heads=heads, d_head=d_head, d_ff=heads * d_head, n_layers=num_layers)
+        self.embed = nn.Linear(1, hidden_channels)
+        self.rho = MLP(hidden_channels * k, hidden_channels, k, 4, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.k = k
+
+    def _prepare(self, train=False):
+        layers = []
+        for blk in self.enc.layers:
+            m = blk.mha
+            Wqkv = torch.cat([m.proj_q.weight.detach(), m.proj_k.weight.detach(), m.proj_v.weight.detach()], dim=0)       # (a copy, no arithmetic)
+            layers.append(dict(qkv=ops.PackedLinear(ops.pack_weight(Wqkv), Wqkv.shape[0], Wqkv.shape[1], None), o=_pack(m.proj_o),
+                               f0=_pack(m.ffn[0]), f3=_pack(m.ffn[3]), heads=m.num_heads,
+                               ln1=(m.norm_in.weight.detach(), m.norm_in.bias.detach(), m.norm_in.eps),
+                               ln2=(m.norm_inter.weight.detach(), m.norm_inter.bias.detach(), m.norm_inter.eps)))
+        return dict(embed=_pack(self.embed), layers=layers, rho=_prep_mlp(self.rho, train))
+
+    def _forward_value(self, P, g, x, train):
+        """Eval and the train-mode value: the encoder has no BatchNorm, so both signs ride in the slot axis in either mode (rho's
+        BatchNorms see the batch once per forward, as in the reference)."""
+        N, K = x.shape[0], self.k
+        S = 2 * K
+        plan = cached_plan(g, N)
+        h = torch.stack([x, self._neg(x.view(N * K, 1)).view(N, K, 1)], dim=1).reshape(N * S, 1)         # rows node * 2K + sign * K + slot
+        h = ops.masked_linear(h, P["embed"])
+        for Lp in P["layers"]:
+            qkv = ops.masked_linear(h, Lp["qkv"])
+            D = qkv.shape[1] // 3
+            att, _ = ops.graph_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], plan.graph_ptr, N, S, Lp["heads"])
+            h = ops.masked_layernorm(ops.masked_linear(att, Lp["o"]), h, *Lp["ln1"])
+            f = ops.masked_linear(ops.masked_linear(h, Lp["f0"], relu=True), Lp["f3"])
+            h = ops.masked_layernorm(f, h, *Lp["ln2"])
+        z = ops.slot_sum(h.view(N * 2, -1), N, 2)                                      # sum over the sign axis -> [N, K * hidden]
+        return _run_mlp(P["rho"], z, train=train).view(N, K, 1)                        # deepsigns.py:116-118
+
+    def _forward_grad(self, g, x):
+        """Differentiable train-mode forward: one attention launch per block forward, one backward.  Under `_bucket` the padding nodes
+        form the batch's spare graph: attention never mixes them with valid nodes, and their rows are masked out of every Linear."""
+        from . import autograd as AG
+        N, K = x.shape[0], self.k
+        S = 2 * K
+        pad = getattr(self, "_bucket", None)
+        plan, _ = self._grad_plans(g, N)
+        if ops.deferring():
+            ops.defer("plan", plan)
+        sv = None if pad is None else pad.node_slots * 2                               # 2K slot rows on valid nodes, 0 on padding (index plumbing)
+        sk = 0 if pad is None else S
+        h = torch.stack([x, self._neg(x.view(N * K, 1)).view(N, K, 1)], dim=1).reshape(N * S, 1)
+        h = AG.linear(h, self.embed.weight, self.embed.bias, sv, sk)
+        for blk in self.enc.layers:
+            m = blk.mha
+            Wqkv = torch.cat([m.proj_q.weight, m.proj_k.weight, m.proj_v.weight], dim=0)
+            att = AG.graph_attention(AG.linear(h, Wqkv, None, sv, sk), plan.graph_ptr, N, S, m.num_heads)
+            h = AG.masked_layernorm(AG.linear(att, m.proj_o.weight, None, sv, sk), h, m.norm_in.weight, m.norm_in.bias, m.norm_in.eps, sv, sk)
+            f = AG.linear(AG.linear(h, m.ffn[0].weight, m.ffn[0].bias, sv, sk, relu=True), m.ffn[3].weight, m.ffn[3].bias, sv, sk)
+            h = AG.masked_layernorm(f, h, m.norm_inter.weight, m.norm_inter.bias, m.norm_inter.eps, sv, sk)
+        z = AG.slot_sum(h.view(N * 2, -1), N, 2)
+        return self._rho_grad(z).view(N, K, 1)
+
+
 def get_sign_inv_net(net_params):
-    """nets/ZINC_graph_regression/sign_inv_net.py:3-17 (the 'gin' and 'masked_gin' branches — the only ones a shipped
-    config selects)."""
+    """nets/ZINC_graph_regression/sign_inv_net.py:3-17: 'gcn', 'gin', 'masked_gin' and 'transformer' with the reference's argument lists
+    (a shipped config selects 'gin' or 'masked_gin'; the main script's --sign_inv_net takes all four); anything
+    else raises ValueError('Invalid sign inv net')."""
     assert net_params["sign_inv_net"] is not None, "did not specify sign inv net"
     kind = net_params["sign_inv_net"]
     args = (1, net_params["hidden_dim"], net_params["phi_out_dim"], net_params["sign_inv_layers"], net_params["pos_enc_dim"])
     kw = dict(use_bn=True, dropout=net_params["dropout"], activation=net_params["sign_inv_activation"])
+    if kind == "gcn":
+        return GCNDeepSigns(*args, **kw)
     if kind == "gin":
         return GINDeepSigns(*args, **kw)
     if kind == "masked_gin":
         return MaskedGINDeepSigns(*args, net_params["device"], **kw)
+    if kind == "transformer":
+        return TransformerDeepSigns(*args, **kw)
     raise ValueError("Invalid sign inv net")

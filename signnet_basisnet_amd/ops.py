@@ -1538,3 +1538,72 @@ def ones_vector(n, device):
     if t is None:
         t = _ONES[key] = torch.ones(int(n), dtype=torch.float32, device=device)
     return t
+
+
+# ----------------------------------------------------------------------------- the 'gcn' / 'transformer' sign-invariant encoders (csrc/deepsigns_variants.hip)
+def _row_block(t, name):
+    """A float32 [R, C] block whose rows are contiguous (a column block of a wider row matrix, or a view at an offset) -> its row stride."""
+    if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name}: expected a float32 [R, C] block with contiguous rows")
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def gcn_propagate(x, plan: GraphPlan, rplan: GraphPlan, bias=None, width=0):
+    """dgl.nn.pytorch.GraphConv(norm='both') without its weight: out[i] = cin[i] * sum_{j -> i} cout[j] * x[j] (+ bias[c % width]) with
+    cin / cout = clamp(in- / out-degree, 1)^-1/2 read from the two plans' row pointers (plan: sn_batch_plan of the batch, rplan: of its
+    flipped edge list).  x: [N, C] with contiguous rows (any row stride).  The adjoint w.r.t. x is gcn_propagate(g, rplan, plan)."""
+    require_cuda(x)
+    ldx = _row_block(x, "gcn_propagate: x")
+    N, Cc = x.shape
+    if plan.N != N or rplan.N != N:
+        raise ValueError(f"gcn_propagate: x has {N} rows, the plans {plan.N} and {rplan.N} nodes")
+    if bias is not None:
+        bias = _f32c(bias, "bias")
+        if int(width) <= 0 or bias.numel() != int(width) or Cc % int(width):
+            raise ValueError("gcn_propagate: bias must be [width] with width dividing the row length")
+    out = torch.empty(N, Cc, dtype=torch.float32, device=x.device)
+    if N == 0:
+        return out
+    with _span("sn_gcn_propagate_f32"):
+        check(lib().sn_gcn_propagate_f32(ptr(x), ldx, N, Cc, ptr(plan.rowptr), ptr(plan.col), ptr(rplan.rowptr), ptr(bias), int(width),
+                                         ptr(out), Cc, stream()), "sn_gcn_propagate_f32")
+    return out
+
+
+GRAPH_ATTENTION_MAX_HEAD = 64
+
+
+def graph_attention(q, k, v, graph_ptr, N, S, heads):
+    """Multi-head self-attention over the nodes of each graph, independently per slot (dgl's SetTransformerEncoder block 'sab'): a set is
+    (graph, slot), its rows node * S + slot.  q, k, v: [N*S, heads*dh] blocks with one common row stride (column blocks of one
+    projection); graph_ptr: int32 [B+1].  -> (out [N*S, heads*dh], lse [N*S, heads]).  dh <= 64."""
+    require_cuda(q, k, v)
+    ld = _row_block(q, "graph_attention: q")
+    R, D = q.shape
+    if k.shape != q.shape or v.shape != q.shape or _row_block(k, "graph_attention: k") != ld or _row_block(v, "graph_attention: v") != ld:
+        raise ValueError("graph_attention: q, k, v must be blocks of one shape and one row stride")
+    if D % heads or R != int(N) * int(S):
+        raise ValueError("graph_attention: expected N * S rows of heads * dh columns")
+    B = graph_ptr.numel() - 1
+    out = torch.empty(R, D, dtype=torch.float32, device=q.device)
+    lse = torch.empty(R, heads, dtype=torch.float32, device=q.device)
+    with _span("sn_graph_attention_f32"):
+        check(lib().sn_graph_attention_f32(ptr(q), ptr(k), ptr(v), ld, ptr(graph_ptr), int(N), B, int(S), int(heads), D // heads, ptr(out), D,
+                                           ptr(lse), stream()), "sn_graph_attention_f32")
+    return out, lse
+
+
+def graph_attention_bwd(q, k, v, out, lse, dout, graph_ptr, N, S, heads):
+    """Adjoint of graph_attention -> dqkv [N*S, 3 * heads*dh] (column blocks dq | dk | dv).  Rows of empty graphs do not exist; every
+    row of the result is written."""
+    ld = _row_block(q, "graph_attention_bwd: q")
+    R, D = q.shape
+    out, dout, lse = _f32c(out, "out"), _f32c(dout, "dout"), _f32c(lse, "lse")
+    B = graph_ptr.numel() - 1
+    g = torch.empty(R, 3 * D, dtype=torch.float32, device=q.device)
+    delta = torch.empty(R, heads, dtype=torch.float32, device=q.device)
+    with _span("sn_graph_attention_bwd_f32"):
+        check(lib().sn_graph_attention_bwd_f32(ptr(q), ptr(k), ptr(v), ld, ptr(out), D, ptr(lse), ptr(dout), D, ptr(graph_ptr), int(N), B,
+                                               int(S), int(heads), D // heads, ptr(g), ptr(g[:, D:]), ptr(g[:, 2 * D:]), 3 * D, ptr(delta),
+                                               stream()), "sn_graph_attention_bwd_f32")
+    return g
