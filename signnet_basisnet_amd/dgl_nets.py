@@ -1,18 +1,19 @@
-"""The DGL tree's GIN base network on the HIP layer kernels (first item: the consumer of the sign-invariant
-positional encoding in the tree that owns main_ZINC_graph_regression.py).
+"""The DGL tree's five base networks on the HIP layer kernels (the consumers of the sign-invariant positional
+encoding in the tree that owns main_ZINC_graph_regression.py): `GINNet`, `GatedGCNNet`, `PNANet`, `TransformerNet`, `GATNet`.
 
-Mirrors GraphPrediction/nets/ZINC_graph_regression/gin_net.py:19-139 (`GINNet`) for the configuration the shipped
-GIN_ZINC_LapPE_signinv_GIN.json selects — pe_init = 'lap_pe', lap_lspe = False: `h = embedding_h(h) + embedding_p(p)`
-(:80-92), L x dgl GINConv(MLP(hidden, hidden, out, 2, use_bn), 'sum') (:58-66, 99-100), mean / sum readout (:126-133),
-MLPReadout (layers/mlp_readout_layer.py:9-24) — with the same constructor (`net_params`), forward contract
-`model(g, h, p, e, snorm_n) -> (scores, g)` and state_dict keys, and `model.sign_inv_net` (GINDeepSigns / MaskedGINDeepSigns)
-attached as in the reference.  Eval, train-mode value and — with gradients enabled — the differentiable path (autograd.py).
-The LSPE / random-walk variants (p_out, Whp, lapeig loss) are not built and raise.
+Each mirrors its nets/ZINC_graph_regression/*_net.py for the configurations the shipped JSONs select — pe_init = 'lap_pe',
+lap_lspe = False — with the same constructor (`net_params`), forward contract `model(g, h, p, e, snorm_n) -> (scores, g)` and
+state_dict keys, and `model.sign_inv_net` attached as in the reference.  Eval, train-mode value and — with gradients enabled — the
+differentiable path (autograd.py).  The LSPE / random-walk variants (p_out, Whp, lapeig loss) are not built and raise.
 
 The baseline rows of the same table run on the same nets: pe_init = 'no_pe' (the *_NoPE configs: no embedding_p, `p` is not read and may
 be None) and pe_init = 'lap_pe' behind `handle_lap` with lap_method 'sign_flip' / 'abs_val' / 'canonical' / 'none' (the *_LapPE
 configs); a sign_inv_net is built for lap_method 'sign_inv' only, pe_proj for pe_aggregate 'concat' (GatedGCN, Transformer), as in
 the reference.
+
+What the five share lives in `_DGLNet`: the constructor's head and tail, the forward prologue, the input encoder and the read-out
+(value and differentiable form each), `loss`, the one-launch eval kernels' eligibility (`_stage`) and their deferred error report
+(`check_last`).  A net adds its layer parameters, its layer loop and, where it has them, its padded / fused eval layouts.
 """
 from __future__ import annotations
 
@@ -21,9 +22,12 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
+from types import SimpleNamespace
+
+from . import autograd as AG
 from . import ops
 from ._lib import check, lib, ptr, stream
-from .dgl_deepsigns import MLP, cached_plan, _await_side, _bucket_rows, _max_nodes, _max_in_edges, _node_counts, _BNSite, _GINConv, _pack, _prep_mlp, _run_mlp, get_sign_inv_net
+from .dgl_deepsigns import MLP, cached_plan, _await_side, _bucket_rows, _max_nodes, _max_in_edges, _node_counts, _BNSite, _GINConv, _fold_bn_before, _pack, _pad_mat, _prep_mlp, _run_mlp, get_sign_inv_net
 
 
 def handle_lap(model, batch_pos_enc, batch_graphs, device=None, *, u=None):
@@ -66,10 +70,11 @@ def _check_pe_init(name, pe_init, lap_lspe, use_lapeig_loss):
 def _zero_pe(net, N, dev):
     """[>= N, 1] zeros, kept with the eval cache: the positional encoding a NoPE net hands to a one-launch kernel whose input stage
     adds a projection of it (the projection is zero too: the stage computes embedding_h alone)."""
-    c = net.__dict__.setdefault("_cache", {})
-    z = c.get("zero_pe")
-    if z is None or z.shape[0] < N or z.device != dev:
-        z = c["zero_pe"] = torch.zeros(max(int(N), 256), 1, dtype=torch.float32, device=dev)
+    make = lambda: torch.zeros(max(int(N), 256), 1, dtype=torch.float32, device=dev)
+    z = net._cached("zero_pe", make)
+    if z.shape[0] < N or z.device != dev:          # grown on demand
+        del net._cache["zero_pe"]
+        z = net._cached("zero_pe", make)
     return z
 
 
@@ -108,39 +113,181 @@ class _PackCache:
         self._cache = {}
         return super()._load_from_state_dict(*a, **k)
 
-    def _pk(self, lin):
-        if self.training:
-            return _pack(lin)
+    def _cached(self, key, build):
+        """The cache's entry `key`, made by `build()` on its first use since the cache was emptied."""
         c = self.__dict__.setdefault("_cache", {})
-        if id(lin) not in c:
-            c[id(lin)] = _pack(lin)
-        return c[id(lin)]
+        if key not in c:
+            c[key] = build()
+        return c[key]
+
+    def _pk(self, lin):
+        return _pack(lin) if self.training else self._cached(id(lin), lambda: _pack(lin))
 
     def _bn(self, bn, train):
-        if train:
-            return _BNSite(bn, True)
-        c = self.__dict__.setdefault("_cache", {})
-        if id(bn) not in c:
-            c[id(bn)] = _BNSite(bn, False)
-        return c[id(bn)]
+        return _BNSite(bn, True) if train else self._cached(id(bn), lambda: _BNSite(bn, False))
 
     def _abde(self, L):
         """The four node Linears of a GatedGCN layer packed as one [4d, d] Linear (eval cache)."""
-        c = self.__dict__.setdefault("_cache", {})
-        key = ("abde", id(L))
-        if key not in c:
+        def build():
             W = torch.cat([getattr(L, n).weight.detach() for n in "ABDE"], 0).contiguous()
             b = torch.cat([getattr(L, n).bias.detach() for n in "ABDE"], 0).contiguous()
-            c[key] = ops.PackedLinear(ops.pack_weight(W), W.shape[0], W.shape[1], b)
-        return c[key]
+            return ops.PackedLinear(ops.pack_weight(W), W.shape[0], W.shape[1], b)
+        return self._cached(("abde", id(L)), build)
 
     def _mlp(self, mlp, train):
-        if train:
-            return _prep_mlp(mlp, True)
-        c = self.__dict__.setdefault("_cache", {})
-        if id(mlp) not in c:
-            c[id(mlp)] = _prep_mlp(mlp, False)
-        return c[id(mlp)]
+        return _prep_mlp(mlp, True) if train else self._cached(id(mlp), lambda: _prep_mlp(mlp, False))
+
+
+class _DGLNet(_PackCache, nn.Module):
+    """What GINNet, GatedGCNNet, PNANet, TransformerNet and GATNet share.  A net's __init__ is `_init_common`, its own layers,
+    `_init_tail`; its forward is `_prologue`, then `_encode` / its layer loop / `_readout` (or their `_grad` forms)."""
+
+    _stage_cls = None        # the packer of the net's one-launch eval kernel (_FusedGin, _FusedGated, _FusedTransformer), if it has one
+    _stage_edges = 192       # the most in-edges of a graph that kernel holds; None: the packer's own `max_edges`
+    _malformed_note = ""     # check_last()'s wording of a malformed batch and of the size limit
+    _limit_text = "192 in-edges"
+
+    def _init_common(self, net_params, name, refusals, *, edge_dim=None, in_feat_dropout=None):
+        """The constructor's head: the attributes every net reads from `net_params`, the refusals — the PE switches, then `refusals`
+        ((condition, what the net covers instead) pairs, in order), then dropout — and the input embeddings.  `edge_dim`: the width of
+        embedding_e where it is not hidden_dim; `in_feat_dropout`: where the reference registers its nn.Dropout ('before_h': in front
+        of embedding_h, 'after_e': behind embedding_e; None: the net has none)."""
+        p = net_params
+        hidden = p["hidden_dim"]
+        self._who = name
+        self.n_layers, self.readout, self.batch_norm = p["L"], p["readout"], p["batch_norm"]
+        self.residual, self.edge_feat, self.device = p["residual"], p["edge_feat"], p["device"]
+        self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
+        self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
+        self.pos_enc_dim = p["pos_enc_dim"]
+        _check_pe_init(name, self.pe_init, self.lap_lspe, self.use_lapeig_loss)
+        for refused, covered in refusals:
+            if refused:
+                raise NotImplementedError(f"HIP {name}: {covered}")
+        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
+            raise NotImplementedError(f"HIP {name}: dropout 0.0 (as in the shipped configs)")
+        if self.pe_init == "lap_pe":
+            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
+        if in_feat_dropout == "before_h":
+            self.in_feat_dropout = nn.Dropout(0.0)
+        self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
+        self.embedding_e = nn.Embedding(p["num_bond_type"], edge_dim or hidden) if self.edge_feat else nn.Linear(1, hidden)
+        if in_feat_dropout == "after_e":
+            self.in_feat_dropout = nn.Dropout(0.0)
+
+    def _init_tail(self, net_params):
+        """The constructor's tail, behind the net's own layers: the read-out MLP, `g`, sign_inv_net and pe_proj, in the reference's order."""
+        self.MLP_layer = MLPReadout(net_params["out_dim"], 1)
+        self.g = None
+        if self.lap_method == "sign_inv":
+            self.sign_inv_net = get_sign_inv_net(net_params)
+        if getattr(self, "pe_aggregate", "add") == "concat":
+            self.pe_proj = nn.Linear(2 * net_params["hidden_dim"], net_params["hidden_dim"])
+
+    # ------------------------------------------------------------------ forward: prologue, input encoder, read-out
+    def _prologue(self, g, h, p):
+        """-> (pe, N, hidx, p, train, grad): whether p is read, the node count, the atom types as int64 [N], p as contiguous float (None
+        for NoPE: p is not read, as in the reference), the mode, and whether this call takes the differentiable path."""
+        _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
+        ops.require_cuda(h)
+        pe = self.pe_init == "lap_pe"
+        if pe and p is None:
+            raise NotImplementedError(f"HIP {self._who} with pe_init='lap_pe' needs the positional encoding p")
+        N = h.shape[0]
+        train = self.training
+        grad = train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())
+        return pe, N, h.long().reshape(N), p.contiguous().float() if pe else None, train, grad
+
+    def _plan(self, g, N):
+        src, dst = g.edges()
+        bnn = g.batch_num_nodes().to(src.device)
+        B = int(bnn.numel())
+        # (the node total comes from the graph object's cached host counts: repeat_interleave without output_size would read the sum
+        #  back from the device — a host wait per batch, and not recordable in a HIP graph)
+        if _node_counts(g)[1] != N:
+            raise ValueError("batch_num_nodes does not sum to the number of feature rows")
+        batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)      # index plumbing only
+        return batch.long(), torch.stack([src.long(), dst.long()]), B
+
+    def _encode(self, x, p):
+        """The input encoder of the value paths behind x = embedding_h(h): h + embedding_p(p), or pe_proj(cat[h, embedding_p(p)]) for
+        pe_aggregate 'concat' (gatedgcn_net.py:93-103, transformer_net.py:96-102); NoPE leaves h alone."""
+        if self.pe_init != "lap_pe":
+            return x
+        if getattr(self, "pe_aggregate", "add") == "concat":
+            pp = ops.masked_linear(p, self._pk(self.embedding_p))
+            return ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))
+        return ops.masked_linear(p, self._pk(self.embedding_p), residual=x)
+
+    def _encode_grad(self, hidx, p, vN, k1):
+        """embedding_h and the input encoder as autograd nodes (vN, k1: the valid rows of a padded batch, see _bucket_rows)."""
+        x = AG.embedding_sum(hidx, [self.embedding_h.weight])
+        if self.pe_init != "lap_pe":
+            return AG.mask_rows(x, vN, k1)
+        pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
+        if getattr(self, "pe_aggregate", "add") == "concat":
+            return AG.linear(torch.cat([x, pp], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
+        return AG.masked_add(pp, x, vN, k1)
+
+    def _readout(self, x, plan, first=None):
+        """mean / sum pooling over each graph's nodes, then MLPReadout.  `first`: the first Linear packed for padded channels of x."""
+        hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
+        fcs = self.MLP_layer.FC_layers
+        for i, fc in enumerate(fcs):
+            hg = ops.masked_linear(hg, first if i == 0 and first is not None else self._pk(fc), relu=i < len(fcs) - 1)
+        return hg
+
+    def _readout_grad(self, x, plan, vB, k1):
+        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
+        fcs = self.MLP_layer.FC_layers
+        for i, fc in enumerate(fcs):
+            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
+        return hg
+
+    def loss(self, scores, targets):
+        """*_net.py `loss` with use_lapeig_loss = False: the L1 task loss (a torch reduction over B scalars)."""
+        return (scores - targets).abs().mean()
+
+    # ------------------------------------------------------------------ the one-launch eval kernels: eligibility, deferred errors
+    def _stage(self, g):
+        """The packed stage-kernel parameters if this batch can take the net's one-launch eval path, else None.  A graph with more than
+        64 nodes, or more in-edges than the kernel's LDS image holds (192; GatedGCN: sn_gatedgcn_max_edges(d), 176 at hidden 68), takes
+        the layer path, as the reference evaluates any graph: both counts come with a DGL batch (batch_num_nodes(), batch_num_edges())
+        and are read once per graph object.  A duck-typed graph without edge counts reaches the kernel, which flags such a graph on
+        the device — NaN score, check_last()."""
+        if self._stage_cls is None or self.training or not self.fused_stages:
+            return None
+        fz = self._cached("stage", lambda: self._stage_cls(self))
+        if not fz.ok:
+            return None
+        me = _max_in_edges(g)
+        return fz if 0 < _max_nodes(g) <= 64 and (me is None or me <= (self._stage_edges or fz.max_edges)) else None
+
+    def check_last(self):
+        """Raise what the last one-launch eval forward flagged on the device (its scores are NaN in that case): a node / edge type
+        outside the embedding tables (IndexError, as nn.Embedding), a malformed batch, or a graph the stage kernel could not hold.  One
+        host sync; also run by train().  The layer path (fused_stages = False, train mode; PNA and GAT always) raises immediately
+        instead and leaves nothing to check."""
+        plan, self._last_plan = getattr(self, "_last_plan", None), None
+        if plan is None:
+            return
+        st = plan.status.tolist()
+        if st[3] or st[5]:
+            plan.status[3:6].zero_()         # (the plan is cached on the graph object: a later forward of the same graph starts clean)
+        if st[0]:
+            raise ValueError(f"{self._who}: the last batch is malformed ({self._malformed_note}sn_batch_plan status {st[0]})")
+        if (st[3] & 4) or st[5]:
+            raise IndexError(ops.EMBEDDING_INDEX_ERROR)
+        if st[3] & 8:
+            raise RuntimeError(f"{self._who}: a graph of the last batch has no nodes; its score is NaN — set fused_stages = False "
+                               "for such batches")
+        if st[3] & 3:
+            raise RuntimeError(f"{self._who}: a graph of the last batch has more than 64 nodes or {self._limit_text}; its score is "
+                               "NaN — set fused_stages = False for such batches")
+
+    def train(self, mode=True):
+        self.check_last()
+        return super().train(mode)
 
 
 class _FusedGin:
@@ -151,7 +298,6 @@ class _FusedGin:
 
     def __init__(self, net):
         from .fused import _GnnParams, GNN_MAX_LAYERS
-        from .dgl_deepsigns import _fold_bn_before, _pad_mat
         self.ok = False
         convs, fcs = list(net.layers), list(net.MLP_layer.FC_layers)
         nope = net.pe_init != "lap_pe"       # NoPE: a zero projection of a one-column zero encoding (h = embedding_h(h) + 0)
@@ -209,174 +355,89 @@ class _FusedGin:
         return y
 
 
-class GINNet(_PackCache, nn.Module):
+class GINNet(_DGLNet):
+    """nets/ZINC_graph_regression/gin_net.py:19-139 for the configuration GIN_ZINC_LapPE_signinv_GIN.json selects:
+    `h = embedding_h(h) + embedding_p(p)` (:80-92), L x dgl GINConv(MLP(hidden, hidden, out, 2, use_bn), 'sum') (:58-66, 99-100),
+    mean / sum readout (:126-133), MLPReadout."""
+
     fused_stages = True      # eval: embeddings, every layer and the readout in ONE launch (sn_gin_net_fused_f32); False: the layer path
-
-    def _fused_gin(self, g):
-        """The packed stage-kernel parameters if this batch can take the one-launch path, else None (as GatedGCNNet._fused_gated: graph
-        sizes come with the batch object; a batch beyond the kernel's limits that still reaches it gets NaN scores + check_last())."""
-        if self.training or not self.fused_stages:
-            return None
-        c = self.__dict__.setdefault("_cache", {})
-        if "fused_gin" not in c:
-            c["fused_gin"] = _FusedGin(self)
-        fz = c["fused_gin"]
-        if not fz.ok:
-            return None
-        me = _max_in_edges(g)
-        return fz if 0 < _max_nodes(g) <= 64 and (me is None or me <= 192) else None
-
-    def check_last(self):
-        """Raise what the last one-launch eval forward flagged on the device (its scores are NaN in that case): an atom type outside
-        the embedding table (IndexError, as nn.Embedding), a malformed batch, or a graph the stage kernel could not hold.  One host
-        sync; also run by train().  The layer path (fused_stages = False, train mode) raises immediately instead."""
-        plan, self._last_plan = getattr(self, "_last_plan", None), None
-        if plan is not None:
-            st = plan.status.tolist()
-            if st[3] or st[5]:
-                plan.status[3:6].zero_()         # (the plan is cached on the graph object: a later forward of the same graph starts clean)
-            if st[0]:
-                raise ValueError(f"{type(self).__name__}: the last batch is malformed (sn_batch_plan status {st[0]})")
-            if (st[3] & 4) or st[5]:
-                raise IndexError(ops.EMBEDDING_INDEX_ERROR)
-            if st[3] & 8:
-                raise RuntimeError(f"{type(self).__name__}: a graph of the last batch has no nodes; its score is NaN — set fused_stages = False "
-                                   "for such batches")
-            if st[3] & 3:
-                raise RuntimeError(f"{type(self).__name__}: a graph of the last batch has more than 64 nodes or 192 in-edges; its score is "
-                                   "NaN — set fused_stages = False for such batches")
-
-    def train(self, mode=True):
-        self.check_last()
-        return super().train(mode)
+    _stage_cls = _FusedGin
 
     def __init__(self, net_params):
         super().__init__()
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self.n_layers, self.readout, self.batch_norm = p["L"], p["readout"], p["batch_norm"]
-        self.residual, self.edge_feat, self.device = p["residual"], p["edge_feat"], p["device"]
-        self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
-        self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
-        self.pos_enc_dim = p["pos_enc_dim"]
-        _check_pe_init("GINNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
-        if self.readout == "max":
-            raise NotImplementedError("HIP GINNet: readout 'sum' or 'mean'")
-        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
-            raise NotImplementedError("HIP GINNet: dropout 0.0 (as in the shipped configs)")
-        if self.pe_init == "lap_pe":
-            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
-        self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
-        self.embedding_e = nn.Embedding(p["num_bond_type"], hidden) if self.edge_feat else nn.Linear(1, hidden)   # unused by GIN
+        self._init_common(p, "GINNet", [(p["readout"] == "max", "readout 'sum' or 'mean'")])      # (embedding_e: unused by GIN)
         self.layers = nn.ModuleList(
             [_GINConv(MLP(hidden, hidden, hidden, 2, use_bn=self.batch_norm, dropout=0.0, activation="relu")) for _ in range(self.n_layers - 1)] +
             [_GINConv(MLP(hidden, hidden, out_dim, 2, use_bn=self.batch_norm, dropout=0.0, activation="relu"))])
-        self.MLP_layer = MLPReadout(out_dim, 1)
-        self.g = None
-        if self.lap_method == "sign_inv":
-            self.sign_inv_net = get_sign_inv_net(net_params)
-
-    # ------------------------------------------------------------------
-    def _plan(self, g, N):
-        src, dst = g.edges()
-        bnn = g.batch_num_nodes().to(src.device)
-        B = int(bnn.numel())
-        # (the node total comes from the graph object's cached host counts: repeat_interleave without output_size would read the sum
-        #  back from the device — a host wait per batch, and not recordable in a HIP graph)
-        if _node_counts(g)[1] != N:
-            raise ValueError("batch_num_nodes does not sum to the number of feature rows")
-        batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)      # index plumbing only
-        return batch.long(), torch.stack([src.long(), dst.long()]), B
+        self._init_tail(p)
 
     def _gin_padded(self):
         """Eval cache: the net's parameters with every channel axis zero-padded to a multiple of 4 (pad rows / columns of the weights,
         pad entries of biases and folded BatchNorms are zero, so pad channels stay exactly 0 through ReLU and the aggregations)."""
-        c = self.__dict__.setdefault("_cache", {})
-        if "gin_padded" in c:
-            return c["gin_padded"]
+        return self._cached("gin_padded", self._pad_gin)
+
+    def _pad_gin(self):
         dev = self.embedding_h.weight.device
         up = lambda k: (k + 3) // 4 * 4
 
-        def padw(W, b, rows, cols):
+        def padw(lin, rows, cols):           # (a rectangular pad: _pad_mat makes squares)
             Wp = torch.zeros(rows, cols, dtype=torch.float32, device=dev)
-            Wp[:W.shape[0], :W.shape[1]] = W.detach().float()
-            bp = torch.zeros(rows, dtype=torch.float32, device=dev)
-            if b is not None:
-                bp[:b.shape[0]] = b.detach().float()
-            return ops.PackedLinear(ops.pack_weight(Wp), rows, cols, bp)
-
-        def padv(v, n_):
-            out = torch.zeros(n_, dtype=torch.float32, device=dev)
-            out[:v.shape[0]] = v
-            return out
-
-        class _Site:          # a folded BatchNorm on the padded channels (what _run_mlp reads)
-            def __init__(self, sc, sh):
-                self.scale, self.shift = sc, sh
+            Wp[:lin.weight.shape[0], :lin.weight.shape[1]] = lin.weight.detach().float()
+            return ops.PackedLinear(ops.pack_weight(Wp), rows, cols, ops.pad_vec(lin.bias, rows))
 
         hid = self.embedding_h.weight.shape[1]
         E = torch.zeros(self.embedding_h.weight.shape[0], up(hid), dtype=torch.float32, device=dev)
         E[:, :hid] = self.embedding_h.weight.detach().float()
         P = {"emb_h": E}
         if self.pe_init == "lap_pe":
-            P["emb_p"] = padw(self.embedding_p.weight, self.embedding_p.bias, up(hid), self.embedding_p.weight.shape[1])
+            P["emb_p"] = padw(self.embedding_p, up(hid), self.embedding_p.weight.shape[1])
         layers, keep = [], []
         for conv in self.layers:
             m = conv.apply_func
             chain = []
             for i, lin in enumerate(m.lins):
-                site = None
+                rows, site = up(lin.weight.shape[0]), None
                 if m.use_bn and i < len(m.lins) - 1:
-                    s0 = self._bn(m.bns[i], False)
-                    site = _Site(padv(s0.scale, up(lin.weight.shape[0])), padv(s0.shift, up(lin.weight.shape[0])))
-                chain.append((padw(lin.weight, lin.bias, up(lin.weight.shape[0]), up(lin.weight.shape[1])), site))
+                    s0 = self._bn(m.bns[i], False)          # a folded BatchNorm on the padded channels (what _run_mlp reads)
+                    site = SimpleNamespace(scale=ops.pad_vec(s0.scale, rows), shift=ops.pad_vec(s0.shift, rows))
+                chain.append((padw(lin, rows, up(lin.weight.shape[1])), site))
             # the whole MLP as one sn_mlp_chain_f32 launch: Linear -> ReLU -> [BatchNorm folded into the next Linear] ... -> Linear
             fused = None
             widths = [up(m.lins[0].weight.shape[1])] + [up(l.weight.shape[0]) for l in m.lins]
             rp = max(48, 16 * ((max(widths) + 15) // 16))
             if rp <= 128 and len(m.lins) <= 16:
-                from .dgl_deepsigns import _fold_bn_before, _pad_mat
-                import ctypes as C_
                 ws = []
                 for i, lin in enumerate(m.lins):
                     site = self._bn(m.bns[i - 1], False) if (m.use_bn and i > 0) else None
                     Wf, bf = _fold_bn_before(lin, site)
                     ws.append(ops.pack_split(_pad_mat(Wf, rp), ops.pad_vec(bf, rp), None, None))
                 keep.extend(ws)
-                fused = ((C_.c_void_p * len(ws))(*[w.data_ptr() for w in ws]), len(ws), rp, up(m.lins[-1].weight.shape[0]))
+                fused = ((C.c_void_p * len(ws))(*[w.data_ptr() for w in ws]), len(ws), rp, up(m.lins[-1].weight.shape[0]))
             layers.append((conv.eps, chain, fused))
         P["layers"] = layers
         P["keep"] = keep
         fc0 = self.MLP_layer.FC_layers[0]
-        P["fc0"] = padw(fc0.weight, fc0.bias, fc0.weight.shape[0], up(fc0.weight.shape[1]))
-        c["gin_padded"] = P
+        P["fc0"] = padw(fc0, fc0.weight.shape[0], up(fc0.weight.shape[1]))
         return P
 
     def forward(self, g, h, p, e, snorm_n=None):
-        _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
-        ops.require_cuda(h)
-        pe = self.pe_init == "lap_pe"
-        if pe and p is None:
-            raise NotImplementedError("HIP GINNet with pe_init='lap_pe' needs the positional encoding p")
-        N = h.shape[0]
-        hidx = h.long().reshape(N)
-        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference — gin_net.py:87-92)
-        train = self.training
-        if train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
+        if grad:
             batch, ei, B = self._plan(g, N)
             plan = ops.build_plan(batch, ei, B, 0)
             y = self._forward_grad(plan, batch, ei, B, hidx, p)
         else:
             plan = cached_plan(g, N)       # the sign-invariant net's plan of this graph object, if there is one: ONE sn_batch_plan per batch
             with torch.no_grad():
-                fz = self._fused_gin(g)
+                fz = self._stage(g)
                 if fz is not None:
                     # no host sync on this path: a bad atom type / an oversize graph is flagged in the plan's status block, the score is
                     # NaN, check_last() raises
                     self._last_plan = plan
-                    self.g = g
-                    return fz.run(plan, hidx.contiguous(), p if pe else _zero_pe(self, N, h.device)[:N]), g
-                if not train and self.embedding_h.weight.shape[1] % 4:
+                    y = fz.run(plan, hidx.contiguous(), p if pe else _zero_pe(self, N, h.device)[:N])
+                elif not train and self.embedding_h.weight.shape[1] % 4:
                     # eval, hidden width not a multiple of 4 (GIN_ZINC_LapPE_signinv_GIN.json: 95): every row would be misaligned and every
                     # Linear on the scalar kernel; run on zero-padded channels instead (`_gin_padded`: 95 -> 96, all rows 16-byte aligned)
                     P = self._gin_padded()
@@ -393,36 +454,20 @@ class GINNet(_PackCache, nn.Module):
                         with ops._span("sn_mlp_chain_f32"):
                             check(lib().sn_mlp_chain_f32(ptr(a), a.shape[1], a.shape[0], a.shape[1], None, 0, ws, n_l, rp, ptr(x), d_out, d_out,
                                                          stream()), "sn_mlp_chain_f32")
-                    hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-                    fcs = self.MLP_layer.FC_layers
-                    hg = ops.masked_linear(hg, P["fc0"], relu=len(fcs) > 1)
-                    for i, fc in enumerate(fcs[1:], 1):
-                        hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
-                    self.g = g
-                    return hg, g
-                x = ops.embedding_sum(hidx, [self.embedding_h.weight])
-                if pe:
-                    x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                          # h + embedding_p(p)   (:87-92)
-                for conv in self.layers:
-                    a = ops.gin_aggregate(x, plan, conv.eps)
-                    x = _run_mlp(self._mlp(conv.apply_func, train), a, train=train)
-                hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-                fcs = self.MLP_layer.FC_layers
-                for i, fc in enumerate(fcs):
-                    hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
-                y = hg
+                    y = self._readout(x, plan, first=P["fc0"])
+                else:
+                    x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)          # h + embedding_p(p)   (:87-92)
+                    for conv in self.layers:
+                        a = ops.gin_aggregate(x, plan, conv.eps)
+                        x = _run_mlp(self._mlp(conv.apply_func, train), a, train=train)
+                    y = self._readout(x, plan)
         self.g = g
         return y, g
 
     def _forward_grad(self, plan, batch, ei, B, hidx, p):
-        from . import autograd as AG
         vN, _, vB, k1 = _bucket_rows(self)          # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-        x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        if self.pe_init == "lap_pe":
-            x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1), x, vN, k1)
-        else:
-            x = AG.mask_rows(x, vN, k1)
+        x = self._encode_grad(hidx, p, vN, k1)
         for conv in self.layers:
             mlp = conv.apply_func
             a = AG.gin_aggregate(x, conv.eps, plan, rplan)
@@ -432,15 +477,7 @@ class GINNet(_PackCache, nn.Module):
                 if mlp.use_bn and i < n - 1:
                     a = AG.bn_act(a, mlp.bns[i], vN, k1, relu=False)
             x = a
-        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
-        return hg
-
-    def loss(self, scores, targets):
-        """gin_net.py:141-143 (use_lapeig_loss = False): the L1 task loss (a torch reduction over B scalars)."""
-        return (scores - targets).abs().mean()
+        return self._readout_grad(x, plan, vB, k1)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -533,50 +570,30 @@ class _FusedGated:
         return y.view(-1, 1)
 
 
-class GatedGCNNet(_PackCache, nn.Module):
+class GatedGCNNet(_DGLNet):
     """nets/ZINC_graph_regression/gatedgcn_net.py:18-148 for pe_init = 'lap_pe', lap_lspe = False (the sign-invariant PE configs
     GatedGCN_ZINC_LapPE_signinv_GIN[_mask].json): embedding_h / embedding_p with `add` or `concat` + pe_proj (:93-103), edge
     embedding, L GatedGCN layers on sn_gated_aggregate_f32, mean / sum readout, MLPReadout.  Same constructor, forward contract
     `model(g, h, p, e, snorm_n) -> (scores, g)`, state_dict keys and attached `sign_inv_net` as the reference."""
 
+    fused_stages = True      # eval: layers + readout in ONE launch (sn_gatedgcn_fused_f32); False forces the layer path
+    _stage_cls, _stage_edges = _FusedGated, None
+    _malformed_note = "batch_num_nodes / edges do not describe a batched graph; "
+    _limit_text = "more in-edges than the one-launch kernel holds"
+
     def __init__(self, net_params):
         super().__init__()
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self.n_layers, self.readout, self.batch_norm = p["L"], p["readout"], p["batch_norm"]
-        self.residual, self.edge_feat, self.device = p["residual"], p["edge_feat"], p["device"]
-        self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
-        self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
-        self.pos_enc_dim, self.pe_aggregate = p["pos_enc_dim"], p["pe_aggregate"]
-        _check_pe_init("GatedGCNNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
-        if self.readout == "max" or not self.edge_feat or not self.batch_norm:
-            raise NotImplementedError("HIP GatedGCNNet: readout sum/mean, edge_feat=True, batch_norm=True")
-        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
-            raise NotImplementedError("HIP GatedGCNNet: dropout 0.0 (as in the shipped configs)")
-        if self.pe_init == "lap_pe":
-            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
-        self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
-        self.embedding_e = nn.Embedding(p["num_bond_type"], hidden)
+        self.pe_aggregate = p["pe_aggregate"]
+        self._init_common(p, "GatedGCNNet", [(p["readout"] == "max" or not p["edge_feat"] or not p["batch_norm"],
+                                              "readout sum/mean, edge_feat=True, batch_norm=True")])
         self.layers = nn.ModuleList([GatedGCNLayer(hidden, hidden, 0.0, True, residual=self.residual, graph_norm=False)
                                      for _ in range(self.n_layers - 1)] +
                                     [GatedGCNLayer(hidden, out_dim, 0.0, True, residual=self.residual, graph_norm=False)])
-        self.MLP_layer = MLPReadout(out_dim, 1)
-        self.g = None
-        if self.lap_method == "sign_inv":
-            self.sign_inv_net = get_sign_inv_net(net_params)
-        if self.pe_aggregate == "concat":
-            self.pe_proj = nn.Linear(2 * hidden, hidden)
+        self._init_tail(p)
 
-    _plan = GINNet._plan
-
-    def _encode(self, x, p):
-        """The input encoder of the value paths behind embedding_h (gatedgcn_net.py:93-103): NoPE leaves h alone."""
-        if self.pe_init != "lap_pe":
-            return x
-        if self.pe_aggregate == "concat":
-            pp = ops.masked_linear(p, self._pk(self.embedding_p))
-            return ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))               # (:96-99)
-        return ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                           # (:100-102)
+    _fused_gated = _DGLNet._stage        # (the name the topology tests ask by)
 
     def _forward_behind_side(self, g, h, p, e, fused):
         """The sign-invariant net ran in overlap mode (its event is on the graph): the input encoders (embeddings, PE projection) are
@@ -589,13 +606,7 @@ class GatedGCNNet(_PackCache, nn.Module):
             plan = cached_plan(g, N)
             hidx, eidx = h.long().reshape(N), e.long().reshape(-1)
             st5 = plan.status[5:6]
-            x = ops.embedding_sum(hidx, [self.embedding_h.weight], status=st5)
-            pf = p.contiguous().float()
-            if self.pe_aggregate == "concat":
-                pp = ops.masked_linear(pf, self._pk(self.embedding_p))
-                x = ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))
-            else:
-                x = ops.masked_linear(pf, self._pk(self.embedding_p), residual=x)
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight], status=st5), p.contiguous().float())
             ee = ops.embedding_sum(eidx, [self.embedding_e.weight], status=st5)
             ev2 = torch.cuda.Event()
             ev2.record(side)
@@ -609,71 +620,23 @@ class GatedGCNNet(_PackCache, nn.Module):
 
     def forward(self, g, h, p, e, snorm_n=None):
         if getattr(g, "_sn_side", None) is not None and p is not None and not self.training and self.pe_init == "lap_pe":
-            fz = self._fused_gated(g)
+            fz = self._stage(g)
             if fz is not None:
                 ops.require_cuda(h)
                 y = self._forward_behind_side(g, h, p, e, fz)
                 self.g = g
                 return y, g
-        _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
-        ops.require_cuda(h)
-        pe = self.pe_init == "lap_pe"
-        if pe and p is None:
-            raise NotImplementedError("HIP GatedGCNNet with pe_init='lap_pe' needs the positional encoding p")
-        N = h.shape[0]
-        hidx, eidx = h.long().reshape(N), e.long().reshape(-1)
-        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
-        train = self.training
-        if train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
+        eidx = e.long().reshape(-1)
+        if grad:
             batch, ei, B = self._plan(g, N)
             y = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, hidx, p, eidx)
         else:
             with torch.no_grad():
                 plan = cached_plan(g, N)
-                y = self._forward_value(plan, hidx, p, eidx, train, self._fused_gated(g))
+                y = self._forward_value(plan, hidx, p, eidx, train, self._stage(g))
         self.g = g
         return y, g
-
-    fused_stages = True      # eval: layers + readout in ONE launch (sn_gatedgcn_fused_f32); False forces the layer path
-
-    def _fused_gated(self, g):
-        """The packed stage-kernel parameters if this batch can take the one-launch path, else None."""
-        if self.training or not self.fused_stages:
-            return None
-        c = self.__dict__.setdefault("_cache", {})
-        if "fused_gated" not in c:
-            c["fused_gated"] = _FusedGated(self)
-        fz = c["fused_gated"]
-        if not fz.ok:
-            return None
-        # (a graph with more than 64 nodes, or more in-edges than the kernel's LDS image holds — sn_gatedgcn_max_edges(d), 176 at hidden
-        #  68 —, takes the layer path, as the reference evaluates any graph: both counts come with a DGL batch (batch_num_nodes(),
-        #  batch_num_edges()) and are read once per graph object.  A duck-typed graph without edge counts reaches the kernel, which
-        #  flags such a graph on the device — NaN score, check_last())
-        me = _max_in_edges(g)
-        return fz if 0 < _max_nodes(g) <= 64 and (me is None or me <= fz.max_edges) else None
-
-    def check_last(self):
-        """Raise what the last one-launch eval forward flagged on the device (its scores are NaN in that case): a node / edge type
-        outside the embedding tables (IndexError, as nn.Embedding) or a graph the stage kernel could not hold.  One host sync; also
-        run by train().  The layer-at-a-time path (fused_stages = False, train mode) raises immediately instead."""
-        plan, self._last_plan = getattr(self, "_last_plan", None), None
-        if plan is not None:
-            st = plan.status.tolist()
-            if st[3] or st[5]:
-                plan.status[3:6].zero_()         # (the plan is cached on the graph object: a later forward of the same graph starts clean)
-            if st[0]:
-                raise ValueError("GatedGCNNet: the last batch is malformed (batch_num_nodes / edges do not describe a batched graph; "
-                                 f"sn_batch_plan status {st[0]})")
-            if st[5]:
-                raise IndexError(ops.EMBEDDING_INDEX_ERROR)
-            if st[3] & 3:
-                raise RuntimeError("GatedGCNNet: a graph of the last batch has more than 64 nodes or more in-edges than the one-launch "
-                                   "kernel holds; its score is NaN — set fused_stages = False for such batches")
-
-    def train(self, mode=True):
-        self.check_last()
-        return super().train(mode)
 
     def _forward_value(self, plan, hidx, p, eidx, train, fused=None):
         if fused is not None:
@@ -706,25 +669,12 @@ class GatedGCNNet(_PackCache, nn.Module):
             x = ops.masked_affine(h2, scale=sc, shift=sf, relu=True, residual=x if L.residual else None)
             sc, sf = se.affine(e2, train)
             e = ops.masked_affine(e2, scale=sc, shift=sf, relu=True, residual=e if L.residual else None)
-        hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        for i, fc in enumerate(fcs):
-            hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
-        return hg
+        return self._readout(x, plan)
 
     def _forward_grad(self, plan, batch, ei, B, hidx, p, eidx):
-        from . import autograd as AG
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-        x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        if self.pe_init != "lap_pe":
-            x = AG.mask_rows(x, vN, k1)
-        else:
-            pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
-            if self.pe_aggregate == "concat":
-                x = AG.linear(torch.cat([x, pp], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
-            else:
-                x = AG.masked_add(pp, x, vN, k1)
+        x = self._encode_grad(hidx, p, vN, k1)
         e = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             Ah, Bh, Dh, Eh = (AG.linear(x, getattr(L, n).weight, getattr(L, n).bias, vN, k1) for n in "ABDE")
@@ -732,15 +682,7 @@ class GatedGCNNet(_PackCache, nn.Module):
             h2, e2 = AG.gated_aggregate(Ah, Bh, Dh, Eh, Ce, plan, rplan)
             x = AG.bn_act(h2, L.bn_node_h, vN, k1, relu=True, residual=x if L.residual else None)
             e = AG.bn_act(e2, L.bn_node_e, vE, k1, relu=True, residual=e if L.residual else None)
-        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
-        return hg
-
-    def loss(self, scores, targets):
-        """gatedgcn_net.py:150-152 (use_lapeig_loss = False): the L1 task loss."""
-        return (scores - targets).abs().mean()
+        return self._readout_grad(x, plan, vB, k1)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -785,88 +727,59 @@ class PNALayer(nn.Module):
         self.mixing_network_h = FCLayer(out_dim, out_dim, activation="LeakyReLU")
 
 
-class PNANet(_PackCache, nn.Module):
+class PNANet(_DGLNet):
     """nets/ZINC_graph_regression/pna_net.py:19-170 for the configuration PNA_ZINC_LapPE_signinv_GIN[_mask].json selects: pe_init
     'lap_pe', lap_lspe False, aggregators 'mean max min std', scalers 'identity amplification attenuation', towers with divided
     input, edge features, graph_norm + batch_norm, residual, no GRU, sum / mean readout.  Same constructor (`net_params`), forward
     contract `model(g, h, p, e, snorm_n) -> (scores, g)`, state_dict keys and attached `sign_inv_net`.  Per layer and tower:
     gather cat[h_src, h_dst, e] -> pretrans Linear -> sn_pna_aggregate_f32 -> posttrans Linear -> sn_pointwise_f32 (snorm_n and
     BatchNorm); then the mixing Linear + LeakyReLU + residual.  In eval mode the towers of a layer run side by side and the pretrans
-    gather is folded into the aggregation, on activations padded to 16-byte rows (sn_pna_aggregate_gather_f32, `_forward_eval_padded`).  Eval, train-mode value (batch-statistic BatchNorm, running statistics
-    updated) and — with gradients enabled — the differentiable path (`_forward_grad`)."""
+    gather is folded into the aggregation, on activations padded to 16-byte rows (sn_pna_aggregate_gather_f32,
+    `_forward_eval_padded`).  Eval, train-mode value (batch-statistic BatchNorm, running statistics updated) and — with gradients
+    enabled — the differentiable path (`_forward_grad`)."""
 
     fused_layers = True      # eval, padded layout: one edge-term Linear for all layers, LeakyReLU + residual as the mixing Linear's epilogue
-
 
     def __init__(self, net_params):
         super().__init__()
         p = net_params
-        hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self.n_layers, self.readout = p["L"], p["readout"]
-        self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
-        self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
-        self.pos_enc_dim, self.device = p["pos_enc_dim"], p["device"]
-        self.graph_norm, self.batch_norm, self.residual = p["graph_norm"], p["batch_norm"], p["residual"]
+        hidden, out_dim, edge_dim = p["hidden_dim"], p["out_dim"], p["edge_dim"]
+        self.graph_norm = p["graph_norm"]
         self.aggregators, self.scalers, self.avg_d, self.towers = p["aggregators"], p["scalers"], p["avg_d"], p["towers"]
-        self.edge_feat = p["edge_feat"]
-        _check_pe_init("PNANet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
-        if self.aggregators.split() != ["mean", "max", "min", "std"] or self.scalers.split() != ["identity", "amplification", "attenuation"]:
-            raise NotImplementedError("HIP PNANet: aggregators 'mean max min std', scalers 'identity amplification attenuation'")
-        if not (self.graph_norm and self.batch_norm and self.edge_feat) or p["gru"] or self.readout == "max":
-            raise NotImplementedError("HIP PNANet: graph_norm, batch_norm, edge_feat True; gru False; readout sum / mean")
-        if not (p["divide_input_first"] and p["divide_input_last"]):
-            raise NotImplementedError("HIP PNANet: divide_input_first / _last True (the shipped configs)")
-        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
-            raise NotImplementedError("HIP PNANet: dropout 0.0 (as in the shipped configs)")
-        edge_dim = p["edge_dim"]
-        if self.pe_init == "lap_pe":
-            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
-        self.in_feat_dropout = nn.Dropout(0.0)
-        self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
-        self.embedding_e = nn.Embedding(p["num_bond_type"], edge_dim)
+        self._init_common(p, "PNANet", [
+            (self.aggregators.split() != ["mean", "max", "min", "std"] or self.scalers.split() != ["identity", "amplification", "attenuation"],
+             "aggregators 'mean max min std', scalers 'identity amplification attenuation'"),
+            (not (self.graph_norm and p["batch_norm"] and p["edge_feat"]) or p["gru"] or p["readout"] == "max",
+             "graph_norm, batch_norm, edge_feat True; gru False; readout sum / mean"),
+            (not (p["divide_input_first"] and p["divide_input_last"]), "divide_input_first / _last True (the shipped configs)")],
+            edge_dim=edge_dim, in_feat_dropout="before_h")
         self.layers = nn.ModuleList([PNALayer(hidden, hidden, self.towers, edge_dim, self.residual) for _ in range(self.n_layers - 1)] +
                                     [PNALayer(hidden, out_dim, self.towers, edge_dim, self.residual)])
         if p["pretrans_layers"] != 1 or p["posttrans_layers"] != 1:
             raise NotImplementedError("HIP PNANet: pretrans_layers = posttrans_layers = 1")
-        self.MLP_layer = MLPReadout(out_dim, 1)
-        self.g = None
-        if self.lap_method == "sign_inv":
-            self.sign_inv_net = get_sign_inv_net(net_params)
-
-    _plan = GINNet._plan
+        self._init_tail(p)
 
     def forward(self, g, h, p, e, snorm_n):
-        _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
-        ops.require_cuda(h)
-        pe = self.pe_init == "lap_pe"
-        if (pe and p is None) or snorm_n is None:
+        if snorm_n is None or (p is None and self.pe_init == "lap_pe"):
             raise NotImplementedError("HIP PNANet needs snorm_n (graph_norm) and, with pe_init='lap_pe', the positional encoding p")
-        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
-        N = h.shape[0]
-        train = self.training
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
         avg_log = float(self.avg_d["log"])
         sn = snorm_n.reshape(N).contiguous().float()
-        grad = train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())
+        eidx = e.long().reshape(-1)
         if grad:
             batch, ei, B = self._plan(g, N)
-            plan = ops.build_plan(batch, ei, B, 0)
-            src, dst = ei[0], ei[1]
-        else:
-            plan = cached_plan(g, N)       # shared with the sign-invariant net: ONE sn_batch_plan per batch
-            src, dst = (t.long() for t in g.edges())
-        if grad:
-            hg = self._forward_grad(plan, batch, ei, B, h.long().reshape(N), p, e.long().reshape(-1), sn, avg_log)
+            hg = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, hidx, p, eidx, sn, avg_log)
             self.g = g
             return hg, g
+        plan = cached_plan(g, N)           # shared with the sign-invariant net: ONE sn_batch_plan per batch
         with torch.no_grad():
             if not train and self._pna_padded()["ok"]:
-                hg = self._forward_eval_padded(plan, h, p, e, sn, avg_log)
+                hg = self._forward_eval_padded(plan, hidx, p, eidx, sn, avg_log)
                 self.g = g
                 return hg, g
-            x = ops.embedding_sum(h.long().reshape(N), [self.embedding_h.weight])
-            if pe:
-                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                 # h + embedding_p(p)  (:124-126)
-            ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight])
+            src, dst = (t.long() for t in g.edges())
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)                              # h + embedding_p(p)  (:124-126)
+            ef = ops.embedding_sum(eidx, [self.embedding_e.weight])
             for L in self.layers:
                 it = L.in_dim // L.n_towers
                 outs = []
@@ -887,10 +800,7 @@ class PNANet(_PackCache, nn.Module):
                 hc = torch.cat(outs, dim=1)
                 mix = ops.masked_linear(hc, self._pk(L.mixing_network_h.linear))
                 x = ops.pointwise(mix, act="leaky", slope=0.01, residual=x if L.residual else None)                  # FCLayer LeakyReLU + residual
-            hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-            fcs = self.MLP_layer.FC_layers
-            for i, fc in enumerate(fcs):
-                hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
+            hg = self._readout(x, plan)
         self.g = g
         self._h_last = x
         return hg, g
@@ -911,9 +821,9 @@ class PNANet(_PackCache, nn.Module):
         a tower reads its own input channels; pna_layer.py:38-44 is a Linear over cat[h_src, h_dst, e] = W_s h_src + W_d h_dst + W_e e + b);
         e [Cin_p, edge_dim] + the pretrans biases; post_w [towers, ot_p, 13 it_p] — the towers' posttrans Linears as one grouped (block-diagonal) Linear over
         the tower-major output of the aggregation kernel; the towers' folded BatchNorms side by side (its epilogue, with snorm_n); the mixing Linear in the padded channel order."""
-        c = self.__dict__.setdefault("_cache", {})
-        if "pna_padded" in c:
-            return c["pna_padded"]
+        return self._cached("pna_padded", self._pad_pna)
+
+    def _pad_pna(self):
         dev = self.embedding_h.weight.device
         mk = lambda W_, b_: ops.PackedLinear(ops.pack_weight(W_.contiguous()), W_.shape[0], W_.shape[1], None if b_ is None else b_.contiguous())
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
@@ -971,18 +881,16 @@ class PNANet(_PackCache, nn.Module):
         W0 = z(fc0.weight.shape[0], layers[-1]["C_out"])
         W0[:, layers[-1]["pos_out"]] = fc0.weight.detach().float()
         P["fc0"] = mk(W0, fc0.bias.detach().float())
-        c["pna_padded"] = P
         return P
 
-    def _forward_eval_padded(self, plan, h, p, e, sn, avg_log):
+    def _forward_eval_padded(self, plan, hidx, p, eidx, sn, avg_log):
         """Eval forward on the padded layout (`_pna_padded`): all towers of a layer side by side, the pretrans gather folded into the
         aggregation (sn_pna_aggregate_gather_f32): 7 launches per layer instead of 9 per tower, every Linear on the vector kernels."""
         P = self._pna_padded()
-        N = h.shape[0]
-        x = ops.embedding_sum(h.long().reshape(N), [P["emb_h"]])
+        x = ops.embedding_sum(hidx, [P["emb_h"]])
         if "emb_p" in P:
             x = ops.masked_linear(p, P["emb_p"], residual=x)                                                     # h + embedding_p(p)  (:124-126)
-        ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight])
+        ef = ops.embedding_sum(eidx, [self.embedding_e.weight])
         fuse = self.fused_layers
         qe_all = ops.masked_linear(ef, P["e_all"]) if (fuse and P["e_all"] is not None) else None                # [E, L*C]
         for li, F in enumerate(P["layers"]):
@@ -1000,25 +908,15 @@ class PNANet(_PackCache, nn.Module):
                 mix = ops.masked_linear(hc, F["mix"])
                 x = ops.pointwise(mix, act="leaky", slope=0.01, residual=x if F["residual"] else None)           # FCLayer LeakyReLU + residual
         self._h_last = x.index_select(1, P["layers"][-1]["pos_out"])
-        hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        hg = ops.masked_linear(hg, P["fc0"], relu=len(fcs) > 1)
-        for i, fc in enumerate(fcs[1:], 1):
-            hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
-        return hg
+        return self._readout(x, plan, first=P["fc0"])
 
     def _forward_grad(self, plan, batch, ei, B, hidx, p, eidx, sn, avg_log):
         """Differentiable train-mode forward (SURVEY.md §8 f1 for this net): the same ops as autograd nodes with hand-written adjoints
         (csrc/dgl_layers.hip: CSR walks, no atomics); towers' column slices and concatenations are torch views / copies."""
-        from . import autograd as AG
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE: adjoint of h[src]
         src, dst = ei[0], ei[1]
-        if self.pe_init == "lap_pe":
-            x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1),
-                              AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
-        else:
-            x = AG.mask_rows(AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
+        x = self._encode_grad(hidx, p, vN, k1)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             it = L.in_dim // L.n_towers
@@ -1034,15 +932,8 @@ class PNANet(_PackCache, nn.Module):
             mixl = L.mixing_network_h.linear
             mix = AG.linear(torch.cat(outs, dim=1), mixl.weight, mixl.bias, vN, k1)
             x = AG.act_residual(mix, residual=x if L.residual else None, act="leaky", slope=0.01)
-        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         self._h_last = x.detach()
-        return hg
-
-    def loss(self, scores, targets):
-        return (scores - targets).abs().mean()
+        return self._readout_grad(x, plan, vB, k1)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1085,7 +976,6 @@ class _FusedTransformer:
 
     def __init__(self, net):
         from .fused import _GnnParams, GNN_MAX_LAYERS
-        from .dgl_deepsigns import _pad_mat
         self.ok = False
         Ls, fcs = list(net.layers), list(net.MLP_layer.FC_layers)
         nope = net.pe_init != "lap_pe"       # NoPE: a zero projection of a one-column zero encoding (h = embedding_h(h) + 0)
@@ -1154,65 +1044,31 @@ class _FusedTransformer:
         return y
 
 
-class TransformerNet(_PackCache, nn.Module):
+class TransformerNet(_DGLNet):
     """nets/ZINC_graph_regression/transformer_net.py:21-150 for pe_init 'lap_pe', lap_lspe False, edge_feat True, full_graph False
     (Transformer_ZINC_LapPE_signinv_GIN[_masked].json): embedding_h / embedding_p with `add` or `concat` + pe_proj, edge
     embedding, L x [Q/K/V/E projections -> sn_edge_attention_f32 -> O_h + residual -> BatchNorm -> FFN + residual -> BatchNorm],
     sum / mean readout, MLPReadout.  Same constructor, forward contract, state_dict keys and attached `sign_inv_net`.
     Eval, train-mode value and — with gradients enabled — the differentiable path (`_forward_grad`)."""
 
+    fused_layers = True      # eval: fused projections / epilogues (False: one launch per op, as the train-mode value path)
+    fused_stages = True      # eval, the shipped shape: everything behind the E projection in ONE launch (sn_transformer_net_fused_f32)
+    _stage_cls = _FusedTransformer
+
     def __init__(self, net_params):
         super().__init__()
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self.n_layers, self.readout, self.batch_norm, self.layer_norm = p["L"], p["readout"], p["batch_norm"], p["layer_norm"]
-        self.residual, self.edge_feat, self.device = p["residual"], p["edge_feat"], p["device"]
-        self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
-        self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
-        self.pos_enc_dim, self.pe_aggregate = p["pos_enc_dim"], p["pe_aggregate"]
-        _check_pe_init("TransformerNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
-        if self.readout == "max" or not self.edge_feat:
-            raise NotImplementedError("HIP TransformerNet: readout sum / mean, edge_feat True")
-        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
-            raise NotImplementedError("HIP TransformerNet: dropout 0.0 (as in the shipped configs)")
-        if self.pe_init == "lap_pe":
-            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
-        self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
-        self.embedding_e = nn.Embedding(p["num_bond_type"], hidden)
-        self.in_feat_dropout = nn.Dropout(0.0)
+        self.layer_norm, self.pe_aggregate = p["layer_norm"], p["pe_aggregate"]
+        self._init_common(p, "TransformerNet", [(p["readout"] == "max" or not p["edge_feat"], "readout sum / mean, edge_feat True")],
+                          in_feat_dropout="after_e")
         self.layers = nn.ModuleList([BatchedTransformerLayer(hidden, hidden, p["n_heads"], p["full_graph"], use_edge=True)
                                      for _ in range(self.n_layers - 1)] +
                                     [BatchedTransformerLayer(hidden, out_dim, p["n_heads"], p["full_graph"], use_edge=True)])
-        self.MLP_layer = MLPReadout(out_dim, 1)
-        self.g = None
-        if self.lap_method == "sign_inv":
-            self.sign_inv_net = get_sign_inv_net(net_params)
-        if self.pe_aggregate == "concat":
-            self.pe_proj = nn.Linear(2 * hidden, hidden)
+        self._init_tail(p)
 
-    _plan = GINNet._plan
-
-    fused_layers = True      # eval: fused projections / epilogues (False: one launch per op, as the train-mode value path)
-    fused_stages = True      # eval, the shipped shape: everything behind the E projection in ONE launch (sn_transformer_net_fused_f32)
-
-    def _fused_tf(self, g):
-        """The packed stage-kernel parameters if this batch can take the one-launch path, else None (see GINNet._fused_gin)."""
-        if self.training or not self.fused_stages or not self._fusable():
-            return None
-        c = self.__dict__.setdefault("_cache", {})
-        if "fused_tf" not in c:
-            c["fused_tf"] = _FusedTransformer(self)
-        fz = c["fused_tf"]
-        if not fz.ok:
-            return None
-        me = _max_in_edges(g)
-        return fz if 0 < _max_nodes(g) <= 64 and (me is None or me <= 192) else None
-
-    check_last = GINNet.check_last
-
-    def train(self, mode=True):
-        self.check_last()
-        return super().train(mode)
+    def _stage(self, g):
+        return super()._stage(g) if self._fusable() else None          # (the kernel reads the stacked E projections of `_fused_eval`)
 
     def _fusable(self):
         """Every layer maps hidden -> hidden (the shipped configs: out_dim == hidden_dim), so that the layers' E projections stack."""
@@ -1221,14 +1077,12 @@ class TransformerNet(_PackCache, nn.Module):
 
     def _fused_eval(self):
         """Eval cache: cat[W_Q; W_K; W_V] per layer and cat over the layers of W_E, packed (no biases: use_bias False)."""
-        c = self.__dict__.setdefault("_cache", {})
-        if "fused" not in c:
-            def pack(ws):
-                W = torch.cat([w.detach().float() for w in ws], 0).contiguous()
-                return ops.PackedLinear(ops.pack_weight(W), W.shape[0], W.shape[1], None)
-            c["fused"] = {"qkv": [pack([L.attention_h.Q.weight, L.attention_h.K.weight, L.attention_h.V.weight]) for L in self.layers],
-                          "E": pack([L.attention_h.E.weight for L in self.layers])}
-        return c["fused"]
+        def pack(ws):
+            W = torch.cat([w.detach().float() for w in ws], 0).contiguous()
+            return ops.PackedLinear(ops.pack_weight(W), W.shape[0], W.shape[1], None)
+        return self._cached("fused", lambda: {
+            "qkv": [pack([L.attention_h.Q.weight, L.attention_h.K.weight, L.attention_h.V.weight]) for L in self.layers],
+            "E": pack([L.attention_h.E.weight for L in self.layers])})
 
     def _bn_res(self, y, res, bn, train):
         """BatchNorm1d(res + y): eval folded into one pointwise pass; train: batch statistics of the sum."""
@@ -1241,40 +1095,26 @@ class TransformerNet(_PackCache, nn.Module):
         return ops.pointwise(s, scale=sc, shift=sh)
 
     def forward(self, g, h, p, e, snorm_n=None):
-        _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
-        ops.require_cuda(h)
-        pe = self.pe_init == "lap_pe"
-        if pe and p is None:
-            raise NotImplementedError("HIP TransformerNet with pe_init='lap_pe' needs the positional encoding p")
-        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
-        N = h.shape[0]
-        train = self.training
-        if train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
+        eidx = e.long().reshape(-1)
+        if grad:
             batch, ei, B = self._plan(g, N)
-            plan = ops.build_plan(batch, ei, B, 0)
-            hg = self._forward_grad(plan, batch, ei, B, h.long().reshape(N), p, e.long().reshape(-1))
+            hg = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, hidx, p, eidx)
             self.g = g
             return hg, g
         plan = cached_plan(g, N)           # shared with the sign-invariant net: ONE sn_batch_plan per batch
         with torch.no_grad():
-            fzs = self._fused_tf(g)
+            fzs = self._stage(g)
             if fzs is not None:
                 # no host sync on this path: a bad atom type / an oversize graph -> NaN score + check_last(); a bond type outside its table
                 # is flagged in the plan's status block by the embedding (status[5]) and raised by check_last() as well
-                ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight], status=plan.status[5:6])
+                ef = ops.embedding_sum(eidx, [self.embedding_e.weight], status=plan.status[5:6])
                 Ee_all = ops.masked_linear(ef, self._fused_eval()["E"])
                 self._last_plan = plan
                 self.g = g
-                return fzs.run(plan, h.long().reshape(N).contiguous(), p if pe else _zero_pe(self, N, h.device)[:N], Ee_all), g
-            x = ops.embedding_sum(h.long().reshape(N), [self.embedding_h.weight])
-            if not pe:
-                pass                                                                                                  # NoPE: h alone
-            elif self.pe_aggregate == "concat":
-                pq = ops.masked_linear(p, self._pk(self.embedding_p))
-                x = ops.masked_linear(torch.cat([x, pq], dim=1), self._pk(self.pe_proj))                              # (:96-99)
-            else:
-                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                      # (:101-102)
-            ef = ops.embedding_sum(e.long().reshape(-1), [self.embedding_e.weight])
+                return fzs.run(plan, hidx.contiguous(), p if pe else _zero_pe(self, N, h.device)[:N], Ee_all), g
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)                                   # (:96-102)
+            ef = ops.embedding_sum(eidx, [self.embedding_e.weight])
             if not train and self._fusable():
                 # eval (round 4): 5 launches per layer instead of 12.  Q | K | V are ONE [3d, d] Linear whose column blocks the attention
                 # reads in place; every layer's E projection of the (layer-independent) edge embedding is one [L*d, d] Linear up front;
@@ -1290,19 +1130,16 @@ class TransformerNet(_PackCache, nn.Module):
                     f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
                     x = ops.masked_linear(f, self._pk(L.FFN_h_layer2), residual=x1, residual_pre=True, scale=s2.scale, shift=s2.shift)  # (:300-308)
             else:
-              for L in self.layers:
-                A = L.attention_h
-                Q, K, V = (ops.masked_linear(x, self._pk(getattr(A, n))) for n in "QKV")
-                Ee = ops.masked_linear(ef, self._pk(A.E))
-                a = ops.edge_attention(Q, K, V, Ee, plan, L.num_heads)                                                # (:150-228)
-                o = ops.masked_linear(a, self._pk(L.O_h))
-                x1 = self._bn_res(o, x, L.batch_norm1_h, train)                                                       # residual, BatchNorm (:283-290)
-                f = ops.masked_linear(ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True), self._pk(L.FFN_h_layer2))
-                x = self._bn_res(f, x1, L.batch_norm2_h, train)                                                       # (:300-308)
-            hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-            fcs = self.MLP_layer.FC_layers
-            for i, fc in enumerate(fcs):
-                hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
+                for L in self.layers:
+                    A = L.attention_h
+                    Q, K, V = (ops.masked_linear(x, self._pk(getattr(A, n))) for n in "QKV")
+                    Ee = ops.masked_linear(ef, self._pk(A.E))
+                    a = ops.edge_attention(Q, K, V, Ee, plan, L.num_heads)                                            # (:150-228)
+                    o = ops.masked_linear(a, self._pk(L.O_h))
+                    x1 = self._bn_res(o, x, L.batch_norm1_h, train)                                                   # residual, BatchNorm (:283-290)
+                    f = ops.masked_linear(ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True), self._pk(L.FFN_h_layer2))
+                    x = self._bn_res(f, x1, L.batch_norm2_h, train)                                                   # (:300-308)
+            hg = self._readout(x, plan)
         self.g = g
         self._h_last = x
         return hg, g
@@ -1310,18 +1147,9 @@ class TransformerNet(_PackCache, nn.Module):
     def _forward_grad(self, plan, batch, ei, B, hidx, p, eidx):
         """Differentiable train-mode forward: the sparse attention's adjoint is sn_edge_attention_bwd_f32 (destination pass + source
         pass over the reverse CSR, no atomics); BatchNorm with batch statistics, residuals, FFN as in the value path."""
-        from . import autograd as AG
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-        x = AG.embedding_sum(hidx, [self.embedding_h.weight])
-        if self.pe_init != "lap_pe":
-            x = AG.mask_rows(x, vN, k1)
-        else:
-            pe = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
-            if self.pe_aggregate == "concat":
-                x = AG.linear(torch.cat([x, pe], dim=1), self.pe_proj.weight, self.pe_proj.bias, vN, k1)
-            else:
-                x = AG.masked_add(pe, x, vN, k1)
+        x = self._encode_grad(hidx, p, vN, k1)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
         for L in self.layers:
             A = L.attention_h
@@ -1333,15 +1161,8 @@ class TransformerNet(_PackCache, nn.Module):
             f = AG.linear(AG.linear(x1, L.FFN_h_layer1.weight, L.FFN_h_layer1.bias, vN, k1, relu=True), L.FFN_h_layer2.weight,
                           L.FFN_h_layer2.bias, vN, k1)
             x = AG.bn_act(AG.masked_add(f, x1, vN, k1), L.batch_norm2_h, vN, k1, relu=False)
-        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         self._h_last = x.detach()
-        return hg
-
-    def loss(self, scores, targets):
-        return (scores - targets).abs().mean()
+        return self._readout_grad(x, plan, vB, k1)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1366,7 +1187,7 @@ class GATConv(nn.Module):
         nn.init.xavier_normal_(self.attn_r, gain=gain)
 
 
-class GATNet(_PackCache, nn.Module):
+class GATNet(_DGLNet):
     """nets/ZINC_graph_regression/gat_net.py:19-148 for pe_init = 'lap_pe', lap_lspe = False (GAT_ZINC_LapPE_signinv_GIN.json):
     h = embedding_h(h) + embedding_p(p), L GATConv(ReLU) layers — the first L-1 with their heads flattened, the last averaged over the
     heads (:108-110) — mean / sum readout, MLPReadout.  'GAT (no edge feature)': the edge embedding is a parameter of the
@@ -1378,50 +1199,27 @@ class GATNet(_PackCache, nn.Module):
         super().__init__()
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self.n_layers, self.readout, self.n_heads = p["L"], p["readout"], p["n_heads"]
-        self.pe_init, self.lap_method, self.lap_lspe = p["pe_init"], p["lap_method"], p["lap_lspe"]
-        self.use_lapeig_loss, self.lambda_loss, self.alpha_loss = p["use_lapeig_loss"], p["lambda_loss"], p["alpha_loss"]
-        self.pos_enc_dim, self.device, self.edge_feat = p["pos_enc_dim"], p["device"], p["edge_feat"]
-        self.batch_norm, self.residual = p["batch_norm"], p["residual"]              # read and ignored by the reference too
-        _check_pe_init("GATNet", self.pe_init, self.lap_lspe, self.use_lapeig_loss)
-        if self.readout == "max":
-            raise NotImplementedError("HIP GATNet: readout sum / mean")
-        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
-            raise NotImplementedError("HIP GATNet: dropout 0.0 (as in the shipped configs)")
+        H = self.n_heads = p["n_heads"]
+        self._init_common(p, "GATNet", [(p["readout"] == "max", "readout sum / mean")], in_feat_dropout="after_e")
+        #                     (batch_norm, residual: read and ignored by the reference too)
         if self.n_layers < 2:
             raise ValueError("GATNet: L >= 2 (gat_net.py:62-66 always builds a first and a last layer)")
-        H = self.n_heads
-        if self.pe_init == "lap_pe":
-            self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
-        self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
-        self.embedding_e = nn.Embedding(p["num_bond_type"], hidden) if self.edge_feat else nn.Linear(1, hidden)
-        self.in_feat_dropout = nn.Dropout(0.0)
         self.layers = nn.ModuleList([GATConv(hidden, hidden, H)] + [GATConv(H * hidden, hidden, H) for _ in range(1, self.n_layers - 1)] +
                                     [GATConv(H * hidden, out_dim, H)])
-        self.MLP_layer = MLPReadout(out_dim, 1)
-        self.g = None
-        if self.lap_method == "sign_inv":
-            self.sign_inv_net = get_sign_inv_net(net_params)
+        self._init_tail(p)
 
     def forward(self, g, h, p, e, snorm_n=None):
-        _await_side(g)          # a sign_inv_net in overlap mode hands p over with an event kept on the graph
-        ops.require_cuda(h)
-        pe = self.pe_init == "lap_pe"
-        if pe and p is None:
-            raise NotImplementedError("HIP GATNet with pe_init='lap_pe' needs the positional encoding p")
-        p = p.contiguous().float() if pe else None           # (NoPE: p is not read, as in the reference)
-        N = h.shape[0]
-        if self.training and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
+        if grad:
             batch, ei, B = self._plan(g, N)
-            hg = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, h.long().reshape(N), p)
+            hg = self._forward_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, hidx, p)
             self.g = g
             return hg, g
         plan = cached_plan(g, N)
         with torch.no_grad():
             zero_deg = (plan.rowptr[1:] == plan.rowptr[:-1]).any()
-            x = ops.embedding_sum(h.long().reshape(N), [self.embedding_h.weight])     # raises IndexError as nn.Embedding (one host read)
-            if pe:
-                x = ops.masked_linear(p, self._pk(self.embedding_p), residual=x)                                 # h + embedding_p(p)  (:97-99)
+            x = ops.embedding_sum(hidx, [self.embedding_h.weight])                    # raises IndexError as nn.Embedding (one host read)
+            x = self._encode(x, p)                                                                               # h + embedding_p(p)  (:97-99)
             H = self.n_heads
             for i, L in enumerate(self.layers):
                 f = ops.masked_linear(x, self._fc(L))
@@ -1429,10 +1227,7 @@ class GATNet(_PackCache, nn.Module):
             # the last layer's heads are averaged (:110): sum over the head axis, then 1/H
             x = ops.slot_sum(x.view(N * H, -1), N, H)
             x = ops.pointwise(x, scale=self._const(1.0 / H, x.shape[1]), shift=self._const(0.0, x.shape[1]))
-            hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-            fcs = self.MLP_layer.FC_layers
-            for i, fc in enumerate(fcs):
-                hg = ops.masked_linear(hg, self._pk(fc), relu=i < len(fcs) - 1)
+            hg = self._readout(x, plan)
         zero_msg = ("There are 0-in-degree nodes in the graph: GATConv's edge softmax is undefined for them (DGL raises "
                     "DGLError here unless allow_zero_in_degree is set, which gat_net.py:62-66 leaves at False)")
         if ops.deferring():              # a recorded step (serving.GraphedDGLForward) must not wait for the host: its check() reads these
@@ -1446,12 +1241,9 @@ class GATNet(_PackCache, nn.Module):
         self._h_last = x
         return hg, g
 
-    _plan = GINNet._plan
-
     def _forward_grad(self, plan, batch, ei, B, hidx, p):
         """Differentiable train-mode forward (SURVEY.md §8 f1 for this net): the same ops as autograd nodes; the GATConv adjoint is
         sn_gat_aggregate_bwd_f32 (CSR walks over the in-edges, then over the out-edges; no atomics)."""
-        from . import autograd as AG
         vN, _, vB, k1 = _bucket_rows(self)          # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
 
         def zero_deg():
@@ -1469,38 +1261,20 @@ class GATNet(_PackCache, nn.Module):
                 raise ValueError(zero_msg)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE
         N, H = hidx.shape[0], self.n_heads
-        if self.pe_init == "lap_pe":
-            x = AG.masked_add(AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1),
-                              AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
-        else:
-            x = AG.mask_rows(AG.embedding_sum(hidx, [self.embedding_h.weight]), vN, k1)
+        x = self._encode_grad(hidx, p, vN, k1)
         for L in self.layers:
             x = AG.gat_aggregate(AG.linear(x, L.fc.weight, None, vN, k1), L.attn_l, L.attn_r, L.bias, plan, rplan, H, L.negative_slope, True)
         x = AG.slot_sum(x.view(N * H, -1), N, H)                               # mean over the heads (:110)
         x = AG.act_residual(x, rowscale=torch.full((N,), 1.0 / H, dtype=torch.float32, device=x.device))
-        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
-        fcs = self.MLP_layer.FC_layers
-        for i, fc in enumerate(fcs):
-            hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
         self._h_last = x.detach()
-        return hg
+        return self._readout_grad(x, plan, vB, k1)
 
     def _fc(self, L):
-        c = self.__dict__.setdefault("_cache", {})
-        if self.training or ("fc", id(L)) not in c:
+        def build():
             w = L.fc.weight.detach()
-            pl = ops.PackedLinear(ops.pack_weight(w), w.shape[0], w.shape[1], None)
-            if self.training:
-                return pl
-            c[("fc", id(L))] = pl
-        return c[("fc", id(L))]
+            return ops.PackedLinear(ops.pack_weight(w), w.shape[0], w.shape[1], None)
+        return build() if self.training else self._cached(("fc", id(L)), build)
 
     def _const(self, v, n):
-        c = self.__dict__.setdefault("_cache", {})
-        key = ("const", float(v), int(n))
-        if key not in c:
-            c[key] = torch.full((n,), float(v), dtype=torch.float32, device=self.embedding_h.weight.device)
-        return c[key]
-
-    def loss(self, scores, targets):
-        return (scores - targets).abs().mean()
+        return self._cached(("const", float(v), int(n)),
+                            lambda: torch.full((n,), float(v), dtype=torch.float32, device=self.embedding_h.weight.device))
