@@ -201,10 +201,13 @@ class RhoPlan:
             Lp.ln2_g, Lp.ln2_b = hold(vpad(f.norm.ln.weight)), hold(vpad(f.norm.ln.bias))
         return P
 
-    def run(self, plan: ops.GraphPlan, x, eigen_values, K: int, precision=0):
+    def run(self, plan: ops.GraphPlan, x, eigen_values, K: int, precision=0, out=None):
         """x [N*K, d] -> sum over valid slots of the encoder output, [N, d].  precision: SN_PREC_* of the six [d, d] projections
-        of every layer (PRECISIONS)."""
-        out = torch.empty(plan.N, self.d, dtype=torch.float32, device=x.device)
+        of every layer (PRECISIONS).  out: optional contiguous float32 [N, d] buffer to write (default: a fresh one)."""
+        if out is None:
+            out = torch.empty(plan.N, self.d, dtype=torch.float32, device=x.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (plan.N, self.d) or out.device != x.device:
+            raise ValueError(f"fused rho: out must be a contiguous float32 [{plan.N}, {self.d}] tensor on {x.device}")
         kcap = min(plan.kmax, K) if plan.kmax > 0 else K
         params = self.params_hp if (self.params_hp is not None and kcap <= 16) else self.params
         with ops._span("sn_rho_fused_f32"):
@@ -331,10 +334,11 @@ class GnnPlan:
             return None
         return (self.params, x2.contiguous(), e2.contiguous(), self._front_bytes)
 
-    def run(self, plan: ops.GraphPlan, x, edge_attr, rho_sum, flags_host=None):
+    def run(self, plan: ops.GraphPlan, x, edge_attr, rho_sum, flags_host=None, out=None):
         """-> model output [B, n_out] (graphs with more than 64 nodes set plan.status[3]).  flags_host: optional pinned
         int32 host tensor (>= plan.flags.numel()) that the kernel's last workgroup fills with plan.flags.  A plan built with this
-        stage's front records (plan.front) runs the entry point that starts from them."""
+        stage's front records (plan.front) runs the entry point that starts from them.  out: optional contiguous float32 [B, n_out]
+        buffer to write (default: a fresh one)."""
         P = self.params
         if self.node_discrete:
             if x.dtype != torch.int64:
@@ -356,7 +360,12 @@ class GnnPlan:
             edge_attr = torch.zeros(1, max(1, int(P.edge_nf)), dtype=edge_attr.dtype, device=rho_sum.device)
         if P.node_nf > (10 if self.node_discrete else 16) or P.edge_nf > (10 if self.edge_discrete else 16):
             raise ValueError("too many feature columns for the fused gnn kernel")
-        y = torch.empty(plan.B, self.n_out, dtype=torch.float32, device=rho_sum.device)
+        if out is None:
+            y = torch.empty(plan.B, self.n_out, dtype=torch.float32, device=rho_sum.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (plan.B, self.n_out) or out.device != rho_sum.device:
+            raise ValueError(f"fused gnn: out must be a contiguous float32 [{plan.B}, {self.n_out}] tensor on {rho_sum.device}")
+        else:
+            y = out
         if plan.front is not None and P.node_nf == 1 and P.edge_nf == 1:
             with ops._span("sn_gnn_fused_f32"):
                 check(lib().sn_gnn_fused_front_f32(C.byref(P), ptr(x), x.shape[1], ptr(edge_attr),
