@@ -1214,6 +1214,41 @@ int sn_graph_attention_bwd_f32(const float* q, const float* k, const float* v, i
                                const float* lse, const float* dout, int64_t lddo, const int32_t* graph_ptr, int64_t N, int64_t B,
                                int S, int heads, int dh, float* dq, float* dk, float* dv, int64_t ldg, float* delta, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * torch_geometric's GATConv(in, out, heads, concat=True, dropout=0) on ONE fixed graph, behind its Linear, with the activation that
+ * follows it (LearningFilters/models.py:261-263 builds the layers, :269-270 `x = F.elu(conv(x, edge_index))`), restated from the
+ * library's documented definition.
+ *   feat [N, heads*C]: the layer's Linear output; att_l, att_r, bias (may be NULL): [heads*C]; rowptr / col (nnz entries): the CSR by
+ *   destination of the edge list with the input self loops already dropped and multi-edges kept.  For node i and head h the attention
+ *   set is the CSR in-edges of i in stored order, then i itself (the one self loop PyG gives every node is implicit):
+ *     e_ij = leaky_relu(feat_j . att_l[h] + feat_i . att_r[h], negative_slope),  a = softmax over the set,
+ *     out[i,h,:] = act(sum_j a_ij feat[j,h,:] + bias[h,:]),  act SN_GAT_ACT_NONE or SN_GAT_ACT_ELU (alpha 1, expm1f below 0),
+ *     lse[i,h] = the set's log-sum-exp (for the adjoint).  A node without in-edges returns act(feat_i + bias).
+ *   Online softmax with logits and running maximum in double: any in-degree, any N, logits of any magnitude.  heads <= 16 and C <= 128
+ *   (sn_gat_conv_max_heads / _max_channels; the adjoint keeps 3 * heads * C doubles of parameter partials in LDS, a lane at most two
+ *   channels): beyond, SN_ERR_UNSUPPORTED; act outside {0, 1} or a size < 1: SN_ERR_ARG; both before any launch.  A group of
+ *   sn_gat_conv_group_width(C) = min(64, pow2 >= C) lanes owns one (node, head); there is no in-degree threshold.
+ * sn_gat_conv_bwd_f32: the adjoint in two launches.  rowptr_t / col_t: the CSR of the FLIPPED edge list (the same nnz entries).
+ *   dz = dout * act'(out) is formed on load (ELU: 1 where out > 0, else out + 1); the probabilities are recomputed from lse, nothing
+ *   of size E is kept.  Writes dfeat [N, heads*C] and part [sn_gat_conv_bwd_blocks(N, heads, C), 3 * heads*C]: per-workgroup partials
+ *   of d att_l | d att_r | d bias, summed in block order by sn_train_reduce_parts_f32(part, blocks, 3*heads*C, 3*heads*C, out, ...).
+ *   work: scratch of 5 * N * heads doubles.
+ * One owner per output element, sums in a fixed order, no atomics: bit-reproducible.  Entries of col outside [0, N) are skipped and
+ * rowptr is clamped to [0, nnz]. */
+#define SN_GAT_ACT_NONE 0
+#define SN_GAT_ACT_ELU 1
+int sn_gat_conv_max_heads(void);
+int sn_gat_conv_max_channels(void);
+int sn_gat_conv_group_width(int C);
+int sn_gat_conv_bwd_blocks(int64_t N, int heads, int C);
+int sn_gat_conv_f32(const float* feat, const float* att_l, const float* att_r, const float* bias, int64_t N, int heads, int C,
+                    float negative_slope, int act, const int32_t* rowptr, const int32_t* col, int64_t nnz, float* out, float* lse,
+                    void* stream);
+int sn_gat_conv_bwd_f32(const float* feat, const float* att_l, const float* att_r, const float* out, const float* lse,
+                        const float* dout, int64_t N, int heads, int C, float negative_slope, int act, const int32_t* rowptr,
+                        const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t, int64_t nnz, float* dfeat, float* part,
+                        double* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,12 @@ SIGNATURES = {
     "sn_gcn_propagate_f32": [_p, _l, _l, _i, _p, _p, _p, _p, _i, _p, _l, _p],
     "sn_graph_attention_f32": [_p, _p, _p, _l, _p, _l, _l, _i, _i, _i, _p, _l, _p, _p],
     "sn_graph_attention_bwd_f32": [_p, _p, _p, _l, _p, _l, _p, _p, _l, _p, _l, _l, _i, _i, _i, _p, _p, _p, _l, _p, _p],
+    "sn_gat_conv_max_heads": [],                         # (the four below return a limit / width / count, not a status)
+    "sn_gat_conv_max_channels": [],
+    "sn_gat_conv_group_width": [_i],
+    "sn_gat_conv_bwd_blocks": [_l, _i, _i],
+    "sn_gat_conv_f32": [_p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _l, _p, _p, _p],
+    "sn_gat_conv_bwd_f32": [_p, _p, _p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _p, _p, _l, _p, _p, _p, _p],
 }
 _SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64,
                     "sn_gnn_front_bytes": C.c_int64}

@@ -955,3 +955,34 @@ class _GraphAttention(Function):
 def graph_attention(qkv, graph_ptr, N, S, heads):
     """softmax(q k^T / sqrt(dh)) v per head over the nodes of each graph, independently per slot (rows node * S + slot)."""
     return _GraphAttention.apply(qkv, graph_ptr, N, S, heads)
+
+
+# ----------------------------------------------------------------------------- PyG's GATConv on one fixed graph (csrc/filter_attention.hip)
+class _GatConv(Function):
+    """ops.gat_conv: attention over every node's in-edges and its own loop, bias and the activation in the same launch.  The backward is
+    ops.gat_conv_bwd — two launches that recompute the probabilities from the saved log-sum-exp, and the block-order reduction of the
+    d att_l | d att_r | d bias partials."""
+
+    @staticmethod
+    def forward(ctx, feat, att_l, att_r, bias, op, heads, act, negative_slope):
+        feat = _c(feat.detach())
+        al, ar = _c(att_l.detach()).reshape(-1), _c(att_r.detach()).reshape(-1)
+        out, lse = ops.gat_conv(feat, al, ar, None if bias is None else _c(bias.detach()), op, heads, act, negative_slope)
+        ctx.save_for_backward(feat, al, ar, out, lse)
+        ctx.meta = (op, heads, act, negative_slope, att_l.shape, att_r.shape, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        feat, al, ar, out, lse = ctx.saved_tensors
+        op, heads, act, negative_slope, sl, sr, has_b = ctx.meta
+        dfeat, dl, dr, db = ops.gat_conv_bwd(feat, al, ar, out, lse, _c(g), op, heads, act, negative_slope)
+        return dfeat, dl.view(sl), dr.view(sr), (db if has_b else None), None, None, None, None
+
+
+def gat_conv(feat, att_l, att_r, bias, graph, heads, act="elu", negative_slope=0.2):
+    """act(softmax-attention over in-edges and the implicit self loop + bias): torch_geometric's GATConv behind its Linear.  graph: a
+    filter_baselines.FilterGraph (its `lap` pattern is the edge list without the input self loops) or an ops.SparseOperator with `.t`.
+    Gradients for feat, att_l, att_r and bias."""
+    op = getattr(graph, "lap", graph)
+    return _GatConv.apply(feat, att_l, att_r, bias, op, heads, act, negative_slope)

@@ -67,6 +67,26 @@ BASELINE_OVERRIDES = {
     "learningfilters": {"models": _PKG + ".baseline_filter_models"},
 }
 
+# Opt-in with `baselines="all"` (the runner's `--baselines=all`), on top of everything baselines=True binds: the module that answers the
+# name INSTEAD of BASELINE_OVERRIDES' one.  For LearningFilters it adds GatNet and ARMANet, the last two nets of training.py's --net.
+ALL_BASELINE_OVERRIDES = {
+    "learningfilters": {"models": _PKG + ".all_baseline_filter_models"},
+}
+
+
+def _baseline_table(tree: str, baselines) -> dict:
+    """What `baselines` (False, True or "all") adds to ALIASES[tree]."""
+    if baselines not in (False, True, "all"):
+        raise ValueError(f"baselines must be False, True or 'all', got {baselines!r}")
+    table = {}
+    if baselines:
+        table.update(BASELINE_ALIASES.get(tree, {}))
+        table.update(BASELINE_OVERRIDES.get(tree, {}))
+    if baselines == "all":
+        table.update(ALL_BASELINE_OVERRIDES.get(tree, {}))
+    return table
+
+
 # entry script (basename) -> tree, for the runner
 SCRIPTS = {
     "main_alchemy.py": "alchemy",
@@ -102,12 +122,10 @@ class _AliasLoader(importlib.abc.Loader):
 class AliasFinder(importlib.abc.MetaPathFinder):
     """Answers the names of `ALIASES[tree]` and nothing else; every other import goes on to the normal finders."""
 
-    def __init__(self, tree: str, baselines: bool = False):
+    def __init__(self, tree: str, baselines=False):
         self.tree = tree
         self.table = dict(ALIASES[tree])
-        if baselines:
-            self.table.update(BASELINE_ALIASES.get(tree, {}))
-            self.table.update(BASELINE_OVERRIDES.get(tree, {}))
+        self.table.update(_baseline_table(tree, baselines))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -116,18 +134,22 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         return importlib.machinery.ModuleSpec(fullname, _AliasLoader(impl), origin=impl)
 
 
-def install(tree: str, baselines: bool = False) -> AliasFinder:
+def install(tree: str, baselines=False) -> AliasFinder:
     """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
     `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN) and rebinds those of `BASELINE_OVERRIDES[tree]` (LearningFilters' `models`, with
-    the four polynomial-filter baselines); a finder installed without them is extended in place."""
+    the four polynomial-filter baselines); baselines="all" rebinds those of `ALL_BASELINE_OVERRIDES[tree]` on top (LearningFilters'
+    `models` with GatNet and ARMANet too); a finder installed with less is extended in place."""
     shim_dir(tree)
+    extra = _baseline_table(tree, baselines)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
-            if baselines:
-                for name, impl in {**BASELINE_ALIASES.get(tree, {}), **BASELINE_OVERRIDES.get(tree, {})}.items():
-                    if f.table.get(name) != impl:
-                        f.table[name] = impl
-                        sys.modules.pop(name, None)
+            for name, impl in extra.items():
+                bound_for_all = ALL_BASELINE_OVERRIDES.get(tree, {}).get(name)
+                if bound_for_all is not None and f.table.get(name) == bound_for_all:
+                    continue                    # already bound for "all": a later baselines=True takes nothing away
+                if f.table.get(name) != impl:
+                    f.table[name] = impl
+                    sys.modules.pop(name, None)
             return f
     finder = AliasFinder(tree, baselines)
     sys.meta_path.insert(0, finder)

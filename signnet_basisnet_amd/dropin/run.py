@@ -13,6 +13,9 @@ package, everything else from the tree.  `--tree` overrides the guess from the s
 also binds the trees' baseline models, `dropin.BASELINE_ALIASES`: `baseline_gin` (NetGINE) and `core.model` (the plain GINE GNN of
 `model.gnn_type GINEConv`); without it both stay the tree's.  For LearningFilters it rebinds `models`
 (`dropin.BASELINE_OVERRIDES`) so that BernNet, GPRNet, ChebNet and GcnNet are the HIP classes of `filter_baselines.py`.
+`--baselines=all` binds GatNet and ARMANet as well (`dropin.ALL_BASELINE_OVERRIDES`):
+
+    cd <reference>/LearningFilters  && python -m signnet_basisnet_amd.dropin.run --baselines=all training.py --net GatNet
 """
 from __future__ import annotations
 
@@ -29,6 +32,11 @@ def main(argv=None) -> None:
     while argv and argv[0].startswith("--"):        # the runner's own options come before the script
         if argv[0] == "--baselines":
             baselines, argv = True, argv[1:]
+        elif argv[0].startswith("--baselines="):
+            value = argv[0].split("=", 1)[1]
+            if value != "all":
+                raise SystemExit(f"--baselines={value}: the only value is 'all' (plain --baselines binds the built baselines without GatNet / ARMANet)")
+            baselines, argv = "all", argv[1:]
         elif argv[0] == "--tree":
             if len(argv) < 2:
                 raise SystemExit("--tree needs a value: " + ", ".join(sorted(ALIASES)))
@@ -38,7 +46,7 @@ def main(argv=None) -> None:
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines] <entry script> [script arguments ...]\n"
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] <entry script> [script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
     script = argv[0]
     if not os.path.isfile(script):

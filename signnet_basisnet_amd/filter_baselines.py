@@ -14,8 +14,19 @@ Constructors and state_dict keys / shapes are the reference's: BernNet `convs.i.
 GPRNet `lins.i.*`, `prop1.temp [K+1]`, `fc2.*`; ChebNet `convs.i.lins.k.weight`, `convs.i.bias` and GcnNet `convs.i.lin.weight`,
 `convs.i.bias` as torch_geometric 2.0.1 lays ChebConv / GCNConv out (restated from its documented definition, like the GIN layers).
 `prop1.temp` is float64 in the reference (torch.tensor of a numpy array); here it is float32 and load_state_dict converts.
-GatNet and ARMANet are not polynomial filters of the operator (attention with ELU and self loops; ARMAConv's recursive skip) and are
-not built: gen_model(..., baselines=True) raises NotImplementedError for them.
+
+GatNet and ARMANet (models.py:256-272, 221-236) are not polynomial filters of the operator (attention with ELU and self loops;
+ARMAConv's skip) and stay out of NETS: gen_model(..., baselines=True) and gen_baseline(name, ...) raise NotImplementedError for them as
+before.  They are EXTRA_NETS, built by gen_baseline(name, ..., extra=True) / gen_model(..., baselines="all"):
+
+  GatNet    per conv: forward 2 (the GEMM; sn_gat_conv_f32: attention over the in-edges and the implicit self loop, bias, ELU)
+                      backward 3 for the attention (sn_gat_conv_bwd_f32's two launches, the reduction of the d att_l | d att_r | d bias partials)
+  ARMANet   per conv: forward 1 (combine, c = [0, 1], over FilterGraph.arma) and ONE GEMM over [S x | x]   backward 1 (combine over S^T)
+
+GATConv and ARMAConv are restated from torch_geometric 2.0.1's documented definitions (PyG is not a dependency), their parameter names
+and key order from memory of that release: `att_l`, `att_r` [1, heads, out], `bias`, `lin_l.weight` and the alias `lin_r.weight`;
+`init_weight` [K, in, out], `weight` [max(1, T-1), K, out, out] (unused and without gradient at T = 1), `root_weight` [T, K, in, out],
+`bias` [T, K, 1, out].  Only what the reference sets is built; everything else raises.
 
 The operator follows PyG's source_to_target flow: messages go from edge_index[0] to edge_index[1]; multi-edges add.
 """
@@ -82,6 +93,20 @@ class FilterGraph:
         dis2 = deg2.pow(-0.5)
         dis2.masked_fill_(dis2 == float("inf"), 0)
         self.gcn = _operator_pair(s2, t2, dis2[s2] * one2 * dis2[t2], N)
+        self._edges, self._arma = ei, None
+
+    @property
+    def arma(self):
+        """ARMAConv's operator, gcn_norm(..., add_self_loops=False): every input edge kept (a self loop is an ordinary entry), unit
+        weights, degree over the TARGET index, inf -> 0.  Built on first use (only ARMANet asks for it)."""
+        if self._arma is None:
+            s, t = self._edges[0], self._edges[1]
+            one = torch.ones(s.numel(), dtype=torch.float32, device=self.device)
+            deg = torch.zeros(self.N, dtype=torch.float32, device=self.device).index_add_(0, t, one)
+            dis = deg.pow(-0.5)
+            dis.masked_fill_(dis == float("inf"), 0)
+            self._arma = _operator_pair(s, t, dis[s] * one * dis[t], self.N)
+        return self._arma
 
 
 _GRAPHS = {}
@@ -300,11 +325,145 @@ class GcnNet(nn.Module):
         return AG.linear(h, self.fc2.weight, self.fc2.bias)
 
 
+# ----------------------------------------------------------------------------- GatNet (models.py:256-272; PyG 2.0.1 GATConv, restated)
+def _glorot(t):
+    """PyG's 'glorot': uniform in +-sqrt(6 / (size(-2) + size(-1))), whatever the leading dimensions."""
+    bound = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
+    with torch.no_grad():
+        t.uniform_(-bound, bound)
+
+
+class GATConv(nn.Module):
+    """torch_geometric 2.0.1's GATConv from its documented definition (PyG is not installed here; the parameter layout and key order are
+    restated from memory of 2.0.1): a bias-free Linear `lin_l` [heads * out, in] that `lin_r` aliases (both keys are in the state_dict),
+    `att_l`, `att_r` [1, heads, out] (glorot) and `bias` [heads * out] (zeros).  The input self loops are removed and every node gets
+    exactly one; e_ij = leaky_relu(att_l . x'_j + att_r . x'_i), softmax over j, out_i = sum_j a_ij x'_j + bias, heads concatenated.
+    Only what the reference's GatNet sets is built: concat=True, dropout=0, add_self_loops=True."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, bias=True):
+        super().__init__()
+        if dropout != 0:
+            raise NotImplementedError("GATConv: dropout != 0 is not built (the reference's GatNet sets 0)")
+        if not concat:
+            raise NotImplementedError("GATConv: concat=False is not built (the reference's GatNet concatenates the heads)")
+        if not add_self_loops:
+            raise NotImplementedError("GATConv: add_self_loops=False is not built (the kernel's self loop is implicit)")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.negative_slope, self.dropout, self.add_self_loops = concat, negative_slope, dropout, add_self_loops
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=False)
+        self.lin_r = self.lin_l
+        self.att_l = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_r = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(heads * out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot(self.lin_l.weight)
+        _glorot(self.att_l)
+        _glorot(self.att_r)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, x, edge_index, act=None):
+        """Two launches: the GEMM and the attention (bias and `act` — None or 'elu' — in the attention launch)."""
+        g = _graph_for(x, edge_index)
+        f = AG.linear(x.float(), self.lin_l.weight)
+        return AG.gat_conv(f, self.att_l, self.att_r, self.bias, g, self.heads, act, self.negative_slope)
+
+
+class GatNet(nn.Module):
+    def __init__(self, in_channels, hidden_channels=32, num_heads=4, num_layers=2):
+        super().__init__()
+        if num_layers > 1 and hidden_channels % num_heads:
+            raise ValueError(f"GatNet: hidden_channels = {hidden_channels} is not a multiple of num_heads = {num_heads}: the second layer "
+                             "would not take the first one's output (the reference fails in forward there)")
+        self.convs = nn.ModuleList([GATConv(in_channels, hidden_channels // num_heads, heads=num_heads, concat=True, dropout=0.0)])
+        for _ in range(num_layers - 1):
+            self.convs.append(GATConv(hidden_channels, hidden_channels // num_heads, heads=num_heads, concat=True, dropout=0.0))
+        self.fc2 = nn.Linear(hidden_channels, 1)
+
+    def forward(self, x, edge_index):
+        g = _graph_for(x, edge_index)
+        h = x.float()
+        for conv in self.convs:
+            h = conv(h, g, act="elu")                  # F.elu(conv(x, edge_index)): the ELU rides in the attention launch
+        return AG.linear(h, self.fc2.weight, self.fc2.bias)
+
+
+# ----------------------------------------------------------------------------- ARMANet (models.py:221-236; PyG 2.0.1 ARMAConv, restated)
+class ARMAConv(nn.Module):
+    """torch_geometric 2.0.1's ARMAConv from its documented definition (restated; key order from memory of 2.0.1): `init_weight`
+    [K, in, out], `weight` [max(1, T-1), K, out, out], `root_weight` [T, K, in, out] (glorot) and `bias` [T, K, 1, out] (zeros) for
+    K = num_stacks, T = num_layers.  One stack of one layer — all the reference's ARMANet builds — is
+    act(S (x init_weight) + x root_weight + bias) with S = gcn_norm without added self loops; `weight` is unused at T = 1 and gets
+    no gradient, as in PyG.  act: ReLU only."""
+
+    def __init__(self, in_channels, out_channels, num_stacks=1, num_layers=1, shared_weights=False, act="relu", dropout=0.0, bias=True):
+        super().__init__()
+        if num_stacks != 1 or num_layers != 1:
+            raise NotImplementedError("ARMAConv: one stack of one layer only (the reference's ARMANet builds ARMAConv(in, out, 1, 1, False))")
+        if shared_weights:
+            raise NotImplementedError("ARMAConv: shared_weights=True is not built (the reference passes False)")
+        if dropout != 0:
+            raise NotImplementedError("ARMAConv: dropout != 0 is not built (the reference sets 0)")
+        if not (act == "relu" or act is torch.relu or act is torch.nn.functional.relu or isinstance(act, nn.ReLU)):
+            raise NotImplementedError("ARMAConv: ReLU only (PyG's default)")
+        K, T = num_stacks, num_layers
+        self.in_channels, self.out_channels, self.num_stacks, self.num_layers = in_channels, out_channels, K, T
+        self.shared_weights, self.dropout = shared_weights, dropout
+        self.init_weight = nn.Parameter(torch.empty(K, in_channels, out_channels))
+        self.weight = nn.Parameter(torch.empty(max(1, T - 1), K, out_channels, out_channels))
+        self.root_weight = nn.Parameter(torch.empty(T, K, in_channels, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(T, K, 1, out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.register_buffer("_c01", torch.tensor([0.0, 1.0]), persistent=False)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot(self.init_weight)
+        _glorot(self.weight)
+        _glorot(self.root_weight)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, x, edge_index):
+        g = _graph_for(x, edge_index)
+        x = x.float()
+        # S (x W_init) = (S x) W_init: one propagation, then ONE GEMM over [S x | x] with [W_init; W_root], bias and ReLU in its epilogue
+        p = AG.poly_combine_shared(x, self._c01, g.arma, 1, "monomial", 0.0, 1.0)
+        W = torch.cat([self.init_weight[0], self.root_weight[0, 0]], dim=0)
+        return AG.linear_io(torch.cat([p, x], dim=1), W, None if self.bias is None else self.bias.reshape(-1), relu=True)
+
+
+class ARMANet(nn.Module):
+    def __init__(self, in_channels, hidden_channels=32, num_layers=2):
+        super().__init__()
+        self.convs = nn.ModuleList([ARMAConv(in_channels, hidden_channels, 1, 1, False, dropout=0)])
+        for _ in range(num_layers - 1):
+            self.convs.append(ARMAConv(hidden_channels, hidden_channels, 1, 1, False, dropout=0))
+        self.fc2 = nn.Linear(hidden_channels, 1)
+
+    def forward(self, x, edge_index):
+        g = _graph_for(x, edge_index)
+        h = x.float()
+        for conv in self.convs:
+            h = conv(h, g)                             # F.relu(conv(...)): the conv ends in a ReLU already, the second one is idempotent
+        return AG.linear(h, self.fc2.weight, self.fc2.bias)
+
+
 NETS = {"BernNet": BernNet, "GPRNet": GPRNet, "ChebNet": ChebNet, "GcnNet": GcnNet}
+EXTRA_NETS = {"GatNet": GatNet, "ARMANet": ARMANet}        # opt-in: gen_baseline(..., extra=True), gen_model(..., baselines="all")
 
 
-def gen_baseline(name, in_channels, hidden_channels=32, num_layers=2):
-    """training.py:154-165 for the four names built here."""
+def gen_baseline(name, in_channels, hidden_channels=32, num_layers=2, extra=False):
+    """training.py:154-165 for the four names built here; extra=True: GatNet and ARMANet too."""
+    if extra and name in EXTRA_NETS:
+        return EXTRA_NETS[name](in_channels, hidden_channels=hidden_channels, num_layers=num_layers)
     if name in NOT_BUILT:
         raise NotImplementedError(f"{name} is not a polynomial filter of the graph operator (PyG's GATConv / ARMAConv) and is not built on "
                                   "the HIP stack; BernNet, GPRNet, ChebNet and GcnNet are")

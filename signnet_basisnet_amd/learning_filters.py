@@ -15,7 +15,8 @@ The graph-convolution baselines of gen_model are the paper's comparison rows.  B
 of the graph operator and run on this stack (filter_baselines.py, csrc/poly_filter.hip) when asked for: `gen_model(..., baselines=True)`
 builds them, and `train_step` / `GraphedEpoch` / `fit` hand them the graph through `graph=` (a filter_baselines.FilterGraph or the
 edge_index tensor; the reference passes data.edge_index, training.py:140).  Without the flag every name of GRAPH_CONV_BASELINES raises
-NotImplementedError as before; GatNet and ARMANet (PyG's GATConv / ARMAConv: not polynomials of the operator) raise with it too.
+NotImplementedError as before; GatNet and ARMANet (PyG's GATConv / ARMAConv: not polynomials of the operator) raise with it too and are
+built with `baselines="all"` (csrc/filter_attention.hip: the attention layer's own kernel pair; ARMAConv is one more operator on FilterGraph).
 The 'abs_val' / 'sign_flip' feature variants (training.py:94-100) are one launch of ops.lap_pe_transform.
 
 Everything is differentiable in train mode (autograd.py ops; backward kernels in csrc/backward.hip and csrc/dense_attention.hip).
@@ -205,11 +206,15 @@ def gen_rho(args: FilterArgs, eig: GridEigen):
 
 def gen_model(args: FilterArgs, eig: GridEigen, device="cuda", baselines=False):
     """training.py:152-181: the base network, with `sign_inv_net` / `basis_inv_net` and `rho` attached as attributes.
-    baselines=True: BernNet / GPRNet / ChebNet / GcnNet are built (filter_baselines.py); GatNet and ARMANet raise either way."""
+    baselines=True: BernNet / GPRNet / ChebNet / GcnNet are built (filter_baselines.py); GatNet and ARMANet still raise.
+    baselines="all": those two are built as well (csrc/filter_attention.hip; ARMAConv on the polynomial-filter kernels)."""
     d_in = 1 + eig.pe_dim
+    if baselines not in (False, True, "all"):
+        raise ValueError(f"gen_model: baselines must be False, True or 'all', got {baselines!r}")
     if args.net in GRAPH_CONV_BASELINES and baselines:
         from .filter_baselines import gen_baseline
-        model = gen_baseline(args.net, d_in, hidden_channels=args.hidden_channels, num_layers=args.num_layers)
+        model = gen_baseline(args.net, d_in, hidden_channels=args.hidden_channels, num_layers=args.num_layers,
+                             **({"extra": True} if baselines == "all" else {}))
     elif args.net in GRAPH_CONV_BASELINES:
         raise NotImplementedError(f"{args.net}: the graph-convolution baselines of the filter table are not part of the "
                                   "sign / basis invariant path (SURVEY.md §8 'out of scope'); gen_model(..., baselines=True) builds "
@@ -352,13 +357,16 @@ def r2_score(target, pred):
     return float(1.0 - ss_res / ss_tot) if ss_tot > 0 else 0.0
 
 
-def fit(args: FilterArgs, eig: GridEigen, x, y, m, epochs=None, model=None, optimizer=None, log=None, use_graph=False, graph=None):
+def fit(args: FilterArgs, eig: GridEigen, x, y, m, epochs=None, model=None, optimizer=None, log=None, use_graph=False, graph=None,
+        baselines=None):
     """The per-image loop of training.py:229-250: a fresh model, Adam(lr), `epochs` steps; keeps the minimum loss and its r2.
     Returns {'min_loss', 'best_r2', 'epoch', 'model'}.  The loss is read back once per epoch, as the reference's loss.item() does.
     use_graph: replay the epoch as a captured HIP graph (GraphedEpoch; optimiser = optim.FlatAdam).  graph: the model's second argument
-    (the filter baselines' FilterGraph or edge tensor; with it a fresh model is built with baselines=True)."""
+    (the filter baselines' FilterGraph or edge tensor; with it a fresh model is built with baselines=True).  baselines: gen_model's flag
+    for that fresh model, when the default is not wanted — "all" also builds GatNet and ARMANet."""
     from .optim import Adam, FlatAdam
-    model = model if model is not None else gen_model(args, eig, x.device, baselines=graph is not None)
+    if model is None:
+        model = gen_model(args, eig, x.device, baselines=(graph is not None) if baselines is None else baselines)
     if optimizer is None:
         optimizer = FlatAdam(model.parameters(), lr=args.lr) if use_graph else Adam(model.parameters(), lr=args.lr)
     graphed = GraphedEpoch(model, optimizer, args, eig, x, y, m, graph=graph) if use_graph else None

@@ -1528,6 +1528,86 @@ def poly_combine(a, op: SparseOperator, K, mode="monomial", diag_add=0.0, scale=
     return y
 
 
+# ----------------------------------------------------------------------------- PyG's GATConv on one fixed graph (csrc/filter_attention.hip)
+GAT_ACT_NONE, GAT_ACT_ELU = 0, 1
+GAT_ACTS = {None: GAT_ACT_NONE, "none": GAT_ACT_NONE, "elu": GAT_ACT_ELU}
+
+
+def gat_conv_limits():
+    """(max heads, max channels per head) of sn_gat_conv_f32 / sn_gat_conv_bwd_f32."""
+    return int(lib().sn_gat_conv_max_heads()), int(lib().sn_gat_conv_max_channels())
+
+
+def gat_conv_group_width(C):
+    """Lanes that own one (node, head) of C channels: min(64, the power of two >= C); 0 outside the limits.  The kernel's only dispatch
+    thresholds are the widths at which this doubles, and C = 64 -> 65 (one -> two channels per lane)."""
+    return int(lib().sn_gat_conv_group_width(int(C)))
+
+
+def _gat_check(fn, feat, att_l, att_r, bias, op, heads, act):
+    a = GAT_ACTS.get(act, act) if act is None or isinstance(act, str) else act
+    if a not in (GAT_ACT_NONE, GAT_ACT_ELU):
+        raise ValueError(f"{fn}: act must be one of {sorted(k for k in GAT_ACTS if k)} (or None / 0 / 1), got {act!r}")
+    heads = int(heads)
+    if heads < 1 or feat.dim() != 2 or feat.shape[1] < heads or feat.shape[1] % heads:
+        raise ValueError(f"{fn}: feat must be [N, heads * C] with heads = {heads} >= 1, got {tuple(feat.shape)}")
+    Cc = feat.shape[1] // heads
+    mh, mc = gat_conv_limits()
+    if heads > mh or Cc > mc:                         # before any launch (and before the tensors are looked at)
+        raise ValueError(f"{fn}: heads = {heads}, C = {Cc} is beyond the kernel's limits (heads <= {mh}, C <= {mc})")
+    require_cuda(feat, att_l, att_r, bias, op.rowptr, op.col)
+    # (op.nnz IS op.col.numel(): the kernels clamp rowptr to exactly the entries col holds, provided both arrays are dense in memory)
+    if op.N < 1 or feat.shape[0] != op.N or op.rowptr.dtype != torch.int32 or op.rowptr.numel() != op.N + 1 or op.col.dtype != torch.int32 \
+            or op.col.dim() != 1 or not op.col.is_contiguous() or not op.rowptr.is_contiguous():
+        raise ValueError(f"{fn}: feat has {feat.shape[0]} rows; the operator must be a contiguous CSR (int32) of as many nodes")
+    feat = _f32c(feat, "feat")
+    vecs = [None if t is None else _f32c(t.reshape(-1), n) for t, n in ((att_l, "att_l"), (att_r, "att_r"), (bias, "bias"))]
+    if vecs[0] is None or vecs[1] is None or any(v is not None and v.numel() != heads * Cc for v in vecs):
+        raise ValueError(f"{fn}: att_l, att_r (and bias, if given) must hold heads * C = {heads * Cc} values")
+    return feat, vecs[0], vecs[1], vecs[2], heads, Cc, a
+
+
+def gat_conv(feat, att_l, att_r, bias, op: SparseOperator, heads, act="elu", negative_slope=0.2):
+    """torch_geometric's GATConv behind its Linear, with the activation that follows, in ONE launch (sn_gat_conv_f32).  feat [N, heads*C]:
+    the Linear's output; att_l, att_r, bias (or None): heads*C values; op: the CSR by destination with the input self loops dropped
+    (FilterGraph.lap's pattern; the weights are not read) — every node attends over its in-edges and itself.  act: 'elu' or None.
+    -> (out [N, heads*C], lse [N, heads])."""
+    feat, al, ar, b, heads, Cc, a = _gat_check("gat_conv", feat, att_l, att_r, bias, op, heads, act)
+    N = op.N
+    out = torch.empty(N, heads * Cc, dtype=torch.float32, device=feat.device)
+    lse = torch.empty(N, heads, dtype=torch.float32, device=feat.device)
+    with _span("sn_gat_conv_f32"):
+        check(lib().sn_gat_conv_f32(ptr(feat), ptr(al), ptr(ar), ptr(b), N, heads, Cc, float(negative_slope), a, ptr(op.rowptr), ptr(op.col),
+                                    op.nnz, ptr(out), ptr(lse), stream()), "sn_gat_conv_f32")
+    return out, lse
+
+
+def gat_conv_bwd(feat, att_l, att_r, out, lse, dout, op: SparseOperator, heads, act="elu", negative_slope=0.2):
+    """Adjoint of gat_conv in two launches and one reduction (sn_gat_conv_bwd_f32, sn_train_reduce_parts_f32): op.t must be the operator
+    of the flipped edge list.  dout is the cotangent of `out` (the activation's adjoint is applied inside, from `out`).
+    -> (dfeat [N, heads*C], d att_l [heads*C], d att_r [heads*C], d bias [heads*C])."""
+    feat, al, ar, _, heads, Cc, a = _gat_check("gat_conv_bwd", feat, att_l, att_r, None, op, heads, act)
+    if op.t is None or op.t.N != op.N or op.t.nnz != op.nnz:
+        raise ValueError("gat_conv_bwd: the operator has no transposed partner (.t) of the same size")
+    require_cuda(out, lse, dout, op.t.rowptr, op.t.col)
+    N, D = op.N, heads * Cc
+    out, dout, lse = _f32c(out, "out"), _f32c(dout, "dout"), _f32c(lse, "lse")
+    if tuple(out.shape) != (N, D) or tuple(dout.shape) != (N, D) or lse.numel() != N * heads:
+        raise ValueError(f"gat_conv_bwd: out and dout must be [{N}, {D}], lse [{N}, {heads}]")
+    blocks = int(lib().sn_gat_conv_bwd_blocks(N, heads, Cc))
+    dfeat = torch.empty(N, D, dtype=torch.float32, device=feat.device)
+    part = torch.empty(blocks, 3 * D, dtype=torch.float32, device=feat.device)
+    work = torch.empty(5 * N * heads, dtype=torch.float64, device=feat.device)
+    dpar = torch.empty(3 * D, dtype=torch.float32, device=feat.device)
+    with _span("sn_gat_conv_bwd_f32"):
+        check(lib().sn_gat_conv_bwd_f32(ptr(feat), ptr(al), ptr(ar), ptr(out), ptr(lse), ptr(dout), N, heads, Cc, float(negative_slope), a,
+                                        ptr(op.rowptr), ptr(op.col), ptr(op.t.rowptr), ptr(op.t.col), op.nnz, ptr(dfeat), ptr(part),
+                                        ptr(work), stream()), "sn_gat_conv_bwd_f32")
+    with _span("sn_train_reduce_parts_f32"):
+        check(lib().sn_train_reduce_parts_f32(ptr(part), blocks, 3 * D, 3 * D, ptr(dpar), 0, stream()), "sn_train_reduce_parts_f32")
+    return dfeat, dpar[:D], dpar[D:2 * D], dpar[2 * D:]
+
+
 _ONES = {}
 
 
