@@ -969,7 +969,8 @@ int sn_transformer_net_fused_f32(const sn_gnn_params* params, const void* head_m
  * sn_train_linear_bwd_f32: the adjoint of one link in one pass.
  *     g  = dy * [mask_scale * zo + mask_shift > 0]     (the ReLU behind this Linear's BatchNorm; mask_* NULL: g = dy)
  *     dz = coef_a * g - coef_b - coef_c * zo           (that BatchNorm's backward, sn_train_bn_bwd_finish_f32; coef_* NULL: dz = g)
- *     x_hat = [relu](x * x_scale + x_shift) or x       (the operand the forward link formed on load)
+ *     x_hat = [relu](x * x_scale + x_shift) or x       (the operand the forward link formed on load; x_relu needs x_scale / x_shift:
+ *                                                       a forward link with in_relu alone is x_scale = 1, x_shift = 0 here)
  *     gx = (dz W) * [x_hat > 0 if x_relu]              -> gx [G*R, d_in]  (NULL: no input gradient)
  *     sums_part[g][blk][0][c] = sum gx, [1][c] = sum gx * (x - x_mean[g])   (x_mean != NULL; for the producer's BatchNorm backward)
  *     dw_part[g*nblk + blk] = sum dz^T x_hat (d_out * d_in floats) followed by sum dz (d_out floats, want_db) — per-workgroup

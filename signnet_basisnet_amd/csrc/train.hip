@@ -1834,6 +1834,8 @@ extern "C" int sn_train_linear_bwd_f32(const sn_train_linear_bwd_args* args, voi
   SN_REQUIRE((!p.coef_a && !p.coef_b && !p.coef_c) || (p.coef_a && p.coef_b && p.coef_c && p.zo), "sn_train_linear_bwd_f32: coef_a/b/c need zo");
   SN_REQUIRE((!p.mask_scale && !p.mask_shift) || (p.mask_scale && p.mask_shift && p.zo), "sn_train_linear_bwd_f32: mask_scale/shift need zo");
   SN_REQUIRE((p.x_scale == nullptr) == (p.x_shift == nullptr), "sn_train_linear_bwd_f32: x_scale / x_shift go together");
+  // (the dW product re-forms the operand's ReLU only behind its affine: a plain ReLU operand is x_scale = 1, x_shift = 0)
+  SN_REQUIRE(!p.x_relu || p.x_scale, "sn_train_linear_bwd_f32: x_relu needs x_scale / x_shift");
   SN_REQUIRE(!p.x_mean || (p.gx && p.sums_part), "sn_train_linear_bwd_f32: x_mean needs gx and sums_part");
   SN_REQUIRE(!p.gx_accumulate || (p.gx && !p.x_mean && !p.dot_x), "sn_train_linear_bwd_f32: gx_accumulate excludes the column sums");
   SN_REQUIRE(!p.nvalid || p.K > 0, "sn_train_linear_bwd_f32: nvalid needs K > 0");
