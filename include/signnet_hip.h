@@ -1250,6 +1250,64 @@ int sn_gat_conv_bwd_f32(const float* feat, const float* att_l, const float* att_
                         const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t, int64_t nnz, float* dfeat, float* part,
                         double* work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The message side of SimplifiedPNAConv with aggregators=['mean'] (GINESignNetPyG/core/model_utils/pyg_gnn_wrapper.py:53-106; built by
+ * GNN for model.gnn_type SimplifiedPNAConv, core/model.py:24-27, train/zinc.py:31-46): pre_nn = MLP(3d, d, 2, False) applied to
+ * cat[x_i, x_j, e] (:92-94), i.e. Linear(3d -> 3d, no bias) -> BatchNorm1d(3d) over the E edge rows -> ReLU -> Linear(3d -> d), then
+ * the mean over each node's in-edges (:96-99).  C = 3d.
+ *   z_e = (A[dst(e)] + B[src(e)]) + Q[e]     A = x W1[:, :d]^T, B = x W1[:, d:2d]^T ([N, C], row strides lda, ldb), Q = e W1[:, 2d:]^T
+ *                                            ([E, C] in edge-id order, row stride ldq): the first Linear split over the concatenation
+ *   r[i, c] = (1 / max(deg_i, 1)) sum_{e in in(i)} relu(z_e[c] * scale[c] + shift[c])      (sn_spna_mean_f32; r: [N, C], stride ldr)
+ * The second Linear commutes with the mean and is left to the caller: out_i = W2 r_i + b2 [deg_i > 0].  z is never stored: every
+ * launch forms it on the fly with the same two additions, so the ReLU mask of the adjoint is the forward's bit for bit.  rowptr / col /
+ * eperm: the destination-sorted CSR of sn_batch_plan (in-edges in edge-id order; multi-edges and self loops count; a node without
+ * in-edges gets zeros).  3 <= C <= SN_SPNA_MAX_CHANNELS; any in-degree.
+ * sn_spna_stats_f32 (train mode): per-column mean, biased variance and count of the E rows z_e — per-workgroup (count, mean, M2)
+ *   partials over consecutive node ranges, merged in block order (Chan) — then state[0..4][C] = mean, variance, rstd, scale = gamma *
+ *   rstd, shift = beta - mean * scale, count[0] = E, and the running statistics moved as BatchNorm1d moves them (momentum, unbiased
+ *   variance) when given.  E < 2 is SN_ERR_ARG (torch refuses one value per channel).  work: float[sn_spna_blocks(N, C) * 3 * C].
+ * sn_spna_bwd_f32: the adjoint for dr [N, C] (row stride lddr).  g_e = dr[dst] / deg * [z_e * scale + shift > 0].  state != NULL (as
+ *   written by sn_spna_stats_f32; scale / shift are then taken from it): the full train-mode BatchNorm backward, dz_e = gamma rstd
+ *   (g_e - mean_E(g) - xhat_e mean_E(g xhat)), the two column sums over the edges taken first (partials in block order), and
+ *   dgamma = sum g xhat, dbeta = sum g written when given; state == NULL (eval): dz_e = g_e * scale.  Outputs: dQ[e] = dz_e ([E, C] in
+ *   edge-id order, the one E-sized temporary: the weight gradient of W1[:, 2d:] needs it), dA[i] = sum_{in(i)} dz_e, dB[j] =
+ *   sum_{out(j)} dz_e over rowptr_t / eperm_t, the plan of the FLIPPED edge list.  work: float[sn_spna_blocks(N, C) * 2 * C + 3 * C].
+ * One owner per output element, no atomics, sums in a fixed order: bit-reproducible.  A thread owns (node, 4 consecutive channels) with
+ * 16-byte accesses when sn_spna_vector_path holds for every matrix of the call (C and the row strides multiples of 4, pointers 16-byte
+ * aligned), (node, channel) otherwise. */
+#define SN_SPNA_MAX_CHANNELS 384
+int sn_spna_blocks(int64_t N, int C);
+int sn_spna_vector_path(int C, int64_t lda, int64_t ldb, int64_t ldq, int64_t ldo, const void* a, const void* b, const void* q,
+                        const void* o);
+int sn_spna_stats_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                      int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const float* gamma,
+                      const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* state,
+                      float* count, float* work, void* stream);
+int sn_spna_mean_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                     int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const float* scale,
+                     const float* shift, float* r, int64_t ldr, void* stream);
+int sn_spna_bwd_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                    int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* rowptr_t,
+                    const int32_t* eperm_t, const float* dr, int64_t lddr, const float* scale, const float* shift,
+                    const float* state, const float* gamma, float* dA, int64_t ldda, float* dB, int64_t lddb, float* dQ,
+                    int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The propagation of torch_geometric's GCNConv (gcn_norm, add_self_loops=True, unit edge weights) behind its Linear, which GNN builds
+ * for model.gnn_type GCNConv (GINESignNetPyG/core/model_utils/pyg_gnn_wrapper.py:39-48: `self.layer(x, edge_index)`), restated from
+ * the library's documented definition.  The input's self loops are replaced by exactly one unit loop per node, multi-edges are kept, and
+ * BOTH factors deg^-1/2 come from the in-degree (the sum over the target index) of A + I — not sn_gcn_propagate_f32's DGL
+ * normalisation, whose second factor is the out-degree and which adds no loop.
+ * sn_gcn_pyg_coef_f32:      dis[i] = (1 + #{e in in(i): col[e] != i})^-1/2                                        dis: [N]
+ * sn_gcn_pyg_propagate_f32: out[i] = dis[i] * (sum_{e in in(i), col[e] != i} dis[col[e]] x[col[e]] + dis[i] x[i])   x, out: [N, C]
+ * over the destination-sorted CSR of sn_batch_plan (rowptr, col; E slots; the plan keeps the input's self loops, they are skipped
+ * here), row strides ldx, ldo >= C.  The adjoint w.r.t. x is the same call on the plan of the FLIPPED edge list with the same dis.
+ * Any N (no node limit), any in-degree; one owner per output element, sums in edge order, no atomics: bit-reproducible.  16-byte
+ * vector accesses when C, ldx, ldo are multiples of 4 and x, out 16-byte aligned, scalar ones otherwise. */
+int sn_gcn_pyg_coef_f32(int64_t N, int64_t E, const int32_t* rowptr, const int32_t* col, float* dis, void* stream);
+int sn_gcn_pyg_propagate_f32(const float* x, int64_t ldx, int64_t N, int C, int64_t E, const int32_t* rowptr, const int32_t* col,
+                             const float* dis, float* out, int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

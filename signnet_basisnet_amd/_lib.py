@@ -150,6 +150,14 @@ SIGNATURES = {
     "sn_gat_conv_bwd_blocks": [_l, _i, _i],
     "sn_gat_conv_f32": [_p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _l, _p, _p, _p],
     "sn_gat_conv_bwd_f32": [_p, _p, _p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _p, _p, _l, _p, _p, _p, _p],
+    "sn_spna_blocks": [_l, _i],                          # (the two below return a count / 0 or 1, not a status)
+    "sn_spna_vector_path": [_i, _l, _l, _l, _l, _p, _p, _p, _p],
+    "sn_spna_stats_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p],
+    "sn_spna_mean_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p, _l, _p],
+    "sn_spna_bwd_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _l, _p, _l, _p, _l, _p, _p,
+                        _p, _p],
+    "sn_gcn_pyg_coef_f32": [_l, _l, _p, _p, _p, _p],
+    "sn_gcn_pyg_propagate_f32": [_p, _l, _l, _i, _l, _p, _p, _p, _p, _l, _p],
 }
 _SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64,
                     "sn_gnn_front_bytes": C.c_int64}

@@ -986,3 +986,54 @@ def gat_conv(feat, att_l, att_r, bias, graph, heads, act="elu", negative_slope=0
     Gradients for feat, att_l, att_r and bias."""
     op = getattr(graph, "lap", graph)
     return _GatConv.apply(feat, att_l, att_r, bias, op, heads, act, negative_slope)
+
+
+# ----------------------------------------------------------------------------- SimplifiedPNAConv's message side (csrc/simplified_pna.hip)
+class _SpnaMean(Function):
+    """r = mean over in-edges of relu(BatchNorm1d_train(a[dst] + b[src] + q[e])) with ab = [a | b] one [N, 2C] block: the statistics
+    launch and the mean launch forward, ops.spna_bwd backward (z recomputed; dQ is the one [E, C] temporary)."""
+
+    @staticmethod
+    def forward(ctx, ab, q, gamma, beta, bn, plan, rplan):
+        ab, q = _c(ab.detach()), _c(q.detach())
+        Cc = q.shape[1]
+        a, b = ab[:, :Cc], ab[:, Cc:]
+        state, _ = ops.spna_stats(a, b, q, plan, bn)
+        r = ops.spna_mean(a, b, q, plan, state[3], state[4])
+        ctx.save_for_backward(ab, q, state, gamma)
+        ctx.meta = (plan, rplan, gamma is not None)
+        return r
+
+    @staticmethod
+    def backward(ctx, g):
+        ab, q, state, gamma = ctx.saved_tensors
+        plan, rplan, affine = ctx.meta
+        Cc = q.shape[1]
+        dab = torch.empty_like(ab)
+        dq = torch.empty_like(q)
+        _, _, _, dg, db = ops.spna_bwd(ab[:, :Cc], ab[:, Cc:], q, plan, rplan, _c(g), state=state,
+                                       gamma=None if gamma is None else gamma.detach(), out=(dab[:, :Cc], dab[:, Cc:], dq))
+        return dab, dq, dg if affine else None, db if affine else None, None, None, None
+
+
+def spna_mean(ab, q, bn, plan, rplan):
+    """Train mode, differentiable: [N, C] mean of relu(bn(z_e)) over each node's in-edges; moves bn's running statistics."""
+    return _SpnaMean.apply(ab, q, bn.weight, bn.bias, bn, plan, rplan)
+
+
+# ----------------------------------------------------------------------------- PyG's GCNConv propagation (csrc/pyg_gcn.hip)
+class _GcnPygPropagate(Function):
+    @staticmethod
+    def forward(ctx, x, plan, rplan, dis):
+        ctx.meta = (rplan, dis)
+        return ops.gcn_pyg_propagate(_c(x.detach()), plan, dis)
+
+    @staticmethod
+    def backward(ctx, g):
+        rplan, dis = ctx.meta
+        return ops.gcn_pyg_propagate(_c(g), rplan, dis), None, None, None
+
+
+def gcn_pyg_propagate(x, plan, rplan, dis):
+    """D^-1/2 (A + I) D^-1/2 x in torch_geometric's normalisation; the adjoint is the same launch on the flipped plan."""
+    return _GcnPygPropagate.apply(x, plan, rplan, dis)

@@ -74,8 +74,16 @@ ALL_BASELINE_OVERRIDES = {
 }
 
 
-def _baseline_table(tree: str, baselines) -> dict:
-    """What `baselines` (False, True or "all") adds to ALIASES[tree]."""
+# Opt-in with `gnn_types=True` (the runner's `--gnn-types`), on top of whatever `baselines` binds: the module that answers the name INSTEAD.
+# For GINESignNetPyG it is `core.model` with the plain GNN for every model.gnn_type (GINConv, GCNConv, GATConv, SimplifiedPNAConv next
+# to GINEConv: pyg_gnn_types.py); without the flag `core.model` resolves exactly as before.
+GNN_TYPE_OVERRIDES = {
+    "gine_pyg": {"core.model": _PKG + ".gnn_types_core_model"},
+}
+
+
+def _baseline_table(tree: str, baselines, gnn_types=False) -> dict:
+    """What `baselines` (False, True or "all") and `gnn_types` add to ALIASES[tree]."""
     if baselines not in (False, True, "all"):
         raise ValueError(f"baselines must be False, True or 'all', got {baselines!r}")
     table = {}
@@ -84,6 +92,8 @@ def _baseline_table(tree: str, baselines) -> dict:
         table.update(BASELINE_OVERRIDES.get(tree, {}))
     if baselines == "all":
         table.update(ALL_BASELINE_OVERRIDES.get(tree, {}))
+    if gnn_types:
+        table.update(GNN_TYPE_OVERRIDES.get(tree, {}))
     return table
 
 
@@ -122,10 +132,10 @@ class _AliasLoader(importlib.abc.Loader):
 class AliasFinder(importlib.abc.MetaPathFinder):
     """Answers the names of `ALIASES[tree]` and nothing else; every other import goes on to the normal finders."""
 
-    def __init__(self, tree: str, baselines=False):
+    def __init__(self, tree: str, baselines=False, gnn_types=False):
         self.tree = tree
         self.table = dict(ALIASES[tree])
-        self.table.update(_baseline_table(tree, baselines))
+        self.table.update(_baseline_table(tree, baselines, gnn_types))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -134,24 +144,28 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         return importlib.machinery.ModuleSpec(fullname, _AliasLoader(impl), origin=impl)
 
 
-def install(tree: str, baselines=False) -> AliasFinder:
+def install(tree: str, baselines=False, gnn_types=False) -> AliasFinder:
     """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
     `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN) and rebinds those of `BASELINE_OVERRIDES[tree]` (LearningFilters' `models`, with
     the four polynomial-filter baselines); baselines="all" rebinds those of `ALL_BASELINE_OVERRIDES[tree]` on top (LearningFilters'
-    `models` with GatNet and ARMANet too); a finder installed with less is extended in place."""
+    `models` with GatNet and ARMANet too); gnn_types=True rebinds those of `GNN_TYPE_OVERRIDES[tree]` (GINESignNetPyG's `core.model` with
+    the plain GNN for every model.gnn_type); a finder installed with less is extended in place."""
     shim_dir(tree)
-    extra = _baseline_table(tree, baselines)
+    extra = _baseline_table(tree, baselines, gnn_types)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
             for name, impl in extra.items():
                 bound_for_all = ALL_BASELINE_OVERRIDES.get(tree, {}).get(name)
                 if bound_for_all is not None and f.table.get(name) == bound_for_all:
                     continue                    # already bound for "all": a later baselines=True takes nothing away
+                bound_for_types = GNN_TYPE_OVERRIDES.get(tree, {}).get(name)
+                if bound_for_types is not None and f.table.get(name) == bound_for_types:
+                    continue                    # already bound for gnn_types: a later call without the flag takes nothing away
                 if f.table.get(name) != impl:
                     f.table[name] = impl
                     sys.modules.pop(name, None)
             return f
-    finder = AliasFinder(tree, baselines)
+    finder = AliasFinder(tree, baselines, gnn_types)
     sys.meta_path.insert(0, finder)
     for name in finder.table:           # a module imported before install() would otherwise stay bound to the tree's file
         sys.modules.pop(name, None)

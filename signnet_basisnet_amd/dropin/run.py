@@ -16,6 +16,11 @@ also binds the trees' baseline models, `dropin.BASELINE_ALIASES`: `baseline_gin`
 `--baselines=all` binds GatNet and ARMANet as well (`dropin.ALL_BASELINE_OVERRIDES`):
 
     cd <reference>/LearningFilters  && python -m signnet_basisnet_amd.dropin.run --baselines=all training.py --net GatNet
+
+`--gnn-types` (with `--baselines`) rebinds GINESignNetPyG's `core.model` (`dropin.GNN_TYPE_OVERRIDES`) to the plain GNN for every
+`model.gnn_type` — GINConv, GCNConv, GATConv and SimplifiedPNAConv next to GINEConv:
+
+    cd <reference>/GINESignNetPyG   && python -m signnet_basisnet_amd.dropin.run --baselines --gnn-types -m train.zinc model.gnn_type SimplifiedPNAConv
 """
 from __future__ import annotations
 
@@ -28,10 +33,12 @@ from . import ALIASES, SCRIPTS, install
 
 def main(argv=None) -> None:
     argv = list(sys.argv[1:] if argv is None else argv)
-    tree, baselines = None, False
+    tree, baselines, gnn_types = None, False, False
     while argv and argv[0].startswith("--"):        # the runner's own options come before the script
         if argv[0] == "--baselines":
             baselines, argv = True, argv[1:]
+        elif argv[0] == "--gnn-types":
+            gnn_types, argv = True, argv[1:]
         elif argv[0].startswith("--baselines="):
             value = argv[0].split("=", 1)[1]
             if value != "all":
@@ -46,8 +53,26 @@ def main(argv=None) -> None:
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] <entry script> [script arguments ...]\n"
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] <entry script> "
+                         "[script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
+    if argv[0] == "-m":
+        # `-m package.module` from the tree root, as GINESignNetPyG's README runs `python -m train.zinc`: the module is found on sys.path
+        # (the working directory first) and run as __main__
+        if len(argv) < 2:
+            raise SystemExit("-m needs a module name, e.g. -m train.zinc")
+        module = argv[1]
+        if tree is None:
+            tree = SCRIPTS.get(module.rsplit(".", 1)[-1] + ".py")
+            if tree is None:
+                raise SystemExit(f"cannot tell the reference tree from the module {module!r}; pass --tree " + "|".join(sorted(ALIASES)))
+        install(tree, baselines=baselines, gnn_types=gnn_types)
+        if os.getcwd() in sys.path:
+            sys.path.remove(os.getcwd())
+        sys.path.insert(0, os.getcwd())
+        sys.argv = [module] + argv[2:]
+        runpy.run_module(module, run_name="__main__", alter_sys=True)
+        return
     script = argv[0]
     if not os.path.isfile(script):
         raise SystemExit(f"{script}: no such entry script (run from the reference tree, as the script's README says)")
@@ -55,7 +80,7 @@ def main(argv=None) -> None:
         tree = SCRIPTS.get(os.path.basename(script))
         if tree is None:
             raise SystemExit(f"cannot tell the reference tree from {os.path.basename(script)!r}; pass --tree " + "|".join(sorted(ALIASES)))
-    install(tree, baselines=baselines)
+    install(tree, baselines=baselines, gnn_types=gnn_types)
     script_dir = os.path.dirname(os.path.abspath(script))
     for p in (os.getcwd(), script_dir):          # script_dir ends up first, as under `python script.py`
         if p in sys.path:

@@ -1687,3 +1687,133 @@ def graph_attention_bwd(q, k, v, out, lse, dout, graph_ptr, N, S, heads):
                                                int(S), int(heads), D // heads, ptr(g), ptr(g[:, D:]), ptr(g[:, 2 * D:]), 3 * D, ptr(delta),
                                                stream()), "sn_graph_attention_bwd_f32")
     return g
+
+
+# ----------------------------------------------------------------------------- SimplifiedPNAConv's message side (csrc/simplified_pna.hip)
+SPNA_MAX_CHANNELS = 384      # SN_SPNA_MAX_CHANNELS
+
+
+def spna_vector_path(C, strides, pointers):
+    """The dispatch predicate of the sn_spna_* launches, restated on the host: 16-byte accesses (a thread owns four consecutive channels)
+    iff C and every row stride are multiples of 4 and every pointer is 16-byte aligned; one channel per thread otherwise."""
+    return C % 4 == 0 and all(int(s) % 4 == 0 for s in strides) and all(int(p) % 16 == 0 for p in pointers)
+
+
+def spna_cut(N, C, vector):
+    """How the two column-reduction launches (statistics, adjoint sums) cut their work: (workgroups over consecutive node ranges, nodes per
+    workgroup, column chunks, channel groups per chunk, node slots per workgroup) — make_cut of csrc/simplified_pna.hip."""
+    G = C // 4 if vector else C
+    ny = -(-G // 256)
+    gw = -(-G // ny)
+    slots = 256 // gw
+    want = min(-(-max(int(N), 1) // (slots * 4)), 256)
+    npb = -(-max(int(N), 1) // want)
+    return -(-max(int(N), 1) // npb), npb, ny, gw, slots
+
+
+def _spna_operands(fn, a, b, q, plan):
+    require_cuda(a, b, q)
+    lda, ldb, ldq = _row_block(a, fn + ": a"), _row_block(b, fn + ": b"), _row_block(q, fn + ": q")
+    N, Cc = a.shape
+    if b.shape != a.shape or q.shape[1] != Cc or q.shape[0] != plan.E or plan.N != N:
+        raise ValueError(f"{fn}: a, b must be [N, C] and q [E, C] blocks of the plan's batch (N = {plan.N}, E = {plan.E})")
+    if not 3 <= Cc <= SPNA_MAX_CHANNELS:
+        raise ValueError(f"{fn}: C = {Cc} is outside [3, {SPNA_MAX_CHANNELS}]")
+    return (ptr(a), lda, ptr(b), ldb, ptr(q), ldq, Cc, N, plan.E, ptr(plan.rowptr), ptr(plan.col), ptr(plan.eperm)), N, Cc
+
+
+def spna_stats(a, b, q, plan: GraphPlan, bn):
+    """Train-mode statistics of pre_nn.norms.0 over the E rows z_e = a[dst] + b[src] + q[e], formed on the fly (sn_spna_stats_f32): ->
+    (state [5, C] = mean | biased variance | rstd | scale | shift, count [1]); moves bn's running statistics as BatchNorm1d does."""
+    args, N, Cc = _spna_operands("spna_stats", a, b, q, plan)
+    if plan.E < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size [{plan.E}, {Cc}]")
+    track = bn.track_running_stats and bn.running_mean is not None
+    if track and bn.momentum is None:
+        raise NotImplementedError("BatchNorm1d(momentum=None) (cumulative moving average) is not supported")
+    out = torch.empty(5 * Cc + 4, dtype=torch.float32, device=a.device)
+    work = torch.empty(int(lib().sn_spna_blocks(N, Cc)) * 3 * Cc, dtype=torch.float32, device=a.device)
+    g = None if bn.weight is None else bn.weight.detach()
+    be = None if bn.bias is None else bn.bias.detach()
+    with _span("sn_spna_stats_f32"):
+        check(lib().sn_spna_stats_f32(*args, ptr(g), ptr(be), float(bn.eps), float(bn.momentum or 0.0),
+                                      ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None, ptr(out),
+                                      ptr(out[5 * Cc:]), ptr(work), stream()), "sn_spna_stats_f32")
+    if track:
+        _count_batch(bn)
+    return out[:5 * Cc].view(5, Cc), out[5 * Cc:5 * Cc + 1]
+
+
+def spna_mean(a, b, q, plan: GraphPlan, scale, shift, out=None):
+    """r[i] = mean over i's in-edges of relu((a[i] + b[src] + q[e]) * scale + shift), zeros without in-edges (sn_spna_mean_f32) -> [N, C]."""
+    args, N, Cc = _spna_operands("spna_mean", a, b, q, plan)
+    if scale.numel() != Cc or shift.numel() != Cc:
+        raise ValueError("spna_mean: scale and shift must have C entries")
+    if out is None:
+        out = torch.empty(N, Cc, dtype=torch.float32, device=a.device)
+    elif out.shape != a.shape:
+        raise ValueError("spna_mean: out must be an [N, C] block")
+    ldr = _row_block(out, "spna_mean: out")
+    with _span("sn_spna_mean_f32"):
+        check(lib().sn_spna_mean_f32(*args, ptr(scale), ptr(shift), ptr(out), ldr, stream()), "sn_spna_mean_f32")
+    return out
+
+
+def spna_bwd(a, b, q, plan: GraphPlan, rplan: GraphPlan, dr, *, scale=None, shift=None, state=None, gamma=None, out=None):
+    """Adjoint of spna_mean for dr [N, C] (sn_spna_bwd_f32).  state (from spna_stats): the train-mode BatchNorm backward, -> (dA, dB, dQ,
+    dgamma, dbeta); state None: eval mode with the folded scale / shift, -> (dA, dB, dQ, None, None).  rplan: the plan of the flipped edge
+    list.  out: optional (dA, dB, dQ) blocks to write into."""
+    args, N, Cc = _spna_operands("spna_bwd", a, b, q, plan)
+    require_cuda(dr)
+    lddr = _row_block(dr, "spna_bwd: dr")
+    if dr.shape != a.shape or rplan.N != N or rplan.E != plan.E:
+        raise ValueError("spna_bwd: dr must be [N, C] and rplan the plan of the flipped edge list")
+    dev = a.device
+    if out is None:
+        dA, dB, dQ = (torch.empty(N, Cc, dtype=torch.float32, device=dev), torch.empty(N, Cc, dtype=torch.float32, device=dev),
+                      torch.empty(plan.E, Cc, dtype=torch.float32, device=dev))
+    else:
+        dA, dB, dQ = out
+    ld = [_row_block(t, "spna_bwd: out") for t in (dA, dB, dQ)]
+    dg = db = work = None
+    if state is not None:
+        state = _f32c(state, "state")
+        par = torch.empty(2, Cc, dtype=torch.float32, device=dev)
+        dg, db = par[0], par[1]
+        work = torch.empty(int(lib().sn_spna_blocks(N, Cc)) * 2 * Cc + 3 * Cc, dtype=torch.float32, device=dev)
+    with _span("sn_spna_bwd_f32"):
+        check(lib().sn_spna_bwd_f32(*args, ptr(rplan.rowptr), ptr(rplan.eperm), ptr(dr), lddr, ptr(scale), ptr(shift), ptr(state),
+                                    ptr(gamma), ptr(dA), ld[0], ptr(dB), ld[1], ptr(dQ), ld[2], ptr(dg), ptr(db), ptr(work), stream()),
+              "sn_spna_bwd_f32")
+    return dA, dB, dQ, dg, db
+
+
+# ----------------------------------------------------------------------------- PyG's GCNConv propagation (csrc/pyg_gcn.hip)
+def gcn_pyg_coef(plan: GraphPlan):
+    """dis [N] = (1 + in-degree without self loops)^-1/2: both factors of torch_geometric's gcn_norm (add_self_loops=True, unit weights)."""
+    dis = torch.empty(plan.N, dtype=torch.float32, device=plan.rowptr.device)
+    with _span("sn_gcn_pyg_coef_f32"):
+        check(lib().sn_gcn_pyg_coef_f32(plan.N, plan.E, ptr(plan.rowptr), ptr(plan.col), ptr(dis), stream()), "sn_gcn_pyg_coef_f32")
+    return dis
+
+
+def gcn_pyg_propagate(x, plan: GraphPlan, dis, out=None):
+    """out[i] = dis[i] * (sum over i's in-edges from j != i of dis[j] x[j] + dis[i] x[i]): D^-1/2 (A + I) D^-1/2 x as torch_geometric's
+    GCNConv normalises it (the input's self loops replaced by one unit loop per node).  x: [N, C] with contiguous rows (any row stride).
+    The adjoint w.r.t. x is the same call on the plan of the flipped edge list with the same dis."""
+    require_cuda(x, dis)
+    ldx = _row_block(x, "gcn_pyg_propagate: x")
+    N, Cc = x.shape
+    if plan.N != N or dis.numel() != N or dis.dtype != torch.float32 or not dis.is_contiguous():
+        raise ValueError(f"gcn_pyg_propagate: x has {N} rows, the plan {plan.N} nodes and dis {dis.numel()} entries")
+    if out is None:
+        out = torch.empty(N, Cc, dtype=torch.float32, device=x.device)
+    elif out.shape != x.shape:
+        raise ValueError("gcn_pyg_propagate: out must be an [N, C] block")
+    ldo = _row_block(out, "gcn_pyg_propagate: out")
+    if N == 0:
+        return out
+    with _span("sn_gcn_pyg_propagate_f32"):
+        check(lib().sn_gcn_pyg_propagate_f32(ptr(x), ldx, N, Cc, plan.E, ptr(plan.rowptr), ptr(plan.col), ptr(dis), ptr(out), ldo, stream()),
+              "sn_gcn_pyg_propagate_f32")
+    return out

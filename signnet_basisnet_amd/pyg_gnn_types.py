@@ -1,0 +1,333 @@
+"""The plain GNN of GINESignNetPyG for every `model.gnn_type` (train/zinc.py:31-46: for anything but 'SignNet' the script builds
+`GNN(None, None, nhid, 1, nlayer, gnn_type, dropout, pool, res=True)`, core/model.py:9-79) over the five wrappers of
+core/model_utils/pyg_gnn_wrapper.py: GINEConv (pyg.GNN, unchanged), GINConv, GCNConv, GATConv and SimplifiedPNAConv.
+
+The four wrappers keep the reference's constructors and the `state_dict` keys it produces over torch_geometric 2.0.1 (restated from
+that release's documented modules; PyG is not a dependency):
+
+  GINConv            nn.layers.{0,1}.{weight,bias} (MLP(..., with_norm=False): both Linears keep their bias, no BatchNorm), the same
+                     MLP a second time under layer.nn.*, layer.eps.  edge_attr is ignored (:15-16).
+  GCNConv            layer.lin.weight (+ layer.bias when bias=True; GNN passes bias=not bn, so never here).
+  GATConv            layer.att_src, layer.att_dst [1, heads, out], layer.lin_src.weight and its alias layer.lin_dst.weight.
+  SimplifiedPNAConv  pre_nn.*, post_nn.* (MLP: layers.{0,1}, norms.{0,1} — norms.1 is registered and never called), deg_embedder.weight.
+
+Launches per layer (eval; the train forward puts a statistics launch in front of every BatchNorm):
+  GINConv   sn_gin_aggregate_f32, Linear+ReLU, Linear with the layer's BatchNorm, ReLU and residual in its epilogue
+  GCNConv   sn_gcn_pyg_propagate_f32 (PyG's normalisation, csrc/pyg_gcn.hip), then ONE GEMM with BatchNorm, ReLU and residual folded in:
+            D^-1/2 (A+I) D^-1/2 (x W^T) = (D^-1/2 (A+I) D^-1/2 x) W^T, so the propagation runs first
+  GATConv   Linear, sn_gat_conv_f32 (act none, bias NULL) on the batch's CSR without the input self loops, BatchNorm+ReLU+residual
+  SimplifiedPNAConv   A|B = x [W1[:, :d]; W1[:, d:2d]]^T in one GEMM, Q = e W1[:, 2d:]^T, sn_spna_mean_f32 (train: sn_spna_stats_f32 in
+            front), the W2 GEMM on the [N, 3d] mean with rows of in-degree 0 written as zero, the degree embedding, then post_nn as two
+            GEMMs over cat[x, W2-mean, deg_emb] (one 384-wide GEMM at d = 128: sn_masked_linear_f32 has no width limit)
+
+Not built, as in pyg.GNN: dropout > 0, res=False, bn=False, dos_bins > 0; SimplifiedPNAConv with aggregators other than ['mean'] (GNN
+cannot reach them) or nhid > 128.  These nets train eagerly (no captured step).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from . import pyg as _pyg
+from .filter_baselines import _glorot, _operator_pair
+from .pyg import MLP, DiscreteEncoder, GINEConv, _BN, _GINEps, _Identity, _eval_cache, _lin_bn, _pack
+
+GNN_TYPES = ("GINEConv", "GINConv", "GCNConv", "GATConv", "SimplifiedPNAConv")
+PNA_MAX_HIDDEN = ops.SPNA_MAX_CHANNELS // 3          # 128: C = 3 * nhid channels per edge row
+DEG_VOCAB = 200                                      # pyg_gnn_wrapper.py:61
+
+
+class GINConv(nn.Module):
+    def __init__(self, nin, nout, bias=True):
+        super().__init__()
+        self.nn = MLP(nin, nout, 2, False, bias=bias, with_norm=False)      # pyg_gnn_wrapper.py:10 ("Do not use BN")
+        self.layer = _GINEps(self.nn)
+
+    def reset_parameters(self):
+        self.nn.reset_parameters()
+        self.layer.reset_parameters()
+
+
+class _GCNLayer(nn.Module):
+    def __init__(self, nin, nout, bias):
+        super().__init__()
+        self.lin = nn.Linear(nin, nout, bias=False)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(nout))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot(self.lin.weight)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+
+class GCNConv(nn.Module):
+    def __init__(self, nin, nout, bias=True):
+        super().__init__()
+        self.layer = _GCNLayer(nin, nout, bias)
+
+    def reset_parameters(self):
+        self.layer.reset_parameters()
+
+
+class _GATLayer(nn.Module):
+    def __init__(self, nin, nout, heads, bias):
+        super().__init__()
+        self.heads, self.out_channels, self.negative_slope = heads, nout, 0.2
+        self.lin_src = nn.Linear(nin, heads * nout, bias=False)
+        self.lin_dst = self.lin_src
+        self.att_src = nn.Parameter(torch.empty(1, heads, nout))
+        self.att_dst = nn.Parameter(torch.empty(1, heads, nout))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(heads * nout))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot(self.lin_src.weight)
+        _glorot(self.att_src)
+        _glorot(self.att_dst)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+
+class GATConv(nn.Module):
+    def __init__(self, nin, nout, bias=True, nhead=1):
+        super().__init__()
+        mh, mc = 16, 128            # sn_gat_conv_max_heads / sn_gat_conv_max_channels (checked against the library in forward)
+        if nhead < 1 or nout % nhead:
+            raise ValueError(f"GATConv: nout = {nout} is not a multiple of nhead = {nhead}")
+        if nhead > mh or nout // nhead > mc:
+            raise ValueError(f"GATConv: nhead = {nhead}, {nout // nhead} channels per head is beyond the kernel's limits ({mh}, {mc})")
+        self.layer = _GATLayer(nin, nout // nhead, nhead, bias)
+
+    def reset_parameters(self):
+        self.layer.reset_parameters()
+
+
+class SimplifiedPNAConv(nn.Module):
+    def __init__(self, nin, nout, bias=True, aggregators=("mean",), **kwargs):
+        super().__init__()
+        if list(aggregators) != ["mean"]:
+            raise NotImplementedError(f"SimplifiedPNAConv: only aggregators=['mean'] is built on the HIP path (got {list(aggregators)!r})")
+        if kwargs:
+            raise NotImplementedError(f"SimplifiedPNAConv: MessagePassing options {sorted(kwargs)} are not built on the HIP path")
+        if nin != nout:
+            raise NotImplementedError("SimplifiedPNAConv: nin != nout is not built on the HIP path (GNN builds nhid -> nhid)")
+        if nin > PNA_MAX_HIDDEN:
+            raise ValueError(f"SimplifiedPNAConv: width {nin} > {PNA_MAX_HIDDEN} is not served (the message kernel takes 3 * width <= "
+                             f"{ops.SPNA_MAX_CHANNELS} channels)")
+        self.aggregators = list(aggregators)
+        self.pre_nn = MLP(3 * nin, nin, 2, False)
+        self.post_nn = MLP(3 * nin, nout, 2, False, bias=bias)
+        self.deg_embedder = nn.Embedding(DEG_VOCAB, nin)
+
+    def reset_parameters(self):
+        self.pre_nn.reset_parameters()
+        self.post_nn.reset_parameters()
+        self.deg_embedder.reset_parameters()
+
+
+_WRAPPERS = {"GINEConv": GINEConv, "GINConv": GINConv, "GCNConv": GCNConv, "GATConv": GATConv, "SimplifiedPNAConv": SimplifiedPNAConv}
+
+
+def _gat_operator(data, N):
+    """The batch's CSR by destination without the input self loops, and its transpose (the adjoint's), once per forward."""
+    ei = data.edge_index
+    keep = ei[0] != ei[1]
+    s, t = ei[0][keep], ei[1][keep]
+    return _operator_pair(s, t, torch.ones(s.numel(), dtype=torch.float32, device=ei.device), N)
+
+
+class GNN(_pyg.GNN):
+    """core/model.py's GNN with the reference's signature, for the five gnn_type values.  'GINEConv' is pyg.GNN itself (same launches, bit
+    for bit).  Three modes: eval, the train-mode forward without autograd (batch statistics, running-statistics update) and the
+    differentiable train-mode forward."""
+
+    def __init__(self, nfeat_node, nfeat_edge, nhid, nout, nlayer, gnn_type, dropout=0, pooling="add", bn=True, dos_bins=0, res=True):
+        if gnn_type not in _WRAPPERS:
+            raise ValueError(f"GNN: unknown gnn_type {gnn_type!r}; one of {', '.join(GNN_TYPES)}")
+        if not bn or dos_bins:
+            raise NotImplementedError("GNN: bn=False and dos_bins > 0 are not built on the HIP path")
+        super().__init__(nfeat_node, nfeat_edge, nhid, nout, nlayer, "gine", pooling, dropout=dropout, res=res)
+        self.gnn_type = gnn_type
+        if gnn_type != "GINEConv":
+            self.convs = nn.ModuleList([_WRAPPERS[gnn_type](nhid, nhid, bias=not bn) for _ in range(nlayer)])      # core/model.py:15
+
+    # ------------------------------------------------------------------ what the convs share per forward
+    def _check_edge_ids(self, ea, status):
+        """The edge-blind convs never read the edge embeddings, but the reference computes them (core/model.py:61) and nn.Embedding raises for
+        an id outside its table: the first layer's tables (all layers' have one size) are looked up once, for the range check alone."""
+        enc = self.edge_encoders[0]
+        if isinstance(enc, DiscreteEncoder) and ea.numel():
+            ops.embedding_sum(ea, [e.weight.detach() for e in enc.embeddings], status)
+
+    @staticmethod
+    def _degrees(plan):
+        deg = plan.rowptr[1:] - plan.rowptr[:-1]                  # in-degree, int32 [N]
+        return deg.long(), deg.clamp(max=1).contiguous()
+
+    # ------------------------------------------------------------------ eval / train value without autograd
+    def _forward_layers(self, data, ea, additional_x, train):
+        if self.gnn_type == "GINEConv":
+            return super()._forward_layers(data, ea, additional_x, train)
+        fold = not train
+        kind = self.gnn_type
+        plan = ops.build_plan(data.batch, data.edge_index, int(data.num_graphs), 0)
+        status = plan.status[5:6]
+        cache = _eval_cache(self) if fold else {}
+
+        def cached(key, make):
+            if key not in cache:
+                cache[key] = make()
+            return cache[key]
+
+        def pack(lin):
+            return cached(id(lin), lambda: _pack(lin))
+
+        def bn_of(norm):
+            return cached(id(norm), lambda: _BN(norm, fold))
+
+        def lin_bn(x, lin, norm, relu=True, residual=None):
+            if isinstance(norm, _Identity):
+                return ops.masked_linear(x, pack(lin), relu=relu, residual=residual)
+            return _lin_bn(x, pack(lin), bn_of(norm), train, relu=relu, residual=residual)
+
+        def bn_act(z, norm, residual):
+            """BatchNorm -> ReLU -> + residual on a materialised z (behind an aggregation: no GEMM epilogue to fold into)."""
+            if fold:
+                b = bn_of(norm)
+                return ops.masked_affine(z, scale=b.scale, shift=b.shift, relu=True, residual=residual)
+            _, _, _, sc, sh, _ = ops.bn_train_stats(z, norm)
+            return ops.masked_affine(z, scale=sc, shift=sh, relu=True, residual=residual)
+
+        def encode(enc, v):
+            if isinstance(enc, DiscreteEncoder):
+                return ops.embedding_sum(v, [e.weight.detach() for e in enc.embeddings], status)
+            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+
+        h = encode(self.input_encoder, self._node_ids(data))
+        if additional_x is not None:
+            h = ops.masked_linear(torch.cat([h, additional_x], dim=-1), pack(self.linear))
+        if kind != "SimplifiedPNAConv":
+            self._check_edge_ids(ea, status)
+        if kind == "GCNConv":
+            dis = ops.gcn_pyg_coef(plan)
+        elif kind == "GATConv":
+            op = _gat_operator(data, plan.N)
+        elif kind == "SimplifiedPNAConv":
+            deg, has_in = self._degrees(plan)
+        for enc, conv, norm in zip(self.edge_encoders, self.convs, self.norms):
+            if kind == "GINConv":
+                u = ops.gin_aggregate(h, plan, conv.layer.eps.detach())
+                u = ops.masked_linear(u, pack(conv.nn.layers[0]), relu=True)
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+            elif kind == "GCNConv":
+                h = lin_bn(ops.gcn_pyg_propagate(h, plan, dis), conv.layer.lin, norm, residual=h)
+            elif kind == "GATConv":
+                L = conv.layer
+                f = ops.masked_linear(h, pack(L.lin_src))
+                z, _ = ops.gat_conv(f, L.att_src.detach(), L.att_dst.detach(), None, op, L.heads, None, L.negative_slope)
+                h = bn_act(z, norm, h)
+            else:
+                d = h.shape[1]
+                W1 = conv.pre_nn.layers[0].weight.detach()
+                pab = cached(("ab", id(conv)), lambda: ops.PackedLinear(ops.pack_weight(torch.cat([W1[:, :d], W1[:, d:2 * d]], 0).contiguous()),
+                                                                        6 * d, d, None))
+                pq = cached(("q", id(conv)), lambda: ops.PackedLinear(ops.pack_weight(W1[:, 2 * d:].contiguous()), 3 * d, d, None))
+                ab = ops.masked_linear(h, pab)                                        # [N, 2C]: A | B
+                q = ops.masked_linear(encode(enc, ea), pq)                            # [E, C]
+                a, b = ab[:, :3 * d], ab[:, 3 * d:]
+                bn0 = conv.pre_nn.norms[0]
+                if fold:
+                    f0 = bn_of(bn0)
+                    r = ops.spna_mean(a, b, q, plan, f0.scale, f0.shift)
+                else:
+                    state, _ = ops.spna_stats(a, b, q, plan, bn0)
+                    r = ops.spna_mean(a, b, q, plan, state[3], state[4])
+                m = ops.masked_linear(r, pack(conv.pre_nn.layers[1]), has_in, 1)      # W2 mean + b2 [deg > 0]
+                de = ops.embedding_sum(deg, [conv.deg_embedder.weight.detach()], status)
+                u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0])
+                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=h)
+        pooled = ops.segment_pool(h, plan, self.pooling)
+        if self.pooling == "mean":
+            size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], status)
+            pooled = ops.masked_affine(pooled, residual=size)
+        oe = self.output_encoder
+        y = ops.masked_linear(lin_bn(pooled, oe.layers[0], oe.norms[0]), pack(oe.layers[1]))
+        plan.check()
+        return y
+
+    # ------------------------------------------------------------------ differentiable train mode
+    def _forward_grad(self, data, ea, additional_x):
+        if self.gnn_type == "GINEConv":
+            return super()._forward_grad(data, ea, additional_x)
+        from . import autograd as AG
+        from . import train_stage as T
+        kind = self.gnn_type
+        B = int(data.num_graphs)
+        plan = ops.build_plan(data.batch, data.edge_index, B, 0)
+        rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
+        status = plan.status[5:6]
+        d = self.linear.weight.shape[0]
+        stage = T.supported(d, d)
+
+        def lin_bn(x, lin, norm, relu=True, residual=None):
+            if isinstance(norm, _Identity):
+                y = AG.linear(x, lin.weight, lin.bias, None, 0, relu=relu)
+                return y if residual is None else AG.masked_add(y, residual, None, 0)
+            if stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
+                return T.lin_bn(x, lin, norm, None, 0, relu=relu, residual=residual)
+            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, None, 0, relu=relu, residual=residual)
+
+        def encode(enc, v):
+            if isinstance(enc, DiscreteEncoder):
+                return AG.embedding_sum(v, [e.weight for e in enc.embeddings], status)
+            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+
+        h = encode(self.input_encoder, self._node_ids(data))
+        if additional_x is not None:
+            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, None, 0)
+        if kind != "SimplifiedPNAConv":
+            self._check_edge_ids(ea, status)
+        if kind == "GCNConv":
+            dis = ops.gcn_pyg_coef(plan)
+        elif kind == "GATConv":
+            op = _gat_operator(data, plan.N)
+        elif kind == "SimplifiedPNAConv":
+            deg, has_in = self._degrees(plan)
+        for enc, conv, norm in zip(self.edge_encoders, self.convs, self.norms):
+            if kind == "GINConv":
+                u = AG.gin_aggregate(h, conv.layer.eps, plan, rplan)
+                u = AG.linear(u, conv.nn.layers[0].weight, conv.nn.layers[0].bias, None, 0, relu=True)
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+            elif kind == "GCNConv":
+                h = lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), conv.layer.lin, norm, residual=h)
+            elif kind == "GATConv":
+                L = conv.layer
+                f = AG.linear(h, L.lin_src.weight, None, None, 0)
+                z = AG.gat_conv(f, L.att_src, L.att_dst, None, op, L.heads, None, L.negative_slope)
+                h = AG.bn_act(z, norm, None, 0, relu=True, residual=h)
+            else:
+                W1 = conv.pre_nn.layers[0].weight
+                ab = AG.linear(h, torch.cat([W1[:, :d], W1[:, d:2 * d]], 0), None, None, 0)
+                q = AG.linear(encode(enc, ea), W1[:, 2 * d:], None, None, 0)
+                r = AG.spna_mean(ab, q, conv.pre_nn.norms[0], plan, rplan)
+                l1 = conv.pre_nn.layers[1]
+                m = AG.linear(r, l1.weight, l1.bias, has_in, 1)
+                de = AG.embedding_sum(deg, [conv.deg_embedder.weight], status)
+                u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0])
+                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=h)
+        pooled = AG.segment_pool(h, plan, self.pooling)
+        if self.pooling == "mean":
+            pooled = AG.masked_add(pooled, AG.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight], status), None, 0)
+        oe = self.output_encoder
+        y = lin_bn(pooled, oe.layers[0], oe.norms[0])
+        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, None, 0)
+        plan.check()
+        return y
