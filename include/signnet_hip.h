@@ -1308,6 +1308,22 @@ int sn_gcn_pyg_coef_f32(int64_t N, int64_t E, const int32_t* rowptr, const int32
 int sn_gcn_pyg_propagate_f32(const float* x, int64_t ldx, int64_t N, int C, int64_t E, const int32_t* rowptr, const int32_t* col,
                              const float* dis, float* out, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Train-mode dropout with a counter-based mask (F.dropout / nn.Dropout of the reference's plain GNN and DGL nets):
+ *   y[r,c] = (keep(r,c) ? x[r,c] * scale : 0) + (residual ? residual[r,c] : 0)                      x, y, residual: [R, C]
+ * The mask is a pure function of (seed, step, site, logical index) and is stored nowhere:
+ *   i    = base + r*C + c                      (logical index: independent of ldx / ldr / ldy and of the pointers)
+ *   w    = philox4x32_10(counter = (lo32(i>>2), hi32(i>>2), site, lo32(step)), key = (lo32(seed), hi32(seed)))
+ *   keep = w[i & 3] >= threshold               (the host passes threshold = floor(p * 2^32) in double precision — p = 1 is the
+ *                                               caller's case — and scale = float32(1 / (1 - p)))
+ * state: int64[2] = {seed, step} in DEVICE memory, read by the kernel when it runs: a replay of a captured graph sees the current
+ * step.  The backward is the same call on dy with residual = NULL (the residual's gradient is dy itself): no second kernel, no saved
+ * mask.  x and y must not overlap.  16-byte accesses (one generator call per access) when C % 4 == 0, base % 4 == 0, every ld % 4
+ * == 0 and every pointer is 16-byte aligned; otherwise a scalar path that takes any C, any ld >= C, 4-byte-aligned pointers and any
+ * base >= 0 — the mask is the same on both.  R = 0: SN_OK, no launch.  Columns C..ld of y are never written. */
+int sn_dropout_f32(const float* x, int ldx, int64_t R, int C, uint32_t threshold, float scale, const int64_t* state, uint32_t site,
+                   int64_t base, const float* residual, int ldr, float* y, int ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

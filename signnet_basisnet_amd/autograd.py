@@ -1037,3 +1037,31 @@ class _GcnPygPropagate(Function):
 def gcn_pyg_propagate(x, plan, rplan, dis):
     """D^-1/2 (A + I) D^-1/2 x in torch_geometric's normalisation; the adjoint is the same launch on the flipped plan."""
     return _GcnPygPropagate.apply(x, plan, rplan, dis)
+
+
+# ----------------------------------------------------------------------------- train-mode dropout (csrc/dropout.hip)
+class _Dropout(Function):
+    """keep * x / (1 - p) + residual with the counter-based mask of sn_dropout_f32.  Only `snap` ({seed, step}) is saved: the
+    backward regenerates the mask with the same launch on dy; the residual's gradient is dy itself."""
+
+    @staticmethod
+    def forward(ctx, x, residual, p, snap, site):
+        ctx.save_for_backward(snap)
+        ctx.meta = (p, site, residual is not None)
+        return ops.dropout(_c(x), p, snap, site, residual=None if residual is None else _c(residual))
+
+    @staticmethod
+    def backward(ctx, g):
+        snap, = ctx.saved_tensors
+        p, site, has_res = ctx.meta
+        g = _c(g)
+        return ops.dropout(g, p, snap, site), (g if has_res else None), None, None, None
+
+
+def dropout(x, p, snap, site, residual=None):
+    p = float(p)
+    if p < 0.0 or p > 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    if p == 0.0:
+        return x if residual is None else act_residual(x, residual)
+    return _Dropout.apply(x, residual, p, snap, site)

@@ -135,10 +135,12 @@ def _prep_mlp(mlp: MLP, train=False):
     return out
 
 
-def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False):
-    """mlp.py:37-56 (dropout 0): hidden layers = bias -> relu -> BN; the final Linear optionally followed by the
+def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None):
+    """mlp.py:37-56: hidden layers = bias -> relu -> BN [-> dropout]; the final Linear optionally followed by the
     BatchNorm that GIN.forward applies before the NEXT GINConv (gnns.py:105-112; in eval folded into the GEMM epilogue).
-    train: BatchNorm over ALL rows of the layer (the reference normalises [N, C, K] tensors, padded slots included)."""
+    train: BatchNorm over ALL rows of the layer (the reference normalises [N, C, K] tensors, padded slots included).
+    drop = (p, snap, first site): the train-mode dropout behind hidden layer i (mlp.py:51) is site `first + i` of ops.dropout on the
+    [R, C] rows (GINNet only: the sign-invariant encoders' [N, C, K] tensors are laid out differently here and refuse dropout)."""
     for i, (pl, bn) in enumerate(prep):
         last = i == len(prep) - 1
         site = tail_bn if last else bn
@@ -150,6 +152,8 @@ def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False):
             if site is not None:
                 sc, sh = site.affine(x, True)
                 x = ops.masked_affine(x, scale=sc, shift=sh)
+            if drop is not None and not last and drop[0]:
+                x = ops.dropout(x, drop[0], drop[1], drop[2] + i)
     return x
 
 

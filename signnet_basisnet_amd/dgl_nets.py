@@ -138,10 +138,11 @@ class _PackCache:
         return _prep_mlp(mlp, True) if train else self._cached(id(mlp), lambda: _prep_mlp(mlp, False))
 
 
-class _DGLNet(_PackCache, nn.Module):
+class _DGLNet(ops.DropoutHolder, _PackCache, nn.Module):
     """What GINNet, GatedGCNNet, PNANet, TransformerNet and GATNet share.  A net's __init__ is `_init_common`, its own layers,
     `_init_tail`; its forward is `_prologue`, then `_encode` / its layer loop / `_readout` (or their `_grad` forms)."""
 
+    _feature_dropout = False # dropout / in_feat_dropout > 0 are refused, as before; dropout_models.py's subclasses set True
     _stage_cls = None        # the packer of the net's one-launch eval kernel (_FusedGin, _FusedGated, _FusedTransformer), if it has one
     _stage_edges = 192       # the most in-edges of a graph that kernel holds; None: the packer's own `max_edges`
     _malformed_note = ""     # check_last()'s wording of a malformed batch and of the size limit
@@ -149,7 +150,7 @@ class _DGLNet(_PackCache, nn.Module):
 
     def _init_common(self, net_params, name, refusals, *, edge_dim=None, in_feat_dropout=None):
         """The constructor's head: the attributes every net reads from `net_params`, the refusals — the PE switches, then `refusals`
-        ((condition, what the net covers instead) pairs, in order), then dropout — and the input embeddings.  `edge_dim`: the width of
+        ((condition, what the net covers instead) pairs, in order) —, the two dropout probabilities and the input embeddings.  `edge_dim`: the width of
         embedding_e where it is not hidden_dim; `in_feat_dropout`: where the reference registers its nn.Dropout ('before_h': in front
         of embedding_h, 'after_e': behind embedding_e; None: the net has none)."""
         p = net_params
@@ -164,16 +165,20 @@ class _DGLNet(_PackCache, nn.Module):
         for refused, covered in refusals:
             if refused:
                 raise NotImplementedError(f"HIP {name}: {covered}")
-        if p.get("in_feat_dropout", 0.0) or p.get("dropout", 0.0):
+        # train-mode dropout (ops.dropout: counter-based masks, site = the ordinal of the reference forward's dropout call; site 0 is
+        # in_feat_dropout).  Eval never reads either value.
+        self.p_in_feat = ops.check_dropout_p(p.get("in_feat_dropout", 0.0), f"HIP {name}: in_feat_dropout")
+        self.p_drop = ops.check_dropout_p(p.get("dropout", 0.0), f"HIP {name}: dropout")
+        if (self.p_in_feat or self.p_drop) and not self._feature_dropout:      # opt-in: the classes of dropout_models.py take it
             raise NotImplementedError(f"HIP {name}: dropout 0.0 (as in the shipped configs)")
         if self.pe_init == "lap_pe":
             self.embedding_p = nn.Linear(self.pos_enc_dim, hidden)
         if in_feat_dropout == "before_h":
-            self.in_feat_dropout = nn.Dropout(0.0)
+            self.in_feat_dropout = nn.Dropout(self.p_in_feat)
         self.embedding_h = nn.Embedding(p["num_atom_type"], hidden)
         self.embedding_e = nn.Embedding(p["num_bond_type"], edge_dim or hidden) if self.edge_feat else nn.Linear(1, hidden)
         if in_feat_dropout == "after_e":
-            self.in_feat_dropout = nn.Dropout(0.0)
+            self.in_feat_dropout = nn.Dropout(self.p_in_feat)
 
     def _init_tail(self, net_params):
         """The constructor's tail, behind the net's own layers: the read-out MLP, `g`, sign_inv_net and pe_proj, in the reference's order."""
@@ -198,6 +203,10 @@ class _DGLNet(_PackCache, nn.Module):
         grad = train and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())
         return pe, N, h.long().reshape(N), p.contiguous().float() if pe else None, train, grad
 
+    def _drop_snap(self, train, device):
+        """The {seed, step} snapshot of this train-mode forward (the step advances once, here), or None when no site is active."""
+        return self._dropout_begin(device) if train and self._dropout_active() else None
+
     def _plan(self, g, N):
         src, dst = g.edges()
         bnn = g.batch_num_nodes().to(src.device)
@@ -209,9 +218,12 @@ class _DGLNet(_PackCache, nn.Module):
         batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)      # index plumbing only
         return batch.long(), torch.stack([src.long(), dst.long()]), B
 
-    def _encode(self, x, p):
+    def _encode(self, x, p, snap=None):
         """The input encoder of the value paths behind x = embedding_h(h): h + embedding_p(p), or pe_proj(cat[h, embedding_p(p)]) for
-        pe_aggregate 'concat' (gatedgcn_net.py:93-103, transformer_net.py:96-102); NoPE leaves h alone."""
+        pe_aggregate 'concat' (gatedgcn_net.py:93-103, transformer_net.py:96-102); NoPE leaves h alone.  snap: a train-mode forward's
+        dropout snapshot — in_feat_dropout (site 0) acts on embedding_h(h) first."""
+        if snap is not None and self.p_in_feat:
+            x = ops.dropout(x, self.p_in_feat, snap, 0)
         if self.pe_init != "lap_pe":
             return x
         if getattr(self, "pe_aggregate", "add") == "concat":
@@ -219,9 +231,11 @@ class _DGLNet(_PackCache, nn.Module):
             return ops.masked_linear(torch.cat([x, pp], dim=1), self._pk(self.pe_proj))
         return ops.masked_linear(p, self._pk(self.embedding_p), residual=x)
 
-    def _encode_grad(self, hidx, p, vN, k1):
+    def _encode_grad(self, hidx, p, vN, k1, snap=None):
         """embedding_h and the input encoder as autograd nodes (vN, k1: the valid rows of a padded batch, see _bucket_rows)."""
         x = AG.embedding_sum(hidx, [self.embedding_h.weight])
+        if snap is not None and self.p_in_feat:
+            x = AG.dropout(x, self.p_in_feat, snap, 0)
         if self.pe_init != "lap_pe":
             return AG.mask_rows(x, vN, k1)
         pp = AG.linear(p, self.embedding_p.weight, self.embedding_p.bias, vN, k1)
@@ -367,10 +381,10 @@ class GINNet(_DGLNet):
         super().__init__()
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self._init_common(p, "GINNet", [(p["readout"] == "max", "readout 'sum' or 'mean'")])      # (embedding_e: unused by GIN)
+        self._init_common(p, "GINNet", [(p["readout"] == "max", "readout 'sum' or 'mean'")], in_feat_dropout="after_e")      # (embedding_e: unused by GIN)
         self.layers = nn.ModuleList(
-            [_GINConv(MLP(hidden, hidden, hidden, 2, use_bn=self.batch_norm, dropout=0.0, activation="relu")) for _ in range(self.n_layers - 1)] +
-            [_GINConv(MLP(hidden, hidden, out_dim, 2, use_bn=self.batch_norm, dropout=0.0, activation="relu"))])
+            [_GINConv(MLP(hidden, hidden, hidden, 2, use_bn=self.batch_norm, dropout=self.p_drop, activation="relu")) for _ in range(self.n_layers - 1)] +
+            [_GINConv(MLP(hidden, hidden, out_dim, 2, use_bn=self.batch_norm, dropout=self.p_drop, activation="relu"))])
         self._init_tail(p)
 
     def _gin_padded(self):
@@ -456,10 +470,14 @@ class GINNet(_DGLNet):
                                                          stream()), "sn_mlp_chain_f32")
                     y = self._readout(x, plan, first=P["fc0"])
                 else:
-                    x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)          # h + embedding_p(p)   (:87-92)
+                    snap = self._drop_snap(train, h.device)
+                    x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)          # h + embedding_p(p)   (:87-92)
+                    site = 1                # mlp.py:51: one dropout behind every hidden layer of every GINConv's MLP, in forward order
                     for conv in self.layers:
                         a = ops.gin_aggregate(x, plan, conv.eps)
-                        x = _run_mlp(self._mlp(conv.apply_func, train), a, train=train)
+                        mlp = conv.apply_func
+                        x = _run_mlp(self._mlp(mlp, train), a, train=train, drop=(mlp.dropout, snap, site) if snap is not None else None)
+                        site += len(mlp.lins) - 1
                     y = self._readout(x, plan)
         self.g = g
         return y, g
@@ -467,7 +485,9 @@ class GINNet(_DGLNet):
     def _forward_grad(self, plan, batch, ei, B, hidx, p):
         vN, _, vB, k1 = _bucket_rows(self)          # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-        x = self._encode_grad(hidx, p, vN, k1)
+        snap = self._drop_snap(True, hidx.device)
+        x = self._encode_grad(hidx, p, vN, k1, snap)
+        site = 1
         for conv in self.layers:
             mlp = conv.apply_func
             a = AG.gin_aggregate(x, conv.eps, plan, rplan)
@@ -476,6 +496,10 @@ class GINNet(_DGLNet):
                 a = AG.linear(a, lin.weight, lin.bias, vN, k1, relu=i < n - 1)
                 if mlp.use_bn and i < n - 1:
                     a = AG.bn_act(a, mlp.bns[i], vN, k1, relu=False)
+                if i < n - 1:
+                    if mlp.dropout:
+                        a = AG.dropout(a, mlp.dropout, snap, site)
+                    site += 1
             x = a
         return self._readout_grad(x, plan, vB, k1)
 
@@ -484,10 +508,11 @@ class GINNet(_DGLNet):
 class GatedGCNLayer(nn.Module):
     """layers/gatedgcn_layer.py:12-81 (parameters only; the arithmetic is in GatedGCNNet.forward)."""
 
-    def __init__(self, input_dim, output_dim, dropout, batch_norm, residual=False, graph_norm=True):
+    def __init__(self, input_dim, output_dim, dropout, batch_norm, residual=False, graph_norm=True, feature_dropout=False):
         super().__init__()
-        if dropout or graph_norm:
+        if (dropout and not feature_dropout) or graph_norm:
             raise NotImplementedError("HIP GatedGCNLayer: dropout 0.0 and graph_norm=False (what gatedgcn_net.py builds for lap_pe)")
+        self.dropout = ops.check_dropout_p(dropout, "HIP GatedGCNLayer")
         self.in_channels, self.out_channels = input_dim, output_dim
         self.batch_norm, self.residual = batch_norm, residual and input_dim == output_dim
         for n in "ABCDE":
@@ -587,10 +612,12 @@ class GatedGCNNet(_DGLNet):
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
         self.pe_aggregate = p["pe_aggregate"]
         self._init_common(p, "GatedGCNNet", [(p["readout"] == "max" or not p["edge_feat"] or not p["batch_norm"],
-                                              "readout sum/mean, edge_feat=True, batch_norm=True")])
-        self.layers = nn.ModuleList([GatedGCNLayer(hidden, hidden, 0.0, True, residual=self.residual, graph_norm=False)
+                                              "readout sum/mean, edge_feat=True, batch_norm=True")], in_feat_dropout="after_e")
+        self.layers = nn.ModuleList([GatedGCNLayer(hidden, hidden, self.p_drop, True, residual=self.residual, graph_norm=False,
+                                                   feature_dropout=self._feature_dropout)
                                      for _ in range(self.n_layers - 1)] +
-                                    [GatedGCNLayer(hidden, out_dim, 0.0, True, residual=self.residual, graph_norm=False)])
+                                    [GatedGCNLayer(hidden, out_dim, self.p_drop, True, residual=self.residual, graph_norm=False,
+                                                  feature_dropout=self._feature_dropout)])
         self._init_tail(p)
 
     _fused_gated = _DGLNet._stage        # (the name the topology tests ask by)
@@ -647,9 +674,10 @@ class GatedGCNNet(_DGLNet):
             e = ops.embedding_sum(eidx, [self.embedding_e.weight], status=st5)
             self._last_plan = plan
             return fused.run(plan, x, e)
-        x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)
+        snap = self._drop_snap(train, hidx.device)
+        x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)
         e = ops.embedding_sum(eidx, [self.embedding_e.weight])
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             if not train:
                 # eval: A, B, D, E as ONE GEMM ([4d, d] weight, column blocks of the result go to the gather kernel by stride),
                 # BatchNorm (folded) + ReLU + residual of both h and e fused into the gather pass: 3 launches per layer
@@ -669,19 +697,26 @@ class GatedGCNNet(_DGLNet):
             x = ops.masked_affine(h2, scale=sc, shift=sf, relu=True, residual=x if L.residual else None)
             sc, sf = se.affine(e2, train)
             e = ops.masked_affine(e2, scale=sc, shift=sf, relu=True, residual=e if L.residual else None)
+            if L.dropout:           # gatedgcn_layer.py:74-75: h and e behind the residual, sites 1 + 2l and 2 + 2l
+                x = ops.dropout(x, L.dropout, snap, 1 + 2 * li)
+                e = ops.dropout(e, L.dropout, snap, 2 + 2 * li)
         return self._readout(x, plan)
 
     def _forward_grad(self, plan, batch, ei, B, hidx, p, eidx):
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-        x = self._encode_grad(hidx, p, vN, k1)
+        snap = self._drop_snap(True, hidx.device)
+        x = self._encode_grad(hidx, p, vN, k1, snap)
         e = AG.embedding_sum(eidx, [self.embedding_e.weight])
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             Ah, Bh, Dh, Eh = (AG.linear(x, getattr(L, n).weight, getattr(L, n).bias, vN, k1) for n in "ABDE")
             Ce = AG.linear(e, L.C.weight, L.C.bias, vE, k1)
             h2, e2 = AG.gated_aggregate(Ah, Bh, Dh, Eh, Ce, plan, rplan)
             x = AG.bn_act(h2, L.bn_node_h, vN, k1, relu=True, residual=x if L.residual else None)
             e = AG.bn_act(e2, L.bn_node_e, vE, k1, relu=True, residual=e if L.residual else None)
+            if L.dropout:
+                x = AG.dropout(x, L.dropout, snap, 1 + 2 * li)
+                e = AG.dropout(e, L.dropout, snap, 2 + 2 * li)
         return self._readout_grad(x, plan, vB, k1)
 
 
@@ -709,21 +744,22 @@ class _PnaMLP(nn.Module):
 
 
 class PNATower(nn.Module):
-    def __init__(self, in_dim, out_dim, edge_dim):
+    def __init__(self, in_dim, out_dim, edge_dim, dropout=0.0):
         super().__init__()
+        self.dropout = ops.check_dropout_p(dropout, "HIP PNATower")          # pna_layer.py:79, behind the BatchNorm
         self.batchnorm_h = nn.BatchNorm1d(out_dim)
         self.pretrans_h = _PnaMLP(2 * in_dim + edge_dim, in_dim, in_dim, 1)
         self.posttrans_h = _PnaMLP(13 * in_dim, out_dim, out_dim, 1)          # (4 aggregators x 3 scalers + 1) * in_dim
 
 
 class PNALayer(nn.Module):
-    def __init__(self, in_dim, out_dim, towers, edge_dim, residual):
+    def __init__(self, in_dim, out_dim, towers, edge_dim, residual, dropout=0.0):
         super().__init__()
         if in_dim % towers or out_dim % towers:
             raise ValueError("the number of towers has to divide in_dim and out_dim")
         self.in_dim, self.out_dim, self.n_towers = in_dim, out_dim, towers
         self.residual = residual and in_dim == out_dim
-        self.towers = nn.ModuleList([PNATower(in_dim // towers, out_dim // towers, edge_dim) for _ in range(towers)])
+        self.towers = nn.ModuleList([PNATower(in_dim // towers, out_dim // towers, edge_dim, dropout) for _ in range(towers)])
         self.mixing_network_h = FCLayer(out_dim, out_dim, activation="LeakyReLU")
 
 
@@ -753,8 +789,8 @@ class PNANet(_DGLNet):
              "graph_norm, batch_norm, edge_feat True; gru False; readout sum / mean"),
             (not (p["divide_input_first"] and p["divide_input_last"]), "divide_input_first / _last True (the shipped configs)")],
             edge_dim=edge_dim, in_feat_dropout="before_h")
-        self.layers = nn.ModuleList([PNALayer(hidden, hidden, self.towers, edge_dim, self.residual) for _ in range(self.n_layers - 1)] +
-                                    [PNALayer(hidden, out_dim, self.towers, edge_dim, self.residual)])
+        self.layers = nn.ModuleList([PNALayer(hidden, hidden, self.towers, edge_dim, self.residual, self.p_drop) for _ in range(self.n_layers - 1)] +
+                                    [PNALayer(hidden, out_dim, self.towers, edge_dim, self.residual, self.p_drop)])
         if p["pretrans_layers"] != 1 or p["posttrans_layers"] != 1:
             raise NotImplementedError("HIP PNANet: pretrans_layers = posttrans_layers = 1")
         self._init_tail(p)
@@ -778,9 +814,10 @@ class PNANet(_DGLNet):
                 self.g = g
                 return hg, g
             src, dst = (t.long() for t in g.edges())
-            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)                              # h + embedding_p(p)  (:124-126)
+            snap = self._drop_snap(train, h.device)
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)                        # h + embedding_p(p)  (:124-126)
             ef = ops.embedding_sum(eidx, [self.embedding_e.weight])
-            for L in self.layers:
+            for li, L in enumerate(self.layers):
                 it = L.in_dim // L.n_towers
                 outs = []
                 for t, T in enumerate(L.towers):
@@ -796,6 +833,8 @@ class PNANet(_DGLNet):
                         y = ops.pointwise(y, rowscale=sn)
                         sc, sh = site.affine(y, True)
                         y = ops.pointwise(y, scale=sc, shift=sh)
+                        if T.dropout:          # site 1 + (layer, tower) in forward order
+                            y = ops.dropout(y, T.dropout, snap, 1 + li * L.n_towers + t)
                     outs.append(y)
                 hc = torch.cat(outs, dim=1)
                 mix = ops.masked_linear(hc, self._pk(L.mixing_network_h.linear))
@@ -916,9 +955,10 @@ class PNANet(_DGLNet):
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE: adjoint of h[src]
         src, dst = ei[0], ei[1]
-        x = self._encode_grad(hidx, p, vN, k1)
+        snap = self._drop_snap(True, hidx.device)
+        x = self._encode_grad(hidx, p, vN, k1, snap)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             it = L.in_dim // L.n_towers
             outs = []
             for t, T in enumerate(L.towers):
@@ -928,7 +968,8 @@ class PNANet(_DGLNet):
                 m = AG.linear(z, pre.weight, pre.bias, vE, k1)
                 a = AG.pna_aggregate(m, ht, plan, avg_log)
                 y = AG.act_residual(AG.linear(a, post.weight, post.bias, vN, k1), rowscale=sn)     # graph_norm: h * snorm_n
-                outs.append(AG.bn_act(y, T.batchnorm_h, vN, k1, relu=False))
+                y = AG.bn_act(y, T.batchnorm_h, vN, k1, relu=False)
+                outs.append(AG.dropout(y, T.dropout, snap, 1 + li * L.n_towers + t) if T.dropout else y)
             mixl = L.mixing_network_h.linear
             mix = AG.linear(torch.cat(outs, dim=1), mixl.weight, mixl.bias, vN, k1)
             x = AG.act_residual(mix, residual=x if L.residual else None, act="leaky", slope=0.01)
@@ -950,10 +991,13 @@ class MultiHeadAttentionLayer(nn.Module):
 
 class BatchedTransformerLayer(nn.Module):
     """layers/transformer.py:234-317 with the arguments transformer_net.py:69-70 passes (the rest at their defaults: residual,
-    batch_norm, no layer_norm, use_bias False, dropout 0)."""
+    batch_norm, no layer_norm, use_bias False).  `dropout` (:281, :299: behind the attention output and behind the FFN's ReLU) is the
+    layer's own attribute, as in the reference — whose TransformerNet never hands its net_params['dropout'] to a layer, so a net built
+    from a config keeps 0 here."""
 
-    def __init__(self, in_dim, out_dim, num_heads, full_graph, use_edge=True):
+    def __init__(self, in_dim, out_dim, num_heads, full_graph, dropout=0.0, use_edge=True):
         super().__init__()
+        self.dropout = ops.check_dropout_p(dropout, "HIP BatchedTransformerLayer")
         if full_graph or not use_edge:
             raise NotImplementedError("HIP graph Transformer: full_graph False with edge features (the shipped sign_inv configs)")
         if out_dim % num_heads or out_dim // num_heads > 32:
@@ -1113,7 +1157,9 @@ class TransformerNet(_DGLNet):
                 self._last_plan = plan
                 self.g = g
                 return fzs.run(plan, hidx.contiguous(), p if pe else _zero_pe(self, N, h.device)[:N], Ee_all), g
-            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p)                                   # (:96-102)
+            snap = self._drop_snap(train, h.device)
+            # (transformer.py:281, 299: sites 1 + 2l — attention output — and 2 + 2l — FFN hidden — of each layer's own `dropout`)
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)                             # (:96-102)
             ef = ops.embedding_sum(eidx, [self.embedding_e.weight])
             if not train and self._fusable():
                 # eval (round 4): 5 launches per layer instead of 12.  Q | K | V are ONE [3d, d] Linear whose column blocks the attention
@@ -1130,14 +1176,20 @@ class TransformerNet(_DGLNet):
                     f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
                     x = ops.masked_linear(f, self._pk(L.FFN_h_layer2), residual=x1, residual_pre=True, scale=s2.scale, shift=s2.shift)  # (:300-308)
             else:
-                for L in self.layers:
+                for li, L in enumerate(self.layers):
                     A = L.attention_h
                     Q, K, V = (ops.masked_linear(x, self._pk(getattr(A, n))) for n in "QKV")
                     Ee = ops.masked_linear(ef, self._pk(A.E))
                     a = ops.edge_attention(Q, K, V, Ee, plan, L.num_heads)                                            # (:150-228)
+                    pd = L.dropout if train else 0.0
+                    if pd:
+                        a = ops.dropout(a, pd, snap, 1 + 2 * li)
                     o = ops.masked_linear(a, self._pk(L.O_h))
                     x1 = self._bn_res(o, x, L.batch_norm1_h, train)                                                   # residual, BatchNorm (:283-290)
-                    f = ops.masked_linear(ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True), self._pk(L.FFN_h_layer2))
+                    f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
+                    if pd:
+                        f = ops.dropout(f, pd, snap, 2 + 2 * li)
+                    f = ops.masked_linear(f, self._pk(L.FFN_h_layer2))
                     x = self._bn_res(f, x1, L.batch_norm2_h, train)                                                   # (:300-308)
             hg = self._readout(x, plan)
         self.g = g
@@ -1149,17 +1201,23 @@ class TransformerNet(_DGLNet):
         pass over the reverse CSR, no atomics); BatchNorm with batch statistics, residuals, FFN as in the value path."""
         vN, vE, vB, k1 = _bucket_rows(self)         # (train_graph.DGLBucketedStep: padding rows enter no statistic and no gradient)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-        x = self._encode_grad(hidx, p, vN, k1)
+        snap = self._drop_snap(True, hidx.device)
+        x = self._encode_grad(hidx, p, vN, k1, snap)
         ef = AG.embedding_sum(eidx, [self.embedding_e.weight])
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             A = L.attention_h
             Q, K, V = (AG.linear(x, getattr(A, n).weight, None, vN, k1) for n in "QKV")
             Ee = AG.linear(ef, A.E.weight, None, vE, k1)
             a = AG.edge_attention(Q, K, V, Ee, plan, rplan, L.num_heads)
+            pd = L.dropout
+            if pd:
+                a = AG.dropout(a, pd, snap, 1 + 2 * li)
             o = AG.linear(a, L.O_h.weight, L.O_h.bias, vN, k1)
             x1 = AG.bn_act(AG.masked_add(o, x, vN, k1), L.batch_norm1_h, vN, k1, relu=False)
-            f = AG.linear(AG.linear(x1, L.FFN_h_layer1.weight, L.FFN_h_layer1.bias, vN, k1, relu=True), L.FFN_h_layer2.weight,
-                          L.FFN_h_layer2.bias, vN, k1)
+            f = AG.linear(x1, L.FFN_h_layer1.weight, L.FFN_h_layer1.bias, vN, k1, relu=True)
+            if pd:
+                f = AG.dropout(f, pd, snap, 2 + 2 * li)
+            f = AG.linear(f, L.FFN_h_layer2.weight, L.FFN_h_layer2.bias, vN, k1)
             x = AG.bn_act(AG.masked_add(f, x1, vN, k1), L.batch_norm2_h, vN, k1, relu=False)
         self._h_last = x.detach()
         return self._readout_grad(x, plan, vB, k1)
@@ -1192,7 +1250,8 @@ class GATNet(_DGLNet):
     h = embedding_h(h) + embedding_p(p), L GATConv(ReLU) layers — the first L-1 with their heads flattened, the last averaged over the
     heads (:108-110) — mean / sum readout, MLPReadout.  'GAT (no edge feature)': the edge embedding is a parameter of the
     state_dict only.  Same constructor, forward contract `model(g, h, p, e, snorm_n) -> (scores, g)`, state_dict keys and attached
-    `sign_inv_net`.  No BatchNorm / dropout in this net: eval and train mode compute the same value; with gradients enabled in train
+    `sign_inv_net`.  No BatchNorm in this net, and `dropout` is read and never used (as in the reference): with in_feat_dropout 0 eval and
+    train mode compute the same value; in_feat_dropout > 0 drops embedding_h(h) in train mode (site 0).  With gradients enabled in train
     mode the differentiable path (`_forward_grad`)."""
 
     def __init__(self, net_params):
@@ -1219,7 +1278,7 @@ class GATNet(_DGLNet):
         with torch.no_grad():
             zero_deg = (plan.rowptr[1:] == plan.rowptr[:-1]).any()
             x = ops.embedding_sum(hidx, [self.embedding_h.weight])                    # raises IndexError as nn.Embedding (one host read)
-            x = self._encode(x, p)                                                                               # h + embedding_p(p)  (:97-99)
+            x = self._encode(x, p, self._drop_snap(train, h.device) if self.p_in_feat else None)                 # h + embedding_p(p)  (:97-99)
             H = self.n_heads
             for i, L in enumerate(self.layers):
                 f = ops.masked_linear(x, self._fc(L))
@@ -1261,7 +1320,7 @@ class GATNet(_DGLNet):
                 raise ValueError(zero_msg)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)           # edges grouped by SOURCE
         N, H = hidx.shape[0], self.n_heads
-        x = self._encode_grad(hidx, p, vN, k1)
+        x = self._encode_grad(hidx, p, vN, k1, self._drop_snap(True, hidx.device) if self.p_in_feat else None)
         for L in self.layers:
             x = AG.gat_aggregate(AG.linear(x, L.fc.weight, None, vN, k1), L.attn_l, L.attn_r, L.bias, plan, rplan, H, L.negative_slope, True)
         x = AG.slot_sum(x.view(N * H, -1), N, H)                               # mean over the heads (:110)

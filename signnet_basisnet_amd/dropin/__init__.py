@@ -82,8 +82,18 @@ GNN_TYPE_OVERRIDES = {
 }
 
 
-def _baseline_table(tree: str, baselines, gnn_types=False) -> dict:
-    """What `baselines` (False, True or "all") and `gnn_types` add to ALIASES[tree]."""
+# Opt-in with `feature_dropout=True` (the runner's `--feature-dropout`), on top of the flags above: the modules whose models take train-mode
+# dropout (dropout_models.py).  GINESignNetPyG: `core.model` with the plain GNN for every model.gnn_type and `train.dropout > 0`;
+# GraphPrediction: the five base nets with `--dropout` / `--in_feat_dropout`.  Without the flag every name resolves exactly as before.
+FEATURE_DROPOUT_OVERRIDES = {
+    "gine_pyg": {"core.model": _PKG + ".dropout_core_model"},
+    "graphprediction": {"nets.ZINC_graph_regression." + m: _PKG + ".dropout_nets"
+                        for m in ("gin_net", "gatedgcn_net", "pna_net", "transformer_net", "gat_net")},
+}
+
+
+def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False) -> dict:
+    """What `baselines` (False, True or "all"), `gnn_types` and `feature_dropout` add to ALIASES[tree]."""
     if baselines not in (False, True, "all"):
         raise ValueError(f"baselines must be False, True or 'all', got {baselines!r}")
     table = {}
@@ -94,6 +104,8 @@ def _baseline_table(tree: str, baselines, gnn_types=False) -> dict:
         table.update(ALL_BASELINE_OVERRIDES.get(tree, {}))
     if gnn_types:
         table.update(GNN_TYPE_OVERRIDES.get(tree, {}))
+    if feature_dropout:
+        table.update(FEATURE_DROPOUT_OVERRIDES.get(tree, {}))
     return table
 
 
@@ -132,10 +144,10 @@ class _AliasLoader(importlib.abc.Loader):
 class AliasFinder(importlib.abc.MetaPathFinder):
     """Answers the names of `ALIASES[tree]` and nothing else; every other import goes on to the normal finders."""
 
-    def __init__(self, tree: str, baselines=False, gnn_types=False):
+    def __init__(self, tree: str, baselines=False, gnn_types=False, feature_dropout=False):
         self.tree = tree
         self.table = dict(ALIASES[tree])
-        self.table.update(_baseline_table(tree, baselines, gnn_types))
+        self.table.update(_baseline_table(tree, baselines, gnn_types, feature_dropout))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -144,14 +156,15 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         return importlib.machinery.ModuleSpec(fullname, _AliasLoader(impl), origin=impl)
 
 
-def install(tree: str, baselines=False, gnn_types=False) -> AliasFinder:
+def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False) -> AliasFinder:
     """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
     `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN) and rebinds those of `BASELINE_OVERRIDES[tree]` (LearningFilters' `models`, with
     the four polynomial-filter baselines); baselines="all" rebinds those of `ALL_BASELINE_OVERRIDES[tree]` on top (LearningFilters'
     `models` with GatNet and ARMANet too); gnn_types=True rebinds those of `GNN_TYPE_OVERRIDES[tree]` (GINESignNetPyG's `core.model` with
-    the plain GNN for every model.gnn_type); a finder installed with less is extended in place."""
+    the plain GNN for every model.gnn_type); feature_dropout=True rebinds those of `FEATURE_DROPOUT_OVERRIDES[tree]` (the models that take
+    train-mode dropout); a finder installed with less is extended in place."""
     shim_dir(tree)
-    extra = _baseline_table(tree, baselines, gnn_types)
+    extra = _baseline_table(tree, baselines, gnn_types, feature_dropout)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
             for name, impl in extra.items():
@@ -161,11 +174,14 @@ def install(tree: str, baselines=False, gnn_types=False) -> AliasFinder:
                 bound_for_types = GNN_TYPE_OVERRIDES.get(tree, {}).get(name)
                 if bound_for_types is not None and f.table.get(name) == bound_for_types:
                     continue                    # already bound for gnn_types: a later call without the flag takes nothing away
+                bound_for_dropout = FEATURE_DROPOUT_OVERRIDES.get(tree, {}).get(name)
+                if bound_for_dropout is not None and f.table.get(name) == bound_for_dropout:
+                    continue                    # likewise for feature_dropout
                 if f.table.get(name) != impl:
                     f.table[name] = impl
                     sys.modules.pop(name, None)
             return f
-    finder = AliasFinder(tree, baselines, gnn_types)
+    finder = AliasFinder(tree, baselines, gnn_types, feature_dropout)
     sys.meta_path.insert(0, finder)
     for name in finder.table:           # a module imported before install() would otherwise stay bound to the tree's file
         sys.modules.pop(name, None)

@@ -21,6 +21,12 @@ also binds the trees' baseline models, `dropin.BASELINE_ALIASES`: `baseline_gin`
 `model.gnn_type` — GINConv, GCNConv, GATConv and SimplifiedPNAConv next to GINEConv:
 
     cd <reference>/GINESignNetPyG   && python -m signnet_basisnet_amd.dropin.run --baselines --gnn-types -m train.zinc model.gnn_type SimplifiedPNAConv
+
+`--feature-dropout` rebinds the names of `dropin.FEATURE_DROPOUT_OVERRIDES` to the models that take train-mode dropout
+(`dropout_models.py`): GraphPrediction's five base nets with `--dropout` / `--in_feat_dropout`, and GINESignNetPyG's `core.model` (every
+`model.gnn_type`) with `train.dropout`; without it a non-zero dropout is refused as before:
+
+    cd <reference>/GraphPrediction  && python -m signnet_basisnet_amd.dropin.run --feature-dropout main_ZINC_graph_regression.py --config configs/gatedgcn/GatedGCN_ZINC_NoPE.json --dropout 0.1
 """
 from __future__ import annotations
 
@@ -33,12 +39,14 @@ from . import ALIASES, SCRIPTS, install
 
 def main(argv=None) -> None:
     argv = list(sys.argv[1:] if argv is None else argv)
-    tree, baselines, gnn_types = None, False, False
+    tree, baselines, gnn_types, feature_dropout = None, False, False, False
     while argv and argv[0].startswith("--"):        # the runner's own options come before the script
         if argv[0] == "--baselines":
             baselines, argv = True, argv[1:]
         elif argv[0] == "--gnn-types":
             gnn_types, argv = True, argv[1:]
+        elif argv[0] == "--feature-dropout":
+            feature_dropout, argv = True, argv[1:]
         elif argv[0].startswith("--baselines="):
             value = argv[0].split("=", 1)[1]
             if value != "all":
@@ -53,7 +61,7 @@ def main(argv=None) -> None:
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] <entry script> "
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] <entry script> "
                          "[script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
     if argv[0] == "-m":
@@ -66,7 +74,7 @@ def main(argv=None) -> None:
             tree = SCRIPTS.get(module.rsplit(".", 1)[-1] + ".py")
             if tree is None:
                 raise SystemExit(f"cannot tell the reference tree from the module {module!r}; pass --tree " + "|".join(sorted(ALIASES)))
-        install(tree, baselines=baselines, gnn_types=gnn_types)
+        install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout)
         if os.getcwd() in sys.path:
             sys.path.remove(os.getcwd())
         sys.path.insert(0, os.getcwd())
@@ -80,7 +88,7 @@ def main(argv=None) -> None:
         tree = SCRIPTS.get(os.path.basename(script))
         if tree is None:
             raise SystemExit(f"cannot tell the reference tree from {os.path.basename(script)!r}; pass --tree " + "|".join(sorted(ALIASES)))
-    install(tree, baselines=baselines, gnn_types=gnn_types)
+    install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout)
     script_dir = os.path.dirname(os.path.abspath(script))
     for p in (os.getcwd(), script_dir):          # script_dir ends up first, as under `python script.py`
         if p in sys.path:

@@ -6,6 +6,8 @@ PyTorch's job here), and launches on torch's current stream.  No arithmetic happ
 from __future__ import annotations
 
 import ctypes as C
+import math
+import struct
 from dataclasses import dataclass
 
 import torch
@@ -1817,3 +1819,106 @@ def gcn_pyg_propagate(x, plan: GraphPlan, dis, out=None):
         check(lib().sn_gcn_pyg_propagate_f32(ptr(x), ldx, N, Cc, plan.E, ptr(plan.rowptr), ptr(plan.col), ptr(dis), ptr(out), ldo, stream()),
               "sn_gcn_pyg_propagate_f32")
     return out
+
+
+# ----------------------------------------------------------------------------- train-mode dropout (csrc/dropout.hip)
+class DropoutState:
+    """{seed, step} of the counter-based dropout masks: an int64 [2] DEVICE tensor the kernel reads when it runs, so a replay of a
+    captured graph draws the current step's masks.  seed None takes torch.initial_seed() (reproducible under torch.manual_seed).
+    Not a module buffer: it never enters a state_dict."""
+
+    def __init__(self, seed=None, device="cuda", step=0):
+        self.t = torch.zeros(2, dtype=torch.int64, device=device)
+        self.set(torch.initial_seed() if seed is None else seed, step)
+
+    def set(self, seed, step=0):
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        host = torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, int(step)], dtype=torch.int64)
+        self.t.copy_(host)
+        return self
+
+    def advance(self):
+        """step += 1 on the device (a torch op: recordable in a captured graph)."""
+        self.t[1:].add_(1)
+        return self
+
+    def snapshot(self):
+        """A device clone: what one forward hands to all its sites and to its backward."""
+        return self.t.clone()
+
+
+def dropout_threshold(p):
+    """(threshold, scale) of sn_dropout_f32 for 0 <= p < 1: floor(p * 2^32) in double precision, float32(1 / (1 - p))."""
+    return int(math.floor(float(p) * 4294967296.0)), struct.unpack("f", struct.pack("f", 1.0 / (1.0 - float(p))))[0]
+
+
+def _dropout_launch(x, ldx, R, Cc, p, snap, site, base, residual, ldr, out, ldo):
+    thr, scale = dropout_threshold(p)
+    with _span("sn_dropout_f32"):
+        check(lib().sn_dropout_f32(ptr(x), ldx, R, Cc, thr, scale, ptr(snap), int(site), int(base), ptr(residual), ldr, ptr(out), ldo,
+                                   stream()), "sn_dropout_f32")
+
+
+def dropout(x, p, snap, site, residual=None, base=0):
+    """Train-mode dropout of the logical row-major [R, C] tensor x (C = the last dimension): y = keep * x / (1 - p) + residual, the
+    keep mask drawn by Philox4x32-10 from (snap = {seed, step}, site, base + r*C + c) — see signnet_hip.h.  The backward is the same
+    call on dy.  p == 0: x itself, no launch (x + residual through `pointwise`); p == 1: zeros + residual."""
+    p = float(p)
+    if p < 0.0 or p > 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    if p == 0.0:
+        return x if residual is None else pointwise(x, residual=residual)
+    require_cuda(x, residual)
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("dropout: the residual must have x's shape")
+    if p == 1.0:
+        return torch.zeros_like(x) if residual is None else residual.clone()
+    require_cuda(snap)
+    if snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous():
+        raise ValueError("dropout: snap must be the int64 [2] {seed, step} tensor of a DropoutState")
+    x = _f32c(x, "x")
+    residual = None if residual is None else _f32c(residual, "residual")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    Cc = x.shape[-1]
+    _dropout_launch(x, Cc, x.numel() // Cc, Cc, p, snap, site, base, residual, Cc, out, Cc)
+    return out
+
+
+class DropoutHolder:
+    """Mixin of the models with feature dropout: a lazily created DropoutState kept OUT of the module's buffers (plain attribute: no
+    state_dict key, not in model.buffers()).  A train-mode forward calls `_dropout_begin` once at its start: the step advances, and
+    the snapshot it returns serves every site of that forward and its backward."""
+
+    def seed_dropout(self, seed, step=0):
+        """Masks of the next train-mode forward: those of (seed, step + 1); reproducible from here on."""
+        self.__dict__["_sn_dropout_seed"] = (int(seed), int(step))
+        st = self.__dict__.get("_sn_dropout_state")
+        if st is not None:
+            st.set(seed, step)
+        return self
+
+    def dropout_state(self, device):
+        st = self.__dict__.get("_sn_dropout_state")
+        if st is None or st.t.device != torch.device(device):
+            seed, step = self.__dict__.get("_sn_dropout_seed", (None, 0))
+            if st is not None:                              # the model moved: the state follows with its words
+                seed, step = (int(v) for v in st.t.tolist())
+            st = self.__dict__["_sn_dropout_state"] = DropoutState(seed, device, step)
+        return st
+
+    def _dropout_begin(self, device):
+        return self.dropout_state(device).advance().snapshot()
+
+    def _dropout_active(self):
+        """Whether a train-mode forward of this model draws masks at all."""
+        return any(float(getattr(m, n, 0.0) or 0.0) > 0.0 for m in [self] + list(getattr(self, "layers", []))
+                   for n in ("dropout", "p_in_feat", "p_drop"))
+
+
+def check_dropout_p(p, who):
+    p = float(p)
+    if p < 0.0 or p > 1.0:
+        raise ValueError(f"{who}: dropout probability has to be between 0 and 1, but got {p}")
+    return p

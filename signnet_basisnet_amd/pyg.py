@@ -213,15 +213,21 @@ class SignNet(nn.Module):
                 getattr(self, n).reset_parameters()
 
 
-class GNN(nn.Module):
+class GNN(ops.DropoutHolder, nn.Module):
     """Parameter holder of the GINE network inside SignNetGNN and — `variant='gine'` — a model of its own: `forward(data,
     additional_x=None)` is the plain GINE baseline GINESignNetPyG's default run trains (train/zinc.py:31-46 with model.gnn_type GINEConv:
     GNN(None, None, nhid, 1, nlayer, 'GINEConv', dropout, pool, res=True), core/model.py:44-79), layer at a time on the kernels
-    SignNetGNN's layer path uses (the fused GINE stage is not involved).  dropout > 0 and res=False are not built."""
+    SignNetGNN's layer path uses (the fused GINE stage is not involved).  res=False is not built.  dropout > 0 (core/model.py:65,
+    between the ReLU and the residual) is site `layer` of the counter-based masks of ops.dropout on the logical [N, nhid] tensor: the
+    layer's last link runs without its residual, which moves into the dropout launch.  Eval mode never reads it.  Opt-in: this class and
+    pyg_gnn_types.GNN keep refusing dropout > 0 as before; dropout_models.GNN (`_feature_dropout = True`) takes it."""
+
+    _feature_dropout = False
 
     def __init__(self, nfeat_node, nfeat_edge, nhid, nout, nlayer, variant, pooling="add", dropout=0, res=True):
         super().__init__()
-        if dropout:
+        self.dropout = ops.check_dropout_p(dropout, "GNN")
+        if self.dropout and not self._feature_dropout:
             raise NotImplementedError("GNN: dropout > 0 is not built on the HIP path (core/config.py's default is 0)")
         if not res:
             raise NotImplementedError("GNN: res=False is not built on the HIP path (train/zinc.py builds res=True)")
@@ -308,10 +314,15 @@ class GNN(nn.Module):
         h = encode(self.input_encoder, self._node_ids(data))
         if additional_x is not None:
             h = ops.masked_linear(torch.cat([h, additional_x], dim=-1), pack(self.linear))
-        for enc, conv, norm in zip(self.edge_encoders, self.convs, self.norms):
+        drop = self.dropout if train else 0.0
+        snap = self._dropout_begin(h.device) if drop else None
+        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
             u = ops.gine_aggregate(h, encode(enc, ea), plan, conv.layer.eps.detach())
             u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
-            h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+            if drop:
+                h = ops.dropout(lin_bn(u, conv.nn.layers[1], norm), drop, snap, li, residual=h)
+            else:
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
         pooled = ops.segment_pool(h, plan, self.pooling)
         if self.pooling == "mean":
             size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], status)
@@ -353,8 +364,17 @@ class GNN(nn.Module):
         if staged and all(isinstance(enc, DiscreteEncoder) for enc in self.edge_encoders) and 1 < len(self.edge_encoders) <= 16:
             # every layer embeds the same edge_attr with its own tables: one [L, E, C] block, one adjoint launch pair for all layers
             e_all = AG.embedding_sum_layers(ea, [[t.weight for t in enc.embeddings] for enc in self.edge_encoders], status)
+        drop = self.dropout
+        snap = self._dropout_begin(h.device) if drop else None
         for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
-            if e_all is not None:
+            if drop:
+                u = AG.gine_aggregate(h, encode(enc, ea), conv.layer.eps, plan, rplan)
+                if staged:
+                    u = T.mlp2_bn(u, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm)
+                else:
+                    u = lin_bn(lin_bn(u, conv.nn.layers[0], conv.nn.norms[0]), conv.nn.layers[1], norm)
+                h = AG.dropout(u, drop, snap, li, residual=h)
+            elif e_all is not None:
                 h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li)
             elif staged:
                 h = T.gine_layer(h, encode(enc, ea), conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan)

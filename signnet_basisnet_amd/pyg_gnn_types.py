@@ -20,7 +20,9 @@ Launches per layer (eval; the train forward puts a statistics launch in front of
             front), the W2 GEMM on the [N, 3d] mean with rows of in-degree 0 written as zero, the degree embedding, then post_nn as two
             GEMMs over cat[x, W2-mean, deg_emb] (one 384-wide GEMM at d = 128: sn_masked_linear_f32 has no width limit)
 
-Not built, as in pyg.GNN: dropout > 0, res=False, bn=False, dos_bins > 0; SimplifiedPNAConv with aggregators other than ['mean'] (GNN
+dropout > 0 (core/model.py:65): wired as in pyg.GNN (site = the layer, between the ReLU and the residual) and, as there, refused by this
+class; dropout_models.GNN is the subclass that takes it.
+Not built, as in pyg.GNN: res=False, bn=False, dos_bins > 0; SimplifiedPNAConv with aggregators other than ['mean'] (GNN
 cannot reach them) or nhid > 128.  These nets train eagerly (no captured step).
 """
 from __future__ import annotations
@@ -222,18 +224,22 @@ class GNN(_pyg.GNN):
             op = _gat_operator(data, plan.N)
         elif kind == "SimplifiedPNAConv":
             deg, has_in = self._degrees(plan)
-        for enc, conv, norm in zip(self.edge_encoders, self.convs, self.norms):
+        drop = self.dropout if train else 0.0
+        snap = self._dropout_begin(h.device) if drop else None
+        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
+            res = None if drop else h                   # dropout sits between the ReLU and the residual: the add moves into its launch
+            h_in = h
             if kind == "GINConv":
                 u = ops.gin_aggregate(h, plan, conv.layer.eps.detach())
                 u = ops.masked_linear(u, pack(conv.nn.layers[0]), relu=True)
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=res)
             elif kind == "GCNConv":
-                h = lin_bn(ops.gcn_pyg_propagate(h, plan, dis), conv.layer.lin, norm, residual=h)
+                h = lin_bn(ops.gcn_pyg_propagate(h, plan, dis), conv.layer.lin, norm, residual=res)
             elif kind == "GATConv":
                 L = conv.layer
                 f = ops.masked_linear(h, pack(L.lin_src))
                 z, _ = ops.gat_conv(f, L.att_src.detach(), L.att_dst.detach(), None, op, L.heads, None, L.negative_slope)
-                h = bn_act(z, norm, h)
+                h = bn_act(z, norm, res)
             else:
                 d = h.shape[1]
                 W1 = conv.pre_nn.layers[0].weight.detach()
@@ -253,7 +259,9 @@ class GNN(_pyg.GNN):
                 m = ops.masked_linear(r, pack(conv.pre_nn.layers[1]), has_in, 1)      # W2 mean + b2 [deg > 0]
                 de = ops.embedding_sum(deg, [conv.deg_embedder.weight.detach()], status)
                 u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0])
-                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=h)
+                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=res)
+            if drop:
+                h = ops.dropout(h, drop, snap, li, residual=h_in)
         pooled = ops.segment_pool(h, plan, self.pooling)
         if self.pooling == "mean":
             size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], status)
@@ -301,18 +309,22 @@ class GNN(_pyg.GNN):
             op = _gat_operator(data, plan.N)
         elif kind == "SimplifiedPNAConv":
             deg, has_in = self._degrees(plan)
-        for enc, conv, norm in zip(self.edge_encoders, self.convs, self.norms):
+        drop = self.dropout
+        snap = self._dropout_begin(h.device) if drop else None
+        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
+            res = None if drop else h
+            h_in = h
             if kind == "GINConv":
                 u = AG.gin_aggregate(h, conv.layer.eps, plan, rplan)
                 u = AG.linear(u, conv.nn.layers[0].weight, conv.nn.layers[0].bias, None, 0, relu=True)
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=res)
             elif kind == "GCNConv":
-                h = lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), conv.layer.lin, norm, residual=h)
+                h = lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), conv.layer.lin, norm, residual=res)
             elif kind == "GATConv":
                 L = conv.layer
                 f = AG.linear(h, L.lin_src.weight, None, None, 0)
                 z = AG.gat_conv(f, L.att_src, L.att_dst, None, op, L.heads, None, L.negative_slope)
-                h = AG.bn_act(z, norm, None, 0, relu=True, residual=h)
+                h = AG.bn_act(z, norm, None, 0, relu=True, residual=res)
             else:
                 W1 = conv.pre_nn.layers[0].weight
                 ab = AG.linear(h, torch.cat([W1[:, :d], W1[:, d:2 * d]], 0), None, None, 0)
@@ -322,7 +334,9 @@ class GNN(_pyg.GNN):
                 m = AG.linear(r, l1.weight, l1.bias, has_in, 1)
                 de = AG.embedding_sum(deg, [conv.deg_embedder.weight], status)
                 u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0])
-                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=h)
+                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=res)
+            if drop:
+                h = AG.dropout(h, drop, snap, li, residual=h_in)
         pooled = AG.segment_pool(h, plan, self.pooling)
         if self.pooling == "mean":
             pooled = AG.masked_add(pooled, AG.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight], status), None, 0)

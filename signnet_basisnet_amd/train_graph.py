@@ -128,7 +128,9 @@ def _mask_buffers(model, N, K, dev):
 
 def _capture(step, fwd_bwd, dev, warmup, check=None):
     """Warm up `fwd_bwd` on a side stream (lazy one-time setup: LDS limits, allocator pools) and capture it, under `step._scoped()`,
-    without touching the model's state: buffers (running statistics, counters) and the generator are restored afterwards.
+    without touching the model's state: buffers (running statistics, counters), the generator and the step word of the model's feature
+    dropout (ops.DropoutHolder: its advance and snapshot are recorded inside `fwd_bwd`, so every replay draws the next step's masks) are
+    restored afterwards.
     `check`: what raises for a bad batch after the warm-up (default: the model's check_train()).
     -> (graph, loss, y, the captured forward's status words)."""
     model = step.model
@@ -136,6 +138,9 @@ def _capture(step, fwd_bwd, dev, warmup, check=None):
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     rng = torch.cuda.get_rng_state(dev) if step._masks is not None else None
+    # (the state exists before the capture: its creation copies from the host)
+    drop = model.dropout_state(dev) if getattr(model, "_dropout_active", lambda: False)() else None
+    drop_saved = None if drop is None else drop.t.clone()
     with step._scoped():
         with torch.cuda.stream(side):
             for _ in range(warmup):
@@ -153,6 +158,8 @@ def _capture(step, fwd_bwd, dev, warmup, check=None):
             b.copy_(sv)
     if rng is not None:
         torch.cuda.set_rng_state(rng, dev)      # the warm-up's draws do not count: the first step draws what an eager one would
+    if drop is not None:
+        drop.t.copy_(drop_saved)                # nor do its dropout steps
     return graph, loss.detach(), y.detach(), status
 
 
