@@ -109,11 +109,18 @@ __device__ __forceinline__ float tile_rowsum(float v) {
 // bit-identical outputs, and measured SLOWER (61.5 -> 72.9 us on the headline batch): see rho_eight_waves() below.  Default: 4.
 // PREC: the product set of the six [d, d] projections of a layer (fused_common.hpp); the attention's score and value products (fp32
 // MFMA), the softmax, the LayerNorms and the slot sum are the same arithmetic in every mode.
-template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST>
+// RES3 (REGATTN && ONE && NW == 4, instantiated for NT = 8 only): compiled for THREE waves per SIMD, i.e. <= 168 registers and no
+// private segment, so that three workgroups are resident per CU (3 x 47 KB of LDS) and the headline batch's 738 bins all start at
+// t = 0 instead of 226 of them walking a second, lonely round.  The same products, accumulation orders and epilogues; what differs
+// is control flow only: no eigenvalue-encoder path (ONE has none), and a wave without rows runs the layer on zero rows instead of
+// branching round every product — with one path the compiler no longer carries qf / o / the row array round the other (242 registers
+// before, and 328 bytes of private segment when merely asked for three waves per SIMD).  See launch_rho.
+template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST, bool RES3 = false>
 // (the LDS-attention variants hold two 64-row images beside the weight ring: one workgroup per CU fits, so they may use the whole
 //  register file of a SIMD — 512 registers per lane, no private segment)
-__global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruct S, sn_rho_params P) {
+__global__ __launch_bounds__(64 * NW, REGATTN ? (RES3 ? 3 : 2) : 1) void k_rho_fused(RhoStruct S, sn_rho_params P) {
   static_assert(NW == 4 || (NW == 8 && REGATTN), "eight waves: the register-attention variants only (no 64-row LDS images)");
+  static_assert(!RES3 || (REGATTN && ONE && NW == 4), "three resident workgroups: the one-layer register-attention form only");
   constexpr int NTHR = 64 * NW;
   constexpr int D = 16 * NT;
   constexpr int LD = D + 4;
@@ -282,7 +289,9 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
     }
     const bool valid = unit_ok && slot < kg;
     constexpr bool mfma_attn = REGATTN;                             // one node == one wave tile: attention in registers
-    const bool wave_live = __ballot(valid) != 0ull;
+    // (RES3: a wave without rows — the batch's last bin only — runs the layer on zero rows like any other; nothing of it is stored.
+    //  One path through every product instead of two keeps the row arrays from being carried around the dead path.)
+    const bool wave_live = RES3 || __ballot(valid) != 0ull;
     float* Ar = A + r * LD;
     float* Br = Bm + r * LD;
     SN_STAMP(1);
@@ -313,7 +322,7 @@ __global__ __launch_bounds__(64 * NW, REGATTN ? 2 : 1) void k_rho_fused(RhoStruc
       load_x();
     }
     if (valid) {
-      if (P.has_pos) {
+      if (!RES3 && P.has_pos) {      // (RES3 is a ONE instance: no eigenvalue encoding)
         // eigen_encoder = MaskedMLP(1 -> 1 -> d): Linear . BN . ReLU . Linear . BN . ReLU   (sign_net.py:86,108)
         const float ev = S.eigvals[gs + slot];
         const float t0 = fmaxf((ev * P.pe_w1[0]) * P.pe_bn0_scale[0] + P.pe_bn0_shift[0], 0.f);
@@ -876,7 +885,15 @@ static int launch_rho_wide(const RhoStruct& S, const sn_rho_params& P, int64_t b
   return SN_OK;
 }
 
-template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST>
+// (A/B switch of the profile scripts, read once: SN_RHO_RESIDENT=2 in the environment keeps every register-attention instance on two
+//  workgroups per CU — the form before the three-resident one: k_rho_fused<8, true, true> at 242 registers, hidden 64 at two per CU.)
+static bool rho_three_resident() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("SN_RHO_RESIDENT"); v = (e && e[0] == '2') ? 0 : 1; }
+  return v == 1;
+}
+
+template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST, bool RES3 = false>
 static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_bound, hipStream_t st) {
   constexpr int LD = 16 * NT + 4;
   // (the LayerNorm vectors of the layers the net HAS, not of SN_RHO_MAX_LAYERS: 47 KB instead of 61 for the register-attention variant
@@ -887,22 +904,31 @@ static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_b
   static int cus = 0;
   if (cus == 0) {
     if (lds_max > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_rho_fused<NT, REGATTN, ONE, HP, NW, PREC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_rho_fused<NT, REGATTN, ONE, HP, NW, PREC, RES3>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_max) != hipSuccess)
       return fail(SN_ERR_LAUNCH, "sn_rho_fused_f32: cannot raise the dynamic LDS limit to %zu", lds_max);
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     cus = n > 0 ? n : 256;
   }
-  // eight waves per CU either way: two 4-wave workgroups (two weight streams), or one 8-wave workgroup (one stream)
-  // (4 waves, two workgroups per CU: with the 47 KB of a one-layer net three or four fit, measured 61.5 against 60.6 us — no gain)
-  const int64_t per_cu = NW == 8 ? 1 : 2;
+  // Workgroups resident per CU = what the instance's registers and LDS allow: one 8-wave workgroup (one weight stream); two 4-wave
+  // workgroups (two streams) for the instances compiled for two waves per SIMD; THREE for the 168-register form of the one-layer
+  // d = 128 instance (RES3: 164 registers, 3 x 47 KB of LDS) and for the one-layer hidden-64 instances (144-146 registers, 3 x 28 KB),
+  // when the batch has more bins than two per CU hold — bins of a second round ran alone on their CU for a whole chain latency.
+  // Measured (profiles/rho_resident.json, SN_RHO_RESIDENT=2 against the default, alternating): headline rho 57.2 -> 52.7 us in the
+  // kernel trace (738 bins: one round instead of 1.44; matrix pipe 39 -> 45 % busy), hidden 64 on 1 026 bins 34.4 -> 31.3 us, outputs
+  // byte-identical.  A batch of <= 2 x CUs bins is launched exactly as before.
+  // (An earlier note here recorded "three or four workgroups per CU: 61.5 against 60.6 us, no gain" for the 242-register form.  At
+  //  242 registers a third workgroup is never resident — that run only changed which slot picked up a second bin.)
+  constexpr bool three = REGATTN && ONE && NW == 4 && (RES3 || (NT == 4 && PREC == PREC_HIGHEST));
+  const int64_t bins = REGATTN ? ((int64_t)S.N + NW - 1) / NW : bins_bound;
+  const int64_t per_cu = NW == 8 ? 1 : ((three && rho_three_resident() && bins > (int64_t)2 * cus) ? 3 : 2);
   int64_t grid = bins_bound < per_cu * cus ? bins_bound : per_cu * cus;
 #ifdef SN_RHO_GRID1
   grid = cus;
 #endif
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_rho_fused<NT, REGATTN, ONE, HP, NW, PREC>), dim3((unsigned)grid), dim3(64 * NW), lds, st, S, P);
+  hipLaunchKernelGGL((k_rho_fused<NT, REGATTN, ONE, HP, NW, PREC, RES3>), dim3((unsigned)grid), dim3(64 * NW), lds, st, S, P);
   return SN_OK;
 }
 
@@ -934,6 +960,10 @@ static int dispatch_rho(int nt, const RhoStruct& S, const sn_rho_params& P, int6
         if (nt == 8) return launch_rho<8, true, ONE, false, 8>(S, P, bound, st);
         if (nt == 4) return launch_rho<4, true, ONE, false, 8>(S, P, bound, st);
       }
+    }
+    if constexpr (REGATTN && ONE) {
+      // one layer, d in (112, 128]: the 168-register form (three workgroups resident per CU when the batch has the bins for them)
+      if (nt == 8 && rho_three_resident()) return launch_rho<8, true, true, false, 4, PREC_HIGHEST, true>(S, P, bound, st);
     }
     switch (nt) {
       case 1: return launch_rho<1, REGATTN, ONE>(S, P, bound, st);
