@@ -1324,6 +1324,32 @@ int sn_gcn_pyg_propagate_f32(const float* x, int64_t ldx, int64_t N, int C, int6
 int sn_dropout_f32(const float* x, int ldx, int64_t R, int C, uint32_t threshold, float scale, const int64_t* state, uint32_t site,
                    int64_t base, const float* residual, int ldr, float* y, int ldy, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Attention dropout with a counter-based mask: sn_set_attention_f32 / sn_set_attention_bwd_f32 with the factor that multiplies
+ * P[n, h, q, key] after the softmax (transformer_module.py:49,55) evaluated inside the kernels instead of read from prob_mask.
+ * THE MASK CONTRACT (restated in numpy by tests/attention_dropout_cases.py):
+ *   w      = philox4x32_10(counter = (lo32(n*H + h), (q << 16) | (key >> 2), site, lo32(step)), key = (lo32(seed), hi32(seed)))
+ *   keep   = w[key & 3] >= threshold           (threshold = floor(p * 2^32) in double precision)
+ *   factor = keep ? scale : 0                  (scale = float32(1 / (1 - p)))
+ *   site   = 0x41540000 + index of the rho layer   (SN_ATTN_DROP_SITE: disjoint from the small ordinals of the sn_dropout_f32 sites)
+ * n: node row, h: head, q: query slot, key: key slot; state = int64[2] {seed, step} in DEVICE memory, read when the kernel runs, so a
+ * replay of a captured graph draws the current step's mask.  Neither N nor K enters: the mask of an element (n, h, q, key) does not
+ * change when the batch is padded to more rows or K is a bucket's slot capacity instead of the batch's own.  A data-parallel run
+ * should seed every rank differently (seed + rank): n is the node row within the rank's batch.
+ * Nothing of the mask's size is stored: forward and backward evaluate the same words — one generator call per aligned group of four
+ * keys (per lane in the matrix-pipe kernels, per four iterations of a query row's key loop in the scalar kernels) — and then run the
+ * explicit-mask arithmetic on the factor, so the results equal sn_set_attention[_bwd]_f32 on a prob_mask of those factors bit for
+ * bit.  Same dispatch (matrix pipe for K <= 16, dk in {16, 32, 64}, aligned; the one-wave LDS kernels otherwise) and the same LDS
+ * refusals as the explicit-mask entry points.  SN_ERR_ARG unless N * heads < 2^32, K <= 65536, 1 <= scale < inf (0 <= p < 1) and
+ * state is 8-byte aligned. */
+#define SN_ATTN_DROP_SITE 0x41540000u
+int sn_set_attention_drop_f32(const float* q, const float* k, const float* v, int64_t N, int K, int heads, int dk,
+                              const int32_t* nvalid, uint32_t threshold, float scale, const int64_t* state, uint32_t site, float* out,
+                              void* stream);
+int sn_set_attention_drop_bwd_f32(const float* q, const float* k, const float* v, const float* dout, int64_t N, int K, int heads,
+                                  int dk, const int32_t* nvalid, uint32_t threshold, float scale, const int64_t* state, uint32_t site,
+                                  float* dq, float* dk_out, float* dv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

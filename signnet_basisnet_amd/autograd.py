@@ -257,27 +257,36 @@ def gine_aggregate(h, ee, eps, plan, rplan):
 # ----------------------------------------------------------------------------- set attention / LayerNorm / slot sum
 class _Attention(Function):
     @staticmethod
-    def forward(ctx, q, k, v, N, K, heads, nvalid, prob_mask):
+    def forward(ctx, q, k, v, N, K, heads, nvalid, prob_mask, drop):
         q, k, v = _c(q), _c(k), _c(v)
         ctx.save_for_backward(q, k, v)
-        ctx.meta = (N, K, heads, nvalid, prob_mask)
-        return ops.set_attention(q, k, v, N, K, heads, nvalid, prob_mask)
+        ctx.meta = (N, K, heads, nvalid, prob_mask, drop)
+        return ops.set_attention(q, k, v, N, K, heads, nvalid, prob_mask, drop)
 
     @staticmethod
     def backward(ctx, g):
         q, k, v = ctx.saved_tensors
-        N, K, heads, nvalid, prob_mask = ctx.meta
+        N, K, heads, nvalid, prob_mask, drop = ctx.meta
         g = _c(g)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        args = None if drop is None else ops.attention_drop_args(drop)
+        if args is not None:         # the counter source: the node kept the {seed, step} words, not a mask
+            thr, scale, snap, site = args
+            with ops._span("sn_set_attention_drop_bwd_f32"):
+                check(lib().sn_set_attention_drop_bwd_f32(ptr(q), ptr(k), ptr(v), ptr(g), N, K, heads, q.shape[-1] // heads, ptr(nvalid),
+                                                          thr, scale, ptr(snap), site, ptr(dq), ptr(dk), ptr(dv), stream()),
+                      "sn_set_attention_drop_bwd_f32")
+            return dq, dk, dv, None, None, None, None, None, None
         with ops._span("sn_set_attention_bwd_f32"):
             check(lib().sn_set_attention_bwd_f32(ptr(q), ptr(k), ptr(v), ptr(g), N, K, heads, q.shape[-1] // heads, ptr(nvalid),
                                                  ptr(prob_mask), ptr(dq), ptr(dk), ptr(dv), stream()), "sn_set_attention_bwd_f32")
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
-def set_attention(q, k, v, N, K, heads, nvalid=None, prob_mask=None):
-    """prob_mask: ops.attention_dropout_mask(...) for the train-mode attention dropout, or None."""
-    return _Attention.apply(q, k, v, N, K, heads, nvalid, prob_mask)
+def set_attention(q, k, v, N, K, heads, nvalid=None, prob_mask=None, drop=None):
+    """prob_mask: ops.attention_dropout_mask(...) for the train-mode attention dropout, or None; drop = (p, snap, site): the
+    counter-based source of the same factors (ops.set_attention) — the backward evaluates the same words from `snap`."""
+    return _Attention.apply(q, k, v, N, K, heads, nvalid, prob_mask, drop)
 
 
 class _LayerNorm(Function):

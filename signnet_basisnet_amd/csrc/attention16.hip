@@ -10,7 +10,9 @@
 //  (dk/4) g + s in S^T, and key 4g + s in P V).  The adjoint needs P^T and dS^T for dV and dK: two 16 x 16 transposes through LDS.
 // The scalar kernels they replace (ops.hip k_set_attention, backward.hip k_set_attention_bwd) took 120 us / 250 us for the headline
 // batch (2 950 nodes x 4 heads); they remain for K > 16 and head widths that are not a multiple of 16.
-#include "common.hpp"
+// DROP instantiations take the dropout factors from the counter-based generator of philox.hpp instead of `pmask`: lane (lr, g) owns
+// P[query lr][keys 4g .. 4g+3], exactly one aligned key group — one Philox call per lane and direction, then the explicit-mask code.
+#include "philox.hpp"
 
 namespace sn {
 namespace {
@@ -84,10 +86,10 @@ __device__ __forceinline__ void store_rows(float* __restrict__ dst, int D, int K
       if (4 * g + r < K) dst[(int64_t)(4 * g + r) * D + 16 * t + lr] = val[t][r] * scale;
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void k_attn16_fwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                     int64_t NH, int K, int H, const int32_t* __restrict__ nvalid,
-                                                    const float* __restrict__ pmask, float* __restrict__ out) {
+                                                    const float* __restrict__ pmask, float* __restrict__ out, AttnDrop drop) {
   const int lane = threadIdx.x & 63, lr = lane & 15, g = lane >> 4;
   const int64_t nh = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (nh >= NH) return;
@@ -104,7 +106,12 @@ __global__ __launch_bounds__(256) void k_attn16_fwd(const float* __restrict__ q,
 #pragma unroll
   for (int r = 0; r < 4; ++r) s[r] *= inv_t;
   f32x4 p = softmax_keys(s, kv, lr, g);
-  if (pmask && lr < K) {
+  if constexpr (DROP) {
+    float f[4];
+    attn_drop_factors(drop, (uint32_t)nh, lr, g, f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) if (4 * g + r < K) p[r] *= f[r];
+  } else if (pmask && lr < K) {
     const float* pm = pmask + (nh * K + lr) * K;
 #pragma unroll
     for (int r = 0; r < 4; ++r) if (4 * g + r < K) p[r] *= pm[4 * g + r];
@@ -114,11 +121,11 @@ __global__ __launch_bounds__(256) void k_attn16_fwd(const float* __restrict__ q,
   store_rows<DK>(out + base, D, K, lr, g, o, 1.0f);
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void k_attn16_bwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                     const float* __restrict__ dout, int64_t NH, int K, int H,
                                                     const int32_t* __restrict__ nvalid, const float* __restrict__ pmask,
-                                                    float* __restrict__ dq, float* __restrict__ dkk, float* __restrict__ dv) {
+                                                    float* __restrict__ dq, float* __restrict__ dkk, float* __restrict__ dv, AttnDrop drop) {
   __shared__ float tile[4][2][16][17];
   const int lane = threadIdx.x & 63, lr = lane & 15, g = lane >> 4, w = threadIdx.x >> 6;
   const int64_t nh = (int64_t)blockIdx.x * 4 + w;
@@ -140,7 +147,12 @@ __global__ __launch_bounds__(256) void k_attn16_bwd(const float* __restrict__ q,
   const f32x4 p = softmax_keys(s, kv, lr, g);                  // P[query lr][key 4g + r]
   f32x4 dp = score_t<DK>(rv, rg);                              // dP'[query lr][key 4g + r] = sum_c dO[query][c] v[key][c]
   f32x4 pm = {1.f, 1.f, 1.f, 1.f};
-  if (pmask && lr < K) {
+  if constexpr (DROP) {
+    float f[4];
+    attn_drop_factors(drop, (uint32_t)nh, lr, g, f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) if (4 * g + r < K) pm[r] = f[r];
+  } else if (pmask && lr < K) {
     const float* m = pmask + (nh * K + lr) * K;
 #pragma unroll
     for (int r = 0; r < 4; ++r) if (4 * g + r < K) pm[r] = m[4 * g + r];
@@ -174,27 +186,40 @@ __global__ __launch_bounds__(256) void k_attn16_bwd(const float* __restrict__ q,
 
 inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+template <bool DROP>
+void launch_fwd(const float* q, const float* k, const float* v, int64_t NH, int K, int heads, int dk, const int32_t* nvalid,
+                const float* prob_mask, float* out, AttnDrop d, hipStream_t st) {
+  const dim3 grid((unsigned)cdiv(NH, 4));
+  if (dk == 16) hipLaunchKernelGGL((k_attn16_fwd<16, DROP>), grid, dim3(256), 0, st, q, k, v, NH, K, heads, nvalid, prob_mask, out, d);
+  else if (dk == 32) hipLaunchKernelGGL((k_attn16_fwd<32, DROP>), grid, dim3(256), 0, st, q, k, v, NH, K, heads, nvalid, prob_mask, out, d);
+  else hipLaunchKernelGGL((k_attn16_fwd<64, DROP>), grid, dim3(256), 0, st, q, k, v, NH, K, heads, nvalid, prob_mask, out, d);
+}
+template <bool DROP>
+void launch_bwd(const float* q, const float* k, const float* v, const float* dout, int64_t NH, int K, int heads, int dk,
+                const int32_t* nvalid, const float* prob_mask, float* dq, float* dkk, float* dv, AttnDrop d, hipStream_t st) {
+  const dim3 grid((unsigned)cdiv(NH, 4));
+  if (dk == 16) hipLaunchKernelGGL((k_attn16_bwd<16, DROP>), grid, dim3(256), 0, st, q, k, v, dout, NH, K, heads, nvalid, prob_mask, dq, dkk, dv, d);
+  else if (dk == 32) hipLaunchKernelGGL((k_attn16_bwd<32, DROP>), grid, dim3(256), 0, st, q, k, v, dout, NH, K, heads, nvalid, prob_mask, dq, dkk, dv, d);
+  else hipLaunchKernelGGL((k_attn16_bwd<64, DROP>), grid, dim3(256), 0, st, q, k, v, dout, NH, K, heads, nvalid, prob_mask, dq, dkk, dv, d);
+}
+
 }  // namespace
 
-// returns true when the shape takes the matrix-pipe path (the caller falls back to the scalar kernels otherwise)
+// returns true when the shape takes the matrix-pipe path (the caller falls back to the scalar kernels otherwise); `drop` (may be null):
+// the counter source of the dropout factors in place of prob_mask
 bool attention16_forward(const float* q, const float* k, const float* v, int64_t N, int K, int heads, int dk, const int32_t* nvalid,
-                         const float* prob_mask, float* out, hipStream_t st) {
+                         const float* prob_mask, const AttnDrop* drop, float* out, hipStream_t st) {
   if (K > 16 || (dk != 16 && dk != 32 && dk != 64) || !a16(q) || !a16(k) || !a16(v)) return false;
-  const int64_t NH = N * heads;
-  const dim3 grid((unsigned)cdiv(NH, 4));
-  if (dk == 16) hipLaunchKernelGGL(k_attn16_fwd<16>, grid, dim3(256), 0, st, q, k, v, NH, K, heads, nvalid, prob_mask, out);
-  else if (dk == 32) hipLaunchKernelGGL(k_attn16_fwd<32>, grid, dim3(256), 0, st, q, k, v, NH, K, heads, nvalid, prob_mask, out);
-  else hipLaunchKernelGGL(k_attn16_fwd<64>, grid, dim3(256), 0, st, q, k, v, NH, K, heads, nvalid, prob_mask, out);
+  if (drop) launch_fwd<true>(q, k, v, N * heads, K, heads, dk, nvalid, nullptr, out, *drop, st);
+  else launch_fwd<false>(q, k, v, N * heads, K, heads, dk, nvalid, prob_mask, out, AttnDrop{}, st);
   return true;
 }
 bool attention16_backward(const float* q, const float* k, const float* v, const float* dout, int64_t N, int K, int heads, int dk,
-                          const int32_t* nvalid, const float* prob_mask, float* dq, float* dkk, float* dv, hipStream_t st) {
+                          const int32_t* nvalid, const float* prob_mask, const AttnDrop* drop, float* dq, float* dkk, float* dv,
+                          hipStream_t st) {
   if (K > 16 || (dk != 16 && dk != 32 && dk != 64) || !a16(q) || !a16(k) || !a16(v) || !a16(dout)) return false;
-  const int64_t NH = N * heads;
-  const dim3 grid((unsigned)cdiv(NH, 4));
-  if (dk == 16) hipLaunchKernelGGL(k_attn16_bwd<16>, grid, dim3(256), 0, st, q, k, v, dout, NH, K, heads, nvalid, prob_mask, dq, dkk, dv);
-  else if (dk == 32) hipLaunchKernelGGL(k_attn16_bwd<32>, grid, dim3(256), 0, st, q, k, v, dout, NH, K, heads, nvalid, prob_mask, dq, dkk, dv);
-  else hipLaunchKernelGGL(k_attn16_bwd<64>, grid, dim3(256), 0, st, q, k, v, dout, NH, K, heads, nvalid, prob_mask, dq, dkk, dv);
+  if (drop) launch_bwd<true>(q, k, v, dout, N * heads, K, heads, dk, nvalid, nullptr, dq, dkk, dv, *drop, st);
+  else launch_bwd<false>(q, k, v, dout, N * heads, K, heads, dk, nvalid, prob_mask, dq, dkk, dv, AttnDrop{}, st);
   return true;
 }
 

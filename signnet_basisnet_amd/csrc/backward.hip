@@ -7,7 +7,7 @@
 // slot is valid iff slot < nvalid[node], invalid rows carry zero gradient.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "philox.hpp"
 
 namespace sn {
 namespace {
@@ -343,11 +343,14 @@ __global__ __launch_bounds__(1024) void k_cols_reduce(const float* __restrict__ 
 
 // ============================================================================ per-node set attention backward
 // One wave per (node, head), mirroring k_set_attention: P = softmax(q k^T / sqrt(dk)) over the valid slots, o = P v.
+// DROP: the dropout factors come from the counter-based generator (philox.hpp) instead of `pmask`, one Philox call per four keys in
+// each of the two passes over a query row (recomputed in the second: cheaper than a third [K][K+1] tile of LDS).
+template <bool DROP>
 __global__ __launch_bounds__(64) void k_set_attention_bwd(const float* __restrict__ q, const float* __restrict__ k,
                                                           const float* __restrict__ v, const float* __restrict__ dout, int K,
                                                           int H, int dk, const int32_t* __restrict__ nvalid,
                                                           const float* __restrict__ pmask, float* __restrict__ dq,
-                                                          float* __restrict__ dkk, float* __restrict__ dv) {
+                                                          float* __restrict__ dkk, float* __restrict__ dv, AttnDrop drop) {
   extern __shared__ float sm[];
   const int node = blockIdx.x / H, h = blockIdx.x - node * H;
   const int lane = threadIdx.x;
@@ -384,18 +387,48 @@ __global__ __launch_bounds__(64) void k_set_attention_bwd(const float* __restric
     float zs = 0.f;
     for (int b = 0; b < kv; ++b) { const float e = expf(sp[a * (K + 1) + b] - m); sp[a * (K + 1) + b] = e; zs += e; }
     // with attention dropout the forward used P' = P*m (m = 0 or 1/(1-p)): dP = dP'*m, and dV below needs P'
-    const float* pm = pmask ? pmask + ((int64_t)blockIdx.x * K + a) * K : nullptr;
     float dot = 0.f;
-    for (int b = 0; b < kv; ++b) {
-      const float p = sp[a * (K + 1) + b] / zs, m = pm ? pm[b] : 1.0f, dp = sd[a * (K + 1) + b] * m;
-      sp[a * (K + 1) + b] = p;
-      sd[a * (K + 1) + b] = dp;
-      dot += p * dp;
-    }
-    for (int b = 0; b < kv; ++b) {
-      const float p = sp[a * (K + 1) + b];
-      sd[a * (K + 1) + b] = p * (sd[a * (K + 1) + b] - dot);     // dS
-      sp[a * (K + 1) + b] = p * (pm ? pm[b] : 1.0f);             // P' for dV
+    if constexpr (DROP) {
+      for (int b0 = 0; b0 < kv; b0 += 4) {
+        float f[4];
+        attn_drop_factors(drop, blockIdx.x, a, b0 >> 2, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int b = b0 + r;
+          if (b < kv) {
+            const float p = sp[a * (K + 1) + b] / zs, m = f[r], dp = sd[a * (K + 1) + b] * m;
+            sp[a * (K + 1) + b] = p;
+            sd[a * (K + 1) + b] = dp;
+            dot += p * dp;
+          }
+        }
+      }
+      for (int b0 = 0; b0 < kv; b0 += 4) {
+        float f[4];
+        attn_drop_factors(drop, blockIdx.x, a, b0 >> 2, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int b = b0 + r;
+          if (b < kv) {
+            const float p = sp[a * (K + 1) + b];
+            sd[a * (K + 1) + b] = p * (sd[a * (K + 1) + b] - dot);     // dS
+            sp[a * (K + 1) + b] = p * f[r];                            // P' for dV
+          }
+        }
+      }
+    } else {
+      const float* pm = pmask ? pmask + ((int64_t)blockIdx.x * K + a) * K : nullptr;
+      for (int b = 0; b < kv; ++b) {
+        const float p = sp[a * (K + 1) + b] / zs, m = pm ? pm[b] : 1.0f, dp = sd[a * (K + 1) + b] * m;
+        sp[a * (K + 1) + b] = p;
+        sd[a * (K + 1) + b] = dp;
+        dot += p * dp;
+      }
+      for (int b = 0; b < kv; ++b) {
+        const float p = sp[a * (K + 1) + b];
+        sd[a * (K + 1) + b] = p * (sd[a * (K + 1) + b] - dot);     // dS
+        sp[a * (K + 1) + b] = p * (pm ? pm[b] : 1.0f);             // P' for dV
+      }
     }
   }
   __syncthreads();
@@ -653,7 +686,8 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
 
 namespace sn {
 bool attention16_backward(const float* q, const float* k, const float* v, const float* dout, int64_t N, int K, int heads, int dk,
-                          const int32_t* nvalid, const float* prob_mask, float* dq, float* dkk, float* dv, hipStream_t st);   // attention16.hip
+                          const int32_t* nvalid, const float* prob_mask, const AttnDrop* drop, float* dq, float* dkk, float* dv,
+                          hipStream_t st);   // attention16.hip
 }
 using namespace sn;
 
@@ -774,26 +808,55 @@ extern "C" int sn_masked_layernorm_bwd_acc_f32(const float* x, const float* resi
   return layernorm_bwd_impl(x, residual, dy, R, C, gamma, eps, nvalid, K, du, dgamma, dbeta, scratch, 1, stream);
 }
 
-extern "C" int sn_set_attention_bwd_f32(const float* q, const float* k, const float* v, const float* dout, int64_t N, int K,
-                                        int heads, int dk, const int32_t* nvalid, const float* prob_mask, float* dq,
-                                        float* dk_out, float* dv, void* stream) {
-  SN_REQUIRE(q && k && v && dout && dq && dk_out && dv && N >= 0 && K > 0 && heads > 0 && dk > 0,
-             "sn_set_attention_bwd_f32: bad arguments");
+// both entry points of the set attention's adjoint: `drop` (null: prob_mask or no mask) selects the DROP instantiations
+template <bool DROP>
+static int set_attention_bwd_launch(const char* who, const float* q, const float* k, const float* v, const float* dout, int64_t N, int K,
+                                    int heads, int dk, const int32_t* nvalid, const float* prob_mask, AttnDrop drop, size_t lds,
+                                    float* dq, float* dk_out, float* dv, void* stream) {
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_set_attention_bwd<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return fail(SN_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit", who);
+  hipLaunchKernelGGL(k_set_attention_bwd<DROP>, dim3((unsigned)(N * heads)), dim3(64), lds, (hipStream_t)stream, q, k, v, dout, K,
+                     heads, dk, nvalid, prob_mask, dq, dk_out, dv, drop);
+  SN_CHECK_LAUNCH(who);
+  return SN_OK;
+}
+
+static int set_attention_bwd_impl(const char* who, const float* q, const float* k, const float* v, const float* dout, int64_t N, int K,
+                                  int heads, int dk, const int32_t* nvalid, const float* prob_mask, const AttnDrop* drop, float* dq,
+                                  float* dk_out, float* dv, void* stream) {
+  SN_REQUIRE(q && k && v && dout && dq && dk_out && dv && N >= 0 && K > 0 && heads > 0 && dk > 0, "%s: bad arguments", who);
   if (N == 0) return SN_OK;
-  if (sn::attention16_backward(q, k, v, dout, N, K, heads, dk, nvalid, prob_mask, dq, dk_out, dv, (hipStream_t)stream)) {   // K <= 16
-    SN_CHECK_LAUNCH("sn_set_attention_bwd_f32");
+  if (sn::attention16_backward(q, k, v, dout, N, K, heads, dk, nvalid, prob_mask, drop, dq, dk_out, dv, (hipStream_t)stream)) {   // K <= 16
+    SN_CHECK_LAUNCH(who);
     return SN_OK;
   }
   const size_t lds = ((size_t)4 * K * dk + (size_t)2 * K * (K + 1)) * sizeof(float);
-  SN_REQUIRE(lds <= 160 * 1024, "sn_set_attention_bwd_f32: K=%d dk=%d needs %zu B of LDS (> 160 KiB)", K, dk, lds);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k_set_attention_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return fail(SN_ERR_LAUNCH, "sn_set_attention_bwd_f32: cannot raise the dynamic LDS limit");
-  hipLaunchKernelGGL(k_set_attention_bwd, dim3((unsigned)(N * heads)), dim3(64), lds, (hipStream_t)stream, q, k, v, dout, K,
-                     heads, dk, nvalid, prob_mask, dq, dk_out, dv);
-  SN_CHECK_LAUNCH("sn_set_attention_bwd_f32");
-  return SN_OK;
+  SN_REQUIRE(lds <= 160 * 1024, "%s: K=%d dk=%d needs %zu B of LDS (> 160 KiB)", who, K, dk, lds);
+  return drop ? set_attention_bwd_launch<true>(who, q, k, v, dout, N, K, heads, dk, nvalid, nullptr, *drop, lds, dq, dk_out, dv, stream)
+              : set_attention_bwd_launch<false>(who, q, k, v, dout, N, K, heads, dk, nvalid, prob_mask, AttnDrop{}, lds, dq, dk_out, dv,
+                                                stream);
+}
+
+extern "C" int sn_set_attention_bwd_f32(const float* q, const float* k, const float* v, const float* dout, int64_t N, int K,
+                                        int heads, int dk, const int32_t* nvalid, const float* prob_mask, float* dq,
+                                        float* dk_out, float* dv, void* stream) {
+  return set_attention_bwd_impl("sn_set_attention_bwd_f32", q, k, v, dout, N, K, heads, dk, nvalid, prob_mask, nullptr, dq, dk_out, dv,
+                                stream);
+}
+
+extern "C" int sn_set_attention_drop_bwd_f32(const float* q, const float* k, const float* v, const float* dout, int64_t N, int K,
+                                             int heads, int dk, const int32_t* nvalid, uint32_t threshold, float scale,
+                                             const int64_t* state, uint32_t site, float* dq, float* dk_out, float* dv, void* stream) {
+  SN_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 7) == 0,
+             "sn_set_attention_drop_bwd_f32: state must be an 8-byte aligned pointer");
+  SN_REQUIRE(scale >= 1.0f && scale < INFINITY, "sn_set_attention_drop_bwd_f32: scale must be 1 / (1 - p) with 0 <= p < 1");
+  SN_REQUIRE(N >= 0 && heads > 0 && N <= (int64_t)0xFFFFFFFFll / heads && K <= 65536,
+             "sn_set_attention_drop_bwd_f32: the mask contract needs N * heads < 2^32 and K <= 65536");
+  const AttnDrop drop{threshold, scale, state, site};
+  return set_attention_bwd_impl("sn_set_attention_drop_bwd_f32", q, k, v, dout, N, K, heads, dk, nvalid, nullptr, &drop, dq, dk_out,
+                                dv, stream);
 }
 
 extern "C" int sn_gine_aggregate_bwd_f32(const float* h, const float* ee, const float* g, int64_t N, int C,

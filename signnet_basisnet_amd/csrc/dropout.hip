@@ -10,30 +10,11 @@
 // One Philox call yields the four words of one aligned group of four logical elements; a lane owns one group.  Memory-bound, and at
 // this project's shapes ([3001, 128], [E, 77]: ~100-400 K elements) latency-bound: one group per lane keeps every load of a lane in
 // flight at once, the grid is capped at 2048 blocks (8 per CU) and strides beyond that.
-#include "common.hpp"
+#include "philox.hpp"
 
 namespace sn {
 
 constexpr int DROPOUT_MAX_BLOCKS = 2048;
-
-struct philox_out { uint32_t w[4]; };
-
-__device__ __forceinline__ philox_out philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  philox_out o;
-  o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
-  return o;
-}
 
 // Vector path: C % 4 == 0, base % 4 == 0, every ld % 4 == 0, every pointer 16-byte aligned — a group is four consecutive columns
 // of one row: one 128-bit load (two with a residual) and one 128-bit store per Philox call.

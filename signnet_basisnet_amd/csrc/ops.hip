@@ -1,7 +1,7 @@
 // ops.hip — the layer-at-a-time kernels behind the C ABI (include/signnet_hip.h).
 // One kernel per op class the reference's forward inherits from PyG / torch_scatter / DGL / ATen
 // (SURVEY.md §2.1).  The fused whole-stage kernels (fused_*.hip) reuse the same GEMM convention.
-#include "common.hpp"
+#include "philox.hpp"
 
 namespace sn {
 
@@ -1024,10 +1024,13 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
 
 // ============================================================================ per-node set attention
 // One wave per (node, head).  q,k,v rows are [N*K, H*dk]; head h owns columns [h*dk, (h+1)*dk).
+// DROP: the dropout factors come from the counter-based generator (philox.hpp) instead of `pmask`: a query row's loop over its keys
+// takes one Philox call per four keys.
+template <bool DROP>
 __global__ __launch_bounds__(64) void k_set_attention(const float* __restrict__ q, const float* __restrict__ k,
                                                       const float* __restrict__ v, int K, int H, int dk,
                                                       const int32_t* __restrict__ nvalid, const float* __restrict__ pmask,
-                                                      float* __restrict__ out) {
+                                                      float* __restrict__ out, AttnDrop drop) {
   extern __shared__ float sm[];
   const int node = blockIdx.x / H, h = blockIdx.x - node * H;
   const int lane = threadIdx.x;
@@ -1060,8 +1063,18 @@ __global__ __launch_bounds__(64) void k_set_attention(const float* __restrict__ 
     float z = 0.f;
     for (int b = 0; b < kv; ++b) { float e = expf(sp[a * (K + 1) + b] - m); sp[a * (K + 1) + b] = e; z += e; }
     // attention dropout (transformer_module.py:55): the caller's mask holds 0 or 1/(1-p) per (node, head, query, key)
-    const float* pm = pmask ? pmask + ((int64_t)blockIdx.x * K + a) * K : nullptr;
-    for (int b = 0; b < kv; ++b) sp[a * (K + 1) + b] = sp[a * (K + 1) + b] / z * (pm ? pm[b] : 1.0f);
+    if constexpr (DROP) {
+      for (int b0 = 0; b0 < kv; b0 += 4) {
+        float f[4];
+        attn_drop_factors(drop, blockIdx.x, a, b0 >> 2, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (b0 + r < kv) sp[a * (K + 1) + b0 + r] = sp[a * (K + 1) + b0 + r] / z * f[r];
+      }
+    } else {
+      const float* pm = pmask ? pmask + ((int64_t)blockIdx.x * K + a) * K : nullptr;
+      for (int b = 0; b < kv; ++b) sp[a * (K + 1) + b] = sp[a * (K + 1) + b] / z * (pm ? pm[b] : 1.0f);
+    }
   }
   __syncthreads();
   for (int i = lane; i < K * dk; i += 64) {
@@ -1166,7 +1179,7 @@ __global__ __launch_bounds__(256) void k_segment_pool(const float* __restrict__ 
 
 namespace sn {
 bool attention16_forward(const float* q, const float* k, const float* v, int64_t N, int K, int heads, int dk, const int32_t* nvalid,
-                         const float* prob_mask, float* out, hipStream_t st);     // attention16.hip
+                         const float* prob_mask, const AttnDrop* drop, float* out, hipStream_t st);     // attention16.hip
 }
 using namespace sn;
 
@@ -1601,25 +1614,49 @@ extern "C" int sn_masked_layernorm_f32(const float* x, const float* residual, in
   return SN_OK;
 }
 
-extern "C" int sn_set_attention_f32(const float* q, const float* k, const float* v, int64_t N, int K, int heads,
-                                    int dk, const int32_t* nvalid, const float* prob_mask, float* out, void* stream) {
-  SN_REQUIRE(q && k && v && out && N >= 0 && K > 0 && heads > 0 && dk > 0, "sn_set_attention_f32: bad arguments");
+// both entry points of the set attention: `drop` (null: prob_mask or no mask) selects the DROP instantiations
+template <bool DROP>
+static int set_attention_launch(const char* who, const float* q, const float* k, const float* v, int64_t N, int K, int heads, int dk,
+                                const int32_t* nvalid, const float* prob_mask, AttnDrop drop, size_t lds, float* out, void* stream) {
+  if (lds > 64 * 1024) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_set_attention<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+      return fail(SN_ERR_LAUNCH, "%s: cannot raise dynamic LDS limit", who);
+  }
+  hipLaunchKernelGGL(k_set_attention<DROP>, dim3((unsigned)(N * heads)), dim3(64), lds, (hipStream_t)stream, q, k, v, K, heads,
+                     dk, nvalid, prob_mask, out, drop);
+  SN_CHECK_LAUNCH(who);
+  return SN_OK;
+}
+
+static int set_attention_impl(const char* who, const float* q, const float* k, const float* v, int64_t N, int K, int heads, int dk,
+                              const int32_t* nvalid, const float* prob_mask, const AttnDrop* drop, float* out, void* stream) {
+  SN_REQUIRE(q && k && v && out && N >= 0 && K > 0 && heads > 0 && dk > 0, "%s: bad arguments", who);
   size_t lds = ((size_t)3 * K * dk + (size_t)K * (K + 1)) * sizeof(float);
-  SN_REQUIRE(lds <= 160 * 1024, "sn_set_attention_f32: K=%d dk=%d needs %zu B of LDS (> 160 KiB)", K, dk, lds);
+  SN_REQUIRE(lds <= 160 * 1024, "%s: K=%d dk=%d needs %zu B of LDS (> 160 KiB)", who, K, dk, lds);
   if (N == 0) return SN_OK;
-  if (sn::attention16_forward(q, k, v, N, K, heads, dk, nvalid, prob_mask, out, (hipStream_t)stream)) {     // K <= 16: matrix pipe
-    SN_CHECK_LAUNCH("sn_set_attention_f32");
+  if (sn::attention16_forward(q, k, v, N, K, heads, dk, nvalid, prob_mask, drop, out, (hipStream_t)stream)) {     // K <= 16: matrix pipe
+    SN_CHECK_LAUNCH(who);
     return SN_OK;
   }
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_set_attention), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return fail(SN_ERR_LAUNCH, "sn_set_attention_f32: cannot raise dynamic LDS limit");
-  }
-  hipLaunchKernelGGL(k_set_attention, dim3((unsigned)(N * heads)), dim3(64), lds, (hipStream_t)stream, q, k, v, K, heads,
-                     dk, nvalid, prob_mask, out);
-  SN_CHECK_LAUNCH("sn_set_attention_f32");
-  return SN_OK;
+  return drop ? set_attention_launch<true>(who, q, k, v, N, K, heads, dk, nvalid, nullptr, *drop, lds, out, stream)
+              : set_attention_launch<false>(who, q, k, v, N, K, heads, dk, nvalid, prob_mask, AttnDrop{}, lds, out, stream);
+}
+
+extern "C" int sn_set_attention_f32(const float* q, const float* k, const float* v, int64_t N, int K, int heads,
+                                    int dk, const int32_t* nvalid, const float* prob_mask, float* out, void* stream) {
+  return set_attention_impl("sn_set_attention_f32", q, k, v, N, K, heads, dk, nvalid, prob_mask, nullptr, out, stream);
+}
+
+extern "C" int sn_set_attention_drop_f32(const float* q, const float* k, const float* v, int64_t N, int K, int heads, int dk,
+                                         const int32_t* nvalid, uint32_t threshold, float scale, const int64_t* state, uint32_t site,
+                                         float* out, void* stream) {
+  SN_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 7) == 0, "sn_set_attention_drop_f32: state must be an 8-byte aligned pointer");
+  SN_REQUIRE(scale >= 1.0f && scale < INFINITY, "sn_set_attention_drop_f32: scale must be 1 / (1 - p) with 0 <= p < 1");
+  SN_REQUIRE(N >= 0 && heads > 0 && N <= (int64_t)0xFFFFFFFFll / heads && K <= 65536,
+             "sn_set_attention_drop_f32: the mask contract needs N * heads < 2^32 and K <= 65536");
+  const AttnDrop drop{threshold, scale, state, site};
+  return set_attention_impl("sn_set_attention_drop_f32", q, k, v, N, K, heads, dk, nvalid, nullptr, &drop, out, stream);
 }
 
 namespace sn {

@@ -27,6 +27,10 @@ also binds the trees' baseline models, `dropin.BASELINE_ALIASES`: `baseline_gin`
 `model.gnn_type`) with `train.dropout`; without it a non-zero dropout is refused as before:
 
     cd <reference>/GraphPrediction  && python -m signnet_basisnet_amd.dropin.run --feature-dropout main_ZINC_graph_regression.py --config configs/gatedgcn/GatedGCN_ZINC_NoPE.json --dropout 0.1
+
+`--attn-dropout=counter` makes "counter" the `attn_dropout_source` of every `pyg.SignNetGNN` the run constructs (Alchemy, GINESignNetPyG):
+the train-mode attention-dropout masks are evaluated inside the attention kernels from (seed, step) — seed torch.initial_seed() unless
+the script calls `seed_dropout` — instead of drawn with torch's device generator.
 """
 from __future__ import annotations
 
@@ -47,6 +51,13 @@ def main(argv=None) -> None:
             gnn_types, argv = True, argv[1:]
         elif argv[0] == "--feature-dropout":
             feature_dropout, argv = True, argv[1:]
+        elif argv[0].startswith("--attn-dropout="):
+            from ..pyg import SignNetGNN
+            try:
+                SignNetGNN.DEFAULT_ATTN_DROPOUT_SOURCE = SignNetGNN.check_attn_dropout_source(argv[0].split("=", 1)[1])
+            except ValueError as e:
+                raise SystemExit(f"{argv[0]}: {e}")
+            argv = argv[1:]
         elif argv[0].startswith("--baselines="):
             value = argv[0].split("=", 1)[1]
             if value != "all":
@@ -61,7 +72,7 @@ def main(argv=None) -> None:
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] <entry script> "
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] [--attn-dropout=counter] <entry script> "
                          "[script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
     if argv[0] == "-m":

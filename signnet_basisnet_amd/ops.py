@@ -684,13 +684,43 @@ def attention_dropout_mask(N, K, heads, p, device):
     return u
 
 
-def set_attention(q, k, v, N, K, heads, nvalid=None, prob_mask=None):
+ATTN_DROP_SITE = 0x41540000      # + index of the rho layer (signnet_hip.h: disjoint from the small ordinals of the feature-dropout sites)
+
+
+def attention_drop_args(drop, who="set_attention"):
+    """drop = (p, snap, site) -> (threshold, scale, snap, site) of sn_set_attention_drop[_bwd]_f32, or None for p == 0 (no mask)."""
+    p, snap, site = drop
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{who}: attention dropout probability has to be in [0, 1), but got {p}")
+    if p == 0.0:
+        return None
+    require_cuda(snap)
+    if snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous():
+        raise ValueError(f"{who}: snap must be the int64 [2] {{seed, step}} tensor of a DropoutState")
+    thr, scale = dropout_threshold(p)
+    return thr, scale, snap, int(site) & 0xFFFFFFFF
+
+
+def set_attention(q, k, v, N, K, heads, nvalid=None, prob_mask=None, drop=None):
+    """prob_mask: an explicit [N, heads, K, K] mask of 0 / 1/(1-p) factors (attention_dropout_mask), or drop = (p, snap, site): the
+    same factors from the counter-based generator inside the kernel (signnet_hip.h: the mask contract; snap = the {seed, step} words
+    of a DropoutState).  Not both.  p == 0: no mask, the plain launch."""
     require_cuda(q, k, v)
     q, k, v = _f32c(q, "q"), _f32c(k, "k"), _f32c(v, "v")
     D = q.shape[-1]
+    if prob_mask is not None and drop is not None:
+        raise ValueError("set_attention: give prob_mask or drop, not both")
     if prob_mask is not None and (prob_mask.shape != (N, heads, K, K) or not prob_mask.is_contiguous()):
         raise ValueError("set_attention: prob_mask must be a contiguous [N, heads, K, K] tensor")
     out = torch.empty_like(q)
+    args = None if drop is None else attention_drop_args(drop)
+    if args is not None:
+        thr, scale, snap, site = args
+        with _span("sn_set_attention_drop_f32"):
+            check(lib().sn_set_attention_drop_f32(ptr(q), ptr(k), ptr(v), N, K, heads, D // heads, ptr(nvalid), thr, scale, ptr(snap), site,
+                                                  ptr(out), stream()), "sn_set_attention_drop_f32")
+        return out
     with _span("sn_set_attention_f32"):
         check(lib().sn_set_attention_f32(ptr(q), ptr(k), ptr(v), N, K, heads, D // heads, ptr(nvalid), ptr(prob_mask), ptr(out),
                                          stream()), "sn_set_attention_f32")

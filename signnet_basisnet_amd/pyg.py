@@ -469,7 +469,7 @@ def host_max_nodes(data):
     return None
 
 
-class SignNetGNN(nn.Module):
+class SignNetGNN(ops.DropoutHolder, nn.Module):
     """HIP SignNet + GINE.  `variant` selects which reference tree's semantics are reproduced.
 
     Extra keyword (not in the reference): `max_k` — use only the first `max_k` eigenvectors
@@ -483,6 +483,15 @@ class SignNetGNN(nn.Module):
     stages, and the graphs beyond the fused limits that strict mode re-runs there: such a batch has its oversize graphs at
     "highest" and the rest at the chosen mode) and the GINE stage.  The reduced modes are built for hidden widths of 4, 7 or 8
     16-channel tiles (52..64, 100..128); at any other width assigning one raises ValueError — a mode is never replaced by another.
+
+    `attn_dropout_source` (a property, default "generator"): where the train-mode attention-dropout masks come from.  "generator":
+    torch's device generator, drawn outside the attention kernels as an explicit [N, heads, K, K] mask per rho layer (the reference's
+    own draws under torch.manual_seed).  "counter": evaluated inside the attention kernels from (seed, step, rho layer, node, head,
+    query, key) — signnet_hip.h, the mask contract; `seed_dropout(seed, step=0)` / `dropout_state(device)` of ops.DropoutHolder hold
+    the two words (never a buffer, never a state_dict key).  Nothing of the mask's size is stored, a captured step draws its own
+    masks at every replay, and a padded step draws the masks of the unpadded one.  Explicit masks in `_attn_masks` win in either
+    mode; eval reads none of this.  Data-parallel ranks should seed differently (seed + rank): the mask is indexed by the node row
+    within the rank's batch.
     """
 
     def __init__(self, node_feat, edge_feat, n_hid, n_out, nl_signnet, nl_gnn, nl_rho=4, ignore_eigval=False,
@@ -520,6 +529,7 @@ class SignNetGNN(nn.Module):
         # train-mode dropout of the attention probabilities (ScaledDotProductAttention's default attn_dropout=0.1,
         # transformer_module.py:46-55 — the only dropout the reference leaves active); 0.0 switches it off
         self.attn_dropout = 0.1
+        self._attn_dropout_source = self.DEFAULT_ATTN_DROPOUT_SOURCE     # see the property below
         self._pending, self._free_hosts, self._flags_host = [], [], None
         self.sign_net = SignNet(n_hid, nl_signnet, self.nl_rho, variant, ignore_eigval)
         self.gnn = GNN(node_feat, edge_feat, n_hid, n_out, nl_gnn, variant)
@@ -527,6 +537,31 @@ class SignNetGNN(nn.Module):
         # nn.Module.load_state_dict on a PARENT (a wrapper, DDP, a bigger model) recurses through _load_from_state_dict and never
         # calls this module's load_state_dict override — the post hook below does fire for every submodule of that recursion
         self.register_load_state_dict_post_hook(_drop_prepared)
+
+    @property
+    def attn_dropout_source(self):
+        """"generator" | "counter": the source of the train-mode attention-dropout masks (class docstring)."""
+        return getattr(self, "_attn_dropout_source", "generator")
+
+    DEFAULT_ATTN_DROPOUT_SOURCE = "generator"       # what a new model starts with (the drop-in runner's --attn-dropout=counter)
+
+    @staticmethod
+    def check_attn_dropout_source(name):
+        if name not in ("generator", "counter"):
+            raise ValueError(f"attn_dropout_source {name!r}: \"generator\" or \"counter\"")
+        return name
+
+    @attn_dropout_source.setter
+    def attn_dropout_source(self, name):
+        self._attn_dropout_source = self.check_attn_dropout_source(name)
+
+    def _dropout_active(self):
+        """Whether a train-mode forward of this model advances and reads the {seed, step} words (ops.DropoutHolder)."""
+        return self.attn_dropout_source == "counter" and float(self.attn_dropout or 0.0) > 0.0
+
+    def _attn_drop(self, snap, li):
+        """The `drop` argument of set_attention for rho layer li (None in generator mode)."""
+        return None if snap is None else (self.attn_dropout, snap, ops.ATTN_DROP_SITE + li)
 
     @property
     def matmul_precision(self):
@@ -945,15 +980,16 @@ class SignNetGNN(nn.Module):
         def lin(x_, m, relu=False):
             return T.linear_module(x_, m, nv, K, relu) if stage else AG.linear(x_, m.weight, m.bias, nv, K, relu=relu)
         static_masks = getattr(self, "_attn_masks", None)       # train_graph.GraphedStep: masks drawn outside the captured step
+        snap = self._dropout_begin(x.device) if self._dropout_active() else None     # counter source: one {seed, step} snapshot per forward
         for li, tl in enumerate(sn.rho.transformer_layers):
             a, f = tl.slf_attn, tl.pos_ffn
             q, k, v = T.qkv(x, a.w_qs, a.w_ks, a.w_vs, nv, K) if stage else (lin(x, a.w_qs), lin(x, a.w_ks), lin(x, a.w_vs))
             pm = static_masks[li] if static_masks is not None else None
             if pm is not None and tuple(pm.shape) != (N, N_HEAD, K, K):   # masks of another batch shape: never reuse them
                 pm = None
-            if pm is None:
+            if pm is None and snap is None:
                 pm = ops.attention_dropout_mask(N, K, N_HEAD, self.attn_dropout, x.device)
-            o = AG.set_attention(q, k, v, N, K, N_HEAD, nv, pm)
+            o = AG.set_attention(q, k, v, N, K, N_HEAD, nv, pm, None if pm is not None else self._attn_drop(snap, li))
             o = lin(o, a.fc)
             y = AG.masked_layernorm(o, x, a.norm.ln.weight, a.norm.ln.bias, LN_EPS, nv, K)
             z = lin(y, f.w_1, relu=True)
@@ -1163,14 +1199,16 @@ class SignNetGNN(nn.Module):
                 p = _lin_bn(p, E_["l1"], E_["bn1"], train, nv, K, relu=True)
                 x = ops.masked_affine(x, nv, K, residual=p)
             given = getattr(self, "_attn_masks", None) if train else None      # explicit masks: the reference's own draws (tests), GraphedStep
+            snap = self._dropout_begin(x.device) if train and self._dropout_active() else None      # counter source
             for li, L in enumerate(P["rho"]):
                 q = ops.masked_linear(x, L["q"], nv, K)
                 k = ops.masked_linear(x, L["k"], nv, K)
                 v = ops.masked_linear(x, L["v"], nv, K)
                 pm = None
                 if train:
-                    pm = given[li] if given is not None else ops.attention_dropout_mask(N, K, N_HEAD, self.attn_dropout, x.device)
-                o = ops.set_attention(q, k, v, N, K, N_HEAD, nv, pm)
+                    pm = given[li] if given is not None else None if snap is not None else \
+                        ops.attention_dropout_mask(N, K, N_HEAD, self.attn_dropout, x.device)
+                o = ops.set_attention(q, k, v, N, K, N_HEAD, nv, pm, None if pm is not None else self._attn_drop(snap, li))
                 o = ops.masked_linear(o, L["fc"], nv, K)
                 y = ops.masked_layernorm(o, x, L["ln1"][0], L["ln1"][1], LN_EPS, nv, K)
                 z = ops.masked_linear(y, L["w1"], nv, K, relu=True)

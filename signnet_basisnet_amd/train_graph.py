@@ -48,7 +48,8 @@ class GraphedStep:
         model.train()
         # the attention dropout (transformer_module.py:46,55; the one dropout the reference leaves active) is random per step: its masks
         # are drawn OUTSIDE the graph with torch's device generator — the same draws in the same order as the eager step — into static
-        # buffers the captured kernels read
+        # buffers the captured kernels read.  With model.attn_dropout_source == "counter" there is nothing to draw: (None, None), the
+        # attention kernels evaluate the masks from the {seed, step} words whose advance is recorded inside the step
         self._draw, self._masks = _mask_buffers(model, int(data.batch.numel()), int(model.max_k), data.batch.device)
         self._status = None
 
@@ -114,8 +115,10 @@ class GraphedStep:
 
 
 def _mask_buffers(model, N, K, dev):
-    """(draw, static buffers) of the attention-dropout masks [N, H, K, K] per rho layer, or (None, None) without dropout."""
-    if not getattr(model, "attn_dropout", 0.0):
+    """(draw, static buffers) of the attention-dropout masks [N, H, K, K] per rho layer, or (None, None) without dropout — and with
+    the counter source (model.attn_dropout_source == "counter"): the attention kernels evaluate the masks themselves from the model's
+    {seed, step} words, whose advance and snapshot are recorded inside the captured step, so nothing is drawn, kept or copied here."""
+    if not getattr(model, "attn_dropout", 0.0) or getattr(model, "attn_dropout_source", "generator") == "counter":
         return None, None
     from . import ops
     from .pyg import N_HEAD
