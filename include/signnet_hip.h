@@ -841,6 +841,12 @@ int sn_rho_fused_f32(const sn_rho_params* params, const float* x, const float* e
  * value products (fp32 MFMA) are not split-packed GEMMs and do not change.  sn_rho_fused_f32 is precision = SN_PREC_HIGHEST. */
 int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x, const float* eigen_values, const int32_t* graph_ptr, int64_t B,
                           int64_t N, const sn_plan_bins* bins, int kmax, int K, float* out_sum, int precision, void* stream);
+/* The same with the workgroup form chosen by the call: waves = 0 is the library's choice (what sn_rho_fused_prec_f32 runs); 4, 8 or
+ * 12 waves per workgroup (= nodes per bin of the register-attention forms) force that form at any N — 12: the one-layer form at
+ * d in (112, 128]; 8: the register-attention forms of d = 64 / 128 and the head-padded ones; both SN_PREC_HIGHEST only.  A form that
+ * is not built for the net and batch is an error.  Every form computes the same bits. */
+int sn_rho_fused_form_f32(const sn_rho_params* params, const float* x, const float* eigen_values, const int32_t* graph_ptr, int64_t B,
+                          int64_t N, const sn_plan_bins* bins, int kmax, int K, float* out_sum, int precision, int waves, void* stream);
 
 /* The GINE network on top of the positional encoding, one launch: rho's output Linear+BatchNorm on the slot
  * sum (sign_net.py:71), then GNN.forward (model.py:36-64 / core/model.py:44-79): input encoder

@@ -55,6 +55,7 @@ SIGNATURES = {
     "sn_rho_fused_f32": [_p, _p, _p, _p, _l, _l, _p, _i, _i, _p, _p],
     "sn_phi_fused_prec_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p],
     "sn_rho_fused_prec_f32": [_p, _p, _p, _p, _l, _l, _p, _i, _i, _p, _i, _p],
+    "sn_rho_fused_form_f32": [_p, _p, _p, _p, _l, _l, _p, _i, _i, _p, _i, _i, _p],
     "sn_gnn_fused_f32": [_p, _p, _i, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _p, _p],
     "sn_gnn_front_bytes": [_p],                          # (int64 byte count: _SPECIAL_RESTYPE)
     "sn_batch_plan_front": [_p, _l, _l, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p],

@@ -106,7 +106,8 @@ __device__ __forceinline__ float tile_rowsum(float v) {
 // NW (round 6; REGATTN only): waves per workgroup = nodes per bin.  The hypothesis: rho is bound by its weight stream — a layer is six
 // split-packed [d, d] matrices = 720 KB of LDS-DMA per bin at d = 128, two 4-wave workgroups per CU = two streams; the register-attention
 // variants keep their rows in registers, so ONE 8-wave workgroup per CU could hold the same 8 nodes behind ONE stream.  Built (NW = 8),
-// bit-identical outputs, and measured SLOWER (61.5 -> 72.9 us on the headline batch): see rho_eight_waves() below.  Default: 4.
+// bit-identical outputs, and measured SLOWER (61.5 -> 72.9 us on the headline batch): see rho_waves_env() below.  Default: 4.
+// (That run was two waves per SIMD on 1.44 rounds; at THREE waves per SIMD and one round the single stream does pay: NW = 12 below.)
 // PREC: the product set of the six [d, d] projections of a layer (fused_common.hpp); the attention's score and value products (fp32
 // MFMA), the softmax, the LayerNorms and the slot sum are the same arithmetic in every mode.
 // RES3 (REGATTN && ONE && NW == 4, instantiated for NT = 8 only): compiled for THREE waves per SIMD, i.e. <= 168 registers and no
@@ -115,12 +116,17 @@ __device__ __forceinline__ float tile_rowsum(float v) {
 // is control flow only: no eigenvalue-encoder path (ONE has none), and a wave without rows runs the layer on zero rows instead of
 // branching round every product — with one path the compiler no longer carries qf / o / the row array round the other (242 registers
 // before, and 328 bytes of private segment when merely asked for three waves per SIMD).  See launch_rho.
+// RES3 && NW == 12: the same three waves per SIMD as ONE workgroup per CU — twelve nodes per bin behind one weight ring, one chunk
+// barrier across the twelve waves.  The body is the four-wave one (a wave's rows, products and stores do not depend on NW), so the
+// outputs repeat it bit for bit; each chunk is staged by two DMA shares per wave, the surplus ones re-staging the last fragment
+// (WRing::issue).  See dispatch_rho for when it runs.
 template <int NT, bool REGATTN, bool ONE, bool HP = false, int NW = 4, int PREC = PREC_HIGHEST, bool RES3 = false>
 // (the LDS-attention variants hold two 64-row images beside the weight ring: one workgroup per CU fits, so they may use the whole
 //  register file of a SIMD — 512 registers per lane, no private segment)
-__global__ __launch_bounds__(64 * NW, REGATTN ? (RES3 ? 3 : 2) : 1) void k_rho_fused(RhoStruct S, sn_rho_params P) {
-  static_assert(NW == 4 || (NW == 8 && REGATTN), "eight waves: the register-attention variants only (no 64-row LDS images)");
-  static_assert(!RES3 || (REGATTN && ONE && NW == 4), "three resident workgroups: the one-layer register-attention form only");
+__global__ __launch_bounds__(64 * NW, REGATTN ? (RES3 ? (NW == 12 ? 1 : 3) : 2) : 1) void k_rho_fused(RhoStruct S, sn_rho_params P) {
+  static_assert(NW == 4 || (NW == 8 && REGATTN) || (NW == 12 && RES3),
+                "eight waves: the register-attention variants only (no 64-row LDS images); twelve: the three-waves-per-SIMD form only");
+  static_assert(!RES3 || (REGATTN && ONE && (NW == 4 || NW == 12)), "three waves per SIMD: the one-layer register-attention form only");
   constexpr int NTHR = 64 * NW;
   constexpr int D = 16 * NT;
   constexpr int LD = D + 4;
@@ -911,7 +917,7 @@ static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_b
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     cus = n > 0 ? n : 256;
   }
-  // Workgroups resident per CU = what the instance's registers and LDS allow: one 8-wave workgroup (one weight stream); two 4-wave
+  // Workgroups resident per CU = what the instance's registers and LDS allow: one 8- or 12-wave workgroup (one weight stream); two 4-wave
   // workgroups (two streams) for the instances compiled for two waves per SIMD; THREE for the 168-register form of the one-layer
   // d = 128 instance (RES3: 164 registers, 3 x 47 KB of LDS) and for the one-layer hidden-64 instances (144-146 registers, 3 x 28 KB),
   // when the batch has more bins than two per CU hold — bins of a second round ran alone on their CU for a whole chain latency.
@@ -922,8 +928,9 @@ static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_b
   //  242 registers a third workgroup is never resident — that run only changed which slot picked up a second bin.)
   constexpr bool three = REGATTN && ONE && NW == 4 && (RES3 || (NT == 4 && PREC == PREC_HIGHEST));
   const int64_t bins = REGATTN ? ((int64_t)S.N + NW - 1) / NW : bins_bound;
-  const int64_t per_cu = NW == 8 ? 1 : ((three && rho_three_resident() && bins > (int64_t)2 * cus) ? 3 : 2);
+  const int64_t per_cu = NW >= 8 ? 1 : ((three && rho_three_resident() && bins > (int64_t)2 * cus) ? 3 : 2);
   int64_t grid = bins_bound < per_cu * cus ? bins_bound : per_cu * cus;
+  if (NW == 12 && bins < grid) grid = bins;      // (twelve waves: one workgroup per bin, no workgroup that only exits)
 #ifdef SN_RHO_GRID1
   grid = cus;
 #endif
@@ -934,16 +941,37 @@ static int launch_rho(const RhoStruct& S, const sn_rho_params& P, int64_t bins_b
 
 // (A/B switch of the profile scripts: SN_RHO_WAVES=8 in the environment puts the register-attention variants of the common widths on
 //  8-wave workgroups.  MEASURED SLOWER and therefore off by default — profiles/scripts/ab_env.sh, one box, alternating: headline rho
-//  61.5 -> 72.9 us, Alchemy 203.7 -> 246.8, hidden 64 16.6 -> 19.8: the stream is not what bounds rho; eight waves meeting at every
-//  chunk barrier cost more than the second stream they save.)
-static bool rho_eight_waves() {
+//  61.5 -> 72.9 us, Alchemy 203.7 -> 246.8, hidden 64 16.6 -> 19.8: eight waves meeting at every chunk barrier cost more than the
+//  second stream they save.  Those runs were two waves per SIMD, one workgroup alone on its CU, 1.44 rounds on the headline batch;
+//  "the stream is not what bounds rho", concluded from them here, did not hold up.  profiles/rho_twelve_waves.json: with the LDS-DMA
+//  of the chunk steps compiled out (wrong results, same instruction stream) the three-resident kernel falls from 54.0 to 47.5 us, so
+//  the stream costs it 6.5 us; ONE twelve-wave workgroup per CU — the same three waves per SIMD, one round, one stream — runs the
+//  headline batch in 51.3 us alone (-2.7) and 53.8 against 57.0 us in the bench's kernel trace.  It loses wherever its twelve-node
+//  bins need a second round (4 101 nodes: 97.0 against 82.0 us), hence the rule in dispatch_rho.
+//  SN_RHO_WAVES=12 / =4 force the twelve-wave / four-wave form of the one-layer d = 128 instance at any N; read once.)
+static int rho_waves_env() {
   static int v = -1;
-  if (v < 0) { const char* e = getenv("SN_RHO_WAVES"); v = (e && e[0] == '8') ? 1 : 0; }
-  return v == 1;
+  if (v < 0) {
+    const char* e = getenv("SN_RHO_WAVES");
+    v = !e ? 0 : (e[0] == '8' ? 8 : ((e[0] == '1' && e[1] == '2') ? 12 : (e[0] == '4' ? 4 : 0)));
+  }
+  return v;
+}
+// waves per workgroup asked for: the call's own choice (sn_rho_fused_form_f32), else the environment's, else 0 = the rules below
+static int rho_waves(int waves) { return waves ? waves : rho_waves_env(); }
+
+static int rho_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
+    cus = n > 0 ? n : 256;
+  }
+  return cus;
 }
 
 template <bool REGATTN, bool ONE, int PREC = PREC_HIGHEST>
-static int dispatch_rho(int nt, const RhoStruct& S, const sn_rho_params& P, int64_t bound, hipStream_t st) {
+static int dispatch_rho(int nt, const RhoStruct& S, const sn_rho_params& P, int64_t bound, int waves, hipStream_t st) {
   if constexpr (PREC != PREC_HIGHEST) {
     // the reduced product sets: the tile counts of the shipped configurations (hidden 64 / 108 / 128), four-wave workgroups
     switch (nt) {
@@ -956,14 +984,23 @@ static int dispatch_rho(int nt, const RhoStruct& S, const sn_rho_params& P, int6
   } else {
     if constexpr (REGATTN) {
       // the common widths on 8-wave workgroups (one weight stream per CU)
-      if (rho_eight_waves()) {
+      if (rho_waves(waves) == 8) {
         if (nt == 8) return launch_rho<8, true, ONE, false, 8>(S, P, bound, st);
         if (nt == 4) return launch_rho<4, true, ONE, false, 8>(S, P, bound, st);
       }
     }
     if constexpr (REGATTN && ONE) {
-      // one layer, d in (112, 128]: the 168-register form (three workgroups resident per CU when the batch has the bins for them)
-      if (nt == 8 && rho_three_resident()) return launch_rho<8, true, true, false, 4, PREC_HIGHEST, true>(S, P, bound, st);
+      if (nt == 8) {
+        // one layer, d in (112, 128]: the 168-register form, three waves per SIMD.  As ONE twelve-wave workgroup per CU (one weight
+        // stream per CU instead of three) where the four-wave form would run three resident workgroups per CU and the twelve-node bins
+        // fit one round: bins4 > 2 CUs and ceil(N / 12) <= CUs.  SN_RHO_WAVES = 12 / 4 or the call's `waves` force either form at any N.
+        const int w = rho_waves(waves);
+        const int64_t cus = rho_cus(), bins4 = ((int64_t)S.N + 3) / 4, bins12 = ((int64_t)S.N + 11) / 12;
+        if (w == 12 || (w == 0 && rho_three_resident() && bins4 > 2 * cus && bins12 <= cus))
+          return launch_rho<8, true, true, false, 12, PREC_HIGHEST, true>(S, P, bound, st);
+        // (three workgroups resident per CU when the batch has the bins for them)
+        if (rho_three_resident()) return launch_rho<8, true, true, false, 4, PREC_HIGHEST, true>(S, P, bound, st);
+      }
     }
     switch (nt) {
       case 1: return launch_rho<1, REGATTN, ONE>(S, P, bound, st);
@@ -980,19 +1017,25 @@ static int dispatch_rho(int nt, const RhoStruct& S, const sn_rho_params& P, int6
 
 // variant choice + launch of one product set (the arguments are those of sn_rho_fused_prec_f32, already checked)
 template <int PREC>
-static int rho_launch(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st) {
+static int rho_launch(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, int waves, hipStream_t st) {
   // attention in registers when every node has <= 16 slots and the head width is a multiple of 16
   const bool one = P.n_layers == 1 && !P.has_pos;
   // most valid slots any node can have: kmax when set, else the dense slot count K (= the largest graph; all eigenvectors)
   const int kcap = (kmax > 0 && kmax < K) ? kmax : K;
   SN_REQUIRE(kcap > 16 || bins->node_graph, "sn_rho_fused_f32: sn_plan_bins.node_graph is needed when every node has <= 16 slots");
+  // a form asked for by the CALL must exist for this net and batch (the environment's switch only applies where it does)
+  const bool heads16 = ((P.d / P.heads) & 15) == 0;
+  SN_REQUIRE(waves != 12 || (one && kcap <= 16 && P.head_pad == 0 && heads16 && P.d > 112),
+             "sn_rho_fused_form_f32: twelve-wave workgroups are built for the one-layer register-attention form at d in (112, 128] only");
+  SN_REQUIRE(waves != 8 || (kcap <= 16 && (P.head_pad > 0 || (heads16 && (P.d == 64 || P.d > 112)))),
+             "sn_rho_fused_form_f32: eight-wave workgroups are built for the register-attention forms of the common widths only");
   if (P.head_pad > 0 && kcap <= 16) {
     // head-padded packing: every head occupies head_pad (16 or 32) channels of the q/k/v/attention tensors, so the register
     // attention applies to any d; all weights / vectors are zero-padded to heads*head_pad channels by the caller
     SN_REQUIRE((P.head_pad == 16 || P.head_pad == 32) && P.head_pad >= P.d / P.heads,
                "sn_rho_fused_f32: head_pad must be 16 or 32 and >= d/heads (got %d for d=%d)", P.head_pad, P.d);
     if constexpr (PREC == PREC_HIGHEST) {
-      if (rho_eight_waves()) {
+      if (rho_waves(waves) == 8) {
         if (P.head_pad == 16) return one ? launch_rho<4, true, true, true, 8>(S, P, bound, st) : launch_rho<4, true, false, true, 8>(S, P, bound, st);
         return one ? launch_rho<8, true, true, true, 8>(S, P, bound, st) : launch_rho<8, true, false, true, 8>(S, P, bound, st);
       }
@@ -1015,8 +1058,8 @@ static int rho_launch(const RhoStruct& S, const sn_rho_params& P, const sn_plan_
     if (cols) return one ? launch_rho_wide<4, true, true, PREC>(S, P, bound, st) : launch_rho_wide<4, false, true, PREC>(S, P, bound, st);
     return one ? launch_rho_wide<4, true, false, PREC>(S, P, bound, st) : launch_rho_wide<4, false, false, PREC>(S, P, bound, st);
   }
-  return regattn ? (one ? dispatch_rho<true, true, PREC>(nt, S, P, bound, st) : dispatch_rho<true, false, PREC>(nt, S, P, bound, st))
-                 : (one ? dispatch_rho<false, true, PREC>(nt, S, P, bound, st) : dispatch_rho<false, false, PREC>(nt, S, P, bound, st));
+  return regattn ? (one ? dispatch_rho<true, true, PREC>(nt, S, P, bound, waves, st) : dispatch_rho<true, false, PREC>(nt, S, P, bound, waves, st))
+                 : (one ? dispatch_rho<false, true, PREC>(nt, S, P, bound, waves, st) : dispatch_rho<false, false, PREC>(nt, S, P, bound, waves, st));
 }
 
 // the reduced product sets' launches, one translation unit each (fused_rho_high.hip, fused_rho_medium.hip include this file with
@@ -1025,11 +1068,11 @@ int rho_launch_high(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bi
 int rho_launch_medium(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st);
 #if defined(SN_PREC_TU) && SN_PREC_TU == SN_PREC_HIGH
 int rho_launch_high(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st) {
-  return rho_launch<PREC_HIGH>(S, P, bins, kmax, K, bound, st);
+  return rho_launch<PREC_HIGH>(S, P, bins, kmax, K, bound, 0, st);
 }
 #elif defined(SN_PREC_TU) && SN_PREC_TU == SN_PREC_MEDIUM
 int rho_launch_medium(const RhoStruct& S, const sn_rho_params& P, const sn_plan_bins* bins, int kmax, int K, int64_t bound, hipStream_t st) {
-  return rho_launch<PREC_MEDIUM>(S, P, bins, kmax, K, bound, st);
+  return rho_launch<PREC_MEDIUM>(S, P, bins, kmax, K, bound, 0, st);
 }
 #endif
 
@@ -1042,9 +1085,9 @@ using namespace sn;
 extern "C" int sn_prof_read_rho(long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_prof), sizeof(long long) * 64); }
 #endif
 
-extern "C" int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
+extern "C" int sn_rho_fused_form_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
                                      const int32_t* graph_ptr, int64_t B, int64_t N, const sn_plan_bins* bins, int kmax,
-                                     int K, float* out_sum, int precision, void* stream) {
+                                     int K, float* out_sum, int precision, int waves, void* stream) {
   SN_REQUIRE(params && x && graph_ptr && bins && bins->rho_bin0 && bins->meta && out_sum, "sn_rho_fused_f32: null pointer");
   const sn_rho_params& P = *params;
   SN_REQUIRE(P.d > 0 && P.d <= 128 && (P.d & 3) == 0, "sn_rho_fused_f32: hidden width %d must be a multiple of 4 in (0, 128]", P.d);
@@ -1060,6 +1103,9 @@ extern "C" int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x
   SN_REQUIRE(K > 0 && B >= 0 && N >= 0 && B < (1ll << 31), "sn_rho_fused_f32: bad sizes");
   SN_REQUIRE(precision == SN_PREC_HIGHEST || precision == SN_PREC_HIGH || precision == SN_PREC_MEDIUM,
              "sn_rho_fused_prec_f32: unknown matmul precision %d (SN_PREC_HIGHEST, SN_PREC_HIGH, SN_PREC_MEDIUM)", precision);
+  SN_REQUIRE(waves == 0 || waves == 4 || waves == 8 || waves == 12, "sn_rho_fused_form_f32: waves must be 0 (the library's choice), 4, 8 or 12 (got %d)", waves);
+  SN_REQUIRE(waves == 0 || waves == 4 || precision == SN_PREC_HIGHEST,
+             "sn_rho_fused_form_f32: the reduced product sets are built on four-wave workgroups only (got waves = %d)", waves);
   if (B == 0 || N == 0) return SN_OK;
   SN_REQUIRE(N < (1ll << 31), "sn_rho_fused_f32: too many nodes");
   RhoStruct S{x, eigen_values, graph_ptr, bins->rho_bin0, bins->meta, (int)B, kmax, K, out_sum, bins->node_graph, (int)N,
@@ -1070,11 +1116,17 @@ extern "C" int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x
   switch (precision) {
     case SN_PREC_HIGH: rc = rho_launch_high(S, P, bins, kmax, K, bound, st); break;
     case SN_PREC_MEDIUM: rc = rho_launch_medium(S, P, bins, kmax, K, bound, st); break;
-    default: rc = rho_launch<PREC_HIGHEST>(S, P, bins, kmax, K, bound, st); break;
+    default: rc = rho_launch<PREC_HIGHEST>(S, P, bins, kmax, K, bound, waves, st); break;
   }
   if (rc != SN_OK) return rc;
   SN_CHECK_LAUNCH("sn_rho_fused_f32");
   return SN_OK;
+}
+
+extern "C" int sn_rho_fused_prec_f32(const sn_rho_params* params, const float* x, const float* eigen_values,
+                                     const int32_t* graph_ptr, int64_t B, int64_t N, const sn_plan_bins* bins, int kmax,
+                                     int K, float* out_sum, int precision, void* stream) {
+  return sn_rho_fused_form_f32(params, x, eigen_values, graph_ptr, B, N, bins, kmax, K, out_sum, precision, 0, stream);
 }
 
 extern "C" int sn_rho_fused_f32(const sn_rho_params* params, const float* x, const float* eigen_values,

@@ -201,9 +201,10 @@ class RhoPlan:
             Lp.ln2_g, Lp.ln2_b = hold(vpad(f.norm.ln.weight)), hold(vpad(f.norm.ln.bias))
         return P
 
-    def run(self, plan: ops.GraphPlan, x, eigen_values, K: int, precision=0, out=None):
+    def run(self, plan: ops.GraphPlan, x, eigen_values, K: int, precision=0, out=None, waves=0):
         """x [N*K, d] -> sum over valid slots of the encoder output, [N, d].  precision: SN_PREC_* of the six [d, d] projections
-        of every layer (PRECISIONS).  out: optional contiguous float32 [N, d] buffer to write (default: a fresh one)."""
+        of every layer (PRECISIONS).  out: optional contiguous float32 [N, d] buffer to write (default: a fresh one).  waves: 0 = the
+        library's choice of workgroup form; 4, 8 or 12 force that form (sn_rho_fused_form_f32: same bits, an error where not built)."""
         if out is None:
             out = torch.empty(plan.N, self.d, dtype=torch.float32, device=x.device)
         elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (plan.N, self.d) or out.device != x.device:
@@ -211,6 +212,12 @@ class RhoPlan:
         kcap = min(plan.kmax, K) if plan.kmax > 0 else K
         params = self.params_hp if (self.params_hp is not None and kcap <= 16) else self.params
         with ops._span("sn_rho_fused_f32"):
+            if waves:
+                check(lib().sn_rho_fused_form_f32(C.byref(params), ptr(x), ptr(eigen_values), ptr(plan.graph_ptr), plan.B,
+                                                  plan.N, C.byref(plan.bins.cstruct), plan.kmax, K, ptr(out), int(precision), int(waves),
+                                                  stream()),
+                      "sn_rho_fused_form_f32")
+                return out
             if precision:
                 check(lib().sn_rho_fused_prec_f32(C.byref(params), ptr(x), ptr(eigen_values), ptr(plan.graph_ptr), plan.B,
                                                   plan.N, C.byref(plan.bins.cstruct), plan.kmax, K, ptr(out), int(precision), stream()),

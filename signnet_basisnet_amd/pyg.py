@@ -1091,7 +1091,10 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
             ev_a.record(side_a)
         side_b.wait_event(ev_a)
         with torch.cuda.stream(side_b), _lib_mod.stream_scope():
-            s = P["rho_fused"].run(plan, x, data.eigen_values if want_vals else None, K, precision=self._prec)
+            # (four-wave workgroups: here rho shares the CUs with the neighbouring forwards' phi and GINE stages, and a twelve-wave
+            #  workgroup can only start on a CU whose whole register file is free — measured 1.7-2.5 % slower in this mode,
+            #  profiles/rho_twelve_waves.json; for every other net and batch 4 is what the library picks anyway)
+            s = P["rho_fused"].run(plan, x, data.eigen_values if want_vals else None, K, precision=self._prec, waves=4)
             ev_b = torch.cuda.Event()
             ev_b.record(side_b)
         cur.wait_event(ev_b)
