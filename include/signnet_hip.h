@@ -1331,6 +1331,27 @@ int sn_dropout_f32(const float* x, int ldx, int64_t R, int C, uint32_t threshold
                    int64_t base, const float* residual, int ldr, float* y, int ldy, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * BatchNorm apply and dropout in one launch (the post-BatchNorm dropout sites of the DGL tree's sign-invariant encoders):
+ *   y[r,c] = rowvalid(r) && keep(r,c) ? fma(x[r,c], scale[c], shift[c]) * pscale : 0                      x, y: [R, C]
+ * rowvalid is the (nvalid, K) row mask of sn_masked_affine_f32 (row r is slot r % K of node r / K, valid when the slot is below
+ * nvalid[node]; nvalid = NULL: every row; with nvalid, K > 0 and R < 2^31); keep is exactly the mask of sn_dropout_f32 at the same
+ * (threshold, state, site, base), i = base + r*C + c.  scale, shift: [C] each, or both NULL (then y = x * pscale where kept: dropout
+ * with a row mask).  The result equals sn_dropout_f32(sn_masked_affine_f32(x, SN_EPI_AFFINE)) bit for bit: the affine is one fused
+ * multiply-add there and here, and the product with pscale is rounded separately.  sn_dropout_f32 on dy (then the BatchNorm adjoint)
+ * is the backward.  x and y must not overlap.  One generator call per aligned group of four logical indices on each of three paths:
+ *   row-vector   C % 4 == 0, ldx % 4 == 0, ldy % 4 == 0, base % 4 == 0, x / y (and scale / shift) 16-byte aligned: 128-bit accesses
+ *                to x, y, scale and shift;
+ *   flat-vector  ldx == ldy == C (any C), base % 4 == 0, x / y 16-byte aligned: the tensor is one contiguous run moved in 128-bit
+ *                accesses, a group may straddle rows, validity and the column of scale / shift are taken per element;
+ *   scalar       anything else: any ld >= C, 4-byte-aligned pointers, any base >= 0.
+ * The mask and the values are the same on all three.  R = 0: SN_OK, no launch.  Columns C..ld of y are never written.  No LDS, no
+ * atomics. */
+#define SN_SIGNINV_DROP_SITE 0x53490000u     /* + ordinal of the F.dropout / nn.Dropout call within one forward of the encoder module */
+int sn_affine_dropout_f32(const float* x, int ldx, int64_t R, int C, const int32_t* nvalid, int K, const float* scale,
+                          const float* shift, uint32_t threshold, float pscale, const int64_t* state, uint32_t site, int64_t base,
+                          float* y, int ldy, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention dropout with a counter-based mask: sn_set_attention_f32 / sn_set_attention_bwd_f32 with the factor that multiplies
  * P[n, h, q, key] after the softmax (transformer_module.py:49,55) evaluated inside the kernels instead of read from prob_mask.
  * THE MASK CONTRACT (restated in numpy by tests/attention_dropout_cases.py):

@@ -160,6 +160,7 @@ SIGNATURES = {
     "sn_gcn_pyg_coef_f32": [_l, _l, _p, _p, _p, _p],
     "sn_gcn_pyg_propagate_f32": [_p, _l, _l, _i, _l, _p, _p, _p, _p, _l, _p],
     "sn_dropout_f32": [_p, _i, _l, _i, C.c_uint32, _f, _p, C.c_uint32, _l, _p, _i, _p, _i, _p],
+    "sn_affine_dropout_f32": [_p, _i, _l, _i, _p, _i, _p, _p, C.c_uint32, _f, _p, C.c_uint32, _l, _p, _i, _p],
     "sn_set_attention_drop_f32": [_p, _p, _p, _l, _i, _i, _i, _p, C.c_uint32, _f, _p, C.c_uint32, _p, _p],
     "sn_set_attention_drop_bwd_f32": [_p, _p, _p, _p, _l, _i, _i, _i, _p, C.c_uint32, _f, _p, C.c_uint32, _p, _p, _p, _p],
 }

@@ -1067,6 +1067,41 @@ class _Dropout(Function):
         return ops.dropout(g, p, snap, site), (g if has_res else None), None, None, None
 
 
+class _BnDrop(Function):
+    """dropout(BatchNorm1d_train(z)): the batch statistics as _BnAct, then the BatchNorm apply and the mask in ONE launch
+    (sn_affine_dropout_f32).  Saves what _BnAct saves plus the 16-byte snapshot; the backward regenerates the mask on dy
+    (sn_dropout_f32) and runs _BnAct's adjoint, which leaves invalid rows out — the two launches of the composition's backward."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, bn, p, snap, site, nvalid, K):
+        z = _c(z)
+        mean, _, rstd, scale, shift, count = ops.bn_train_stats(z, bn, nvalid, K)
+        y = ops.affine_dropout(z, scale, shift, p, snap, site, nvalid, K)
+        ctx.save_for_backward(z, mean, rstd, scale, shift, count, snap)
+        ctx.meta = (nvalid, K, p, site, gamma is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, mean, rstd, scale, shift, count, snap = ctx.saved_tensors
+        nvalid, K, p, site, affine = ctx.meta
+        Cc = z.shape[-1]
+        dz, sums = _bn_act_adjoint(z, ops.dropout(_c(dy), p, snap, site), mean, rstd, scale, shift, count, nvalid, K, False)
+        return dz, sums[Cc:] if affine else None, sums[:Cc] if affine else None, None, None, None, None, None, None
+
+
+def bn_drop(z, bn, p, snap, site, nvalid=None, K=0):
+    """dropout(BatchNorm1d(z) with batch statistics over the valid rows), the apply pass and the mask in one launch; updates bn's
+    running statistics.  p == 0 is bn_act(relu=False) itself; the result and the gradients equal `dropout(bn_act(z, bn, nvalid, K,
+    relu=False), p, snap, site)` bit for bit."""
+    p = float(p)
+    if p < 0.0 or p > 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    if p == 0.0:
+        return bn_act(z, bn, nvalid, K, relu=False)
+    return _BnDrop.apply(z, bn.weight, bn.bias, bn, p, snap, site, nvalid, K)
+
+
 def dropout(x, p, snap, site, residual=None):
     p = float(p)
     if p < 0.0 or p > 1.0:

@@ -135,12 +135,15 @@ def _prep_mlp(mlp: MLP, train=False):
     return out
 
 
-def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None):
+def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None, tail_drop=None, fuse_drop=False):
     """mlp.py:37-56: hidden layers = bias -> relu -> BN [-> dropout]; the final Linear optionally followed by the
     BatchNorm that GIN.forward applies before the NEXT GINConv (gnns.py:105-112; in eval folded into the GEMM epilogue).
     train: BatchNorm over ALL rows of the layer (the reference normalises [N, C, K] tensors, padded slots included).
-    drop = (p, snap, first site): the train-mode dropout behind hidden layer i (mlp.py:51) is site `first + i` of ops.dropout on the
-    [R, C] rows (GINNet only: the sign-invariant encoders' [N, C, K] tensors are laid out differently here and refuse dropout)."""
+    drop = (p, snap, first site): the train-mode dropout behind hidden layer i (mlp.py:51) is site `first + i` on the [R, C] rows —
+    rows node * K + slot with the channels contiguous, the reference's row-major [N, k, C], for the sign-invariant encoders.
+    fuse_drop (the encoders of dropout_signinv.py): where a BatchNorm precedes the site, its apply pass and the mask are ONE launch
+    (ops.affine_dropout) instead of masked_affine + dropout — the same bits.  tail_drop: the site of GIN.forward's inter-layer dropout
+    (gnns.py:105), applied to the final Linear's output in front of `tail_bn`."""
     for i, (pl, bn) in enumerate(prep):
         last = i == len(prep) - 1
         site = tail_bn if last else bn
@@ -149,10 +152,16 @@ def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None):
             x = ops.masked_linear(x, pl, nvalid, K, relu_pre=not last, scale=sc, shift=sh)
         else:
             x = ops.masked_linear(x, pl, nvalid, K, relu=not last)
+            dropped = drop is not None and not last and drop[0]
+            if last and tail_drop is not None and drop is not None and drop[0]:
+                x = ops.dropout(x, drop[0], drop[1], tail_drop)
             if site is not None:
                 sc, sh = site.affine(x, True)
+                if dropped and fuse_drop:
+                    x = ops.affine_dropout(x, sc, sh, drop[0], drop[1], drop[2] + i)
+                    continue
                 x = ops.masked_affine(x, scale=sc, shift=sh)
-            if drop is not None and not last and drop[0]:
+            if dropped:
                 x = ops.dropout(x, drop[0], drop[1], drop[2] + i)
     return x
 
@@ -163,6 +172,30 @@ def _no_dropout(dropout, who):
     if float(dropout) != 0.0:
         raise NotImplementedError(f"{who}: dropout={dropout} is not implemented by the HIP modules (the shipped configs use 0.0); "
                                   "pass dropout=0.0")
+
+
+class _EncoderDropout(ops.DropoutHolder):
+    """Train-mode dropout of a sign-invariant encoder.  Opt-in by class: with `_signinv_dropout` False — the classes
+    of this module — `dropout > 0` is refused as before; the subclasses of dropout_signinv.py set it True and are their own
+    DropoutHolder.  site = ops.SIGNINV_DROP_SITE + the ordinal of the F.dropout / nn.Dropout call within one forward of the
+    reference module — enc(g, x), then enc(g, -x), then rho — so the two encoder calls draw different masks and a train-mode
+    forward with p > 0 is not sign-invariant, there as here; eval draws nothing and stays invariant bit for bit."""
+
+    _signinv_dropout = False
+
+    def _init_dropout(self, dropout, who):
+        if not self._signinv_dropout:
+            _no_dropout(dropout, who)
+        self.p_drop = ops.check_dropout_p(dropout, f"{who}: dropout")
+
+    def _drop_begin(self, train, device):
+        """(p, {seed, step} snapshot) of this train-mode forward — the step advances once, here — or None when no site is active."""
+        p = getattr(self, "p_drop", 0.0)
+        return (p, self._dropout_begin(device)) if train and p > 0.0 else None
+
+    def _rho_site0(self):
+        """Ordinal of rho's first site: behind the sites of the two encoder calls."""
+        return ops.SIGNINV_DROP_SITE + 2 * self._enc_sites()
 
 
 def _pad_mat(W, dp):
@@ -376,8 +409,13 @@ def cached_plan(g, N, k=None):
     return plan
 
 
-class _DeepSignsBase(nn.Module):
+class _DeepSignsBase(_EncoderDropout, nn.Module):
     masked = False
+
+    def _enc_sites(self):
+        """Dropout sites of ONE enc call: a hidden site per GIN MLP (mlp.py:51) and one in front of every layer but the first
+        (gnns.py:105), in the order m0, d1, m1, d2, m2, ..."""
+        return 2 * len(self.enc.layers) - 1
 
     def __init__(self):
         super().__init__()
@@ -449,14 +487,18 @@ class _DeepSignsBase(nn.Module):
             return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, -self.k, bins=True)
         return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, self.k, counts=counts)
 
-    def _phi(self, P, plan, x, N, K, train=False):
-        """enc(g, x) + enc(g, -x): GIN.forward, gnns.py:102-114, twice."""
+    def _phi(self, P, plan, x, N, K, train=False, drop=None):
+        """enc(g, x) + enc(g, -x): GIN.forward, gnns.py:102-114, twice.  drop = (p, snap): the sites of _enc_sites per call."""
         outs = []
+        L = len(P["gin"])
         for sign in (0, 1):
             h = x
+            s0 = ops.SIGNINV_DROP_SITE + sign * self._enc_sites()
             for l, Lp in enumerate(P["gin"]):
                 a = ops.gin_aggregate(h.reshape(N, -1), plan, Lp["eps"], negate=(sign == 1 and l == 0))
-                h = _run_mlp(Lp["mlp"], a.view(N * K, -1), tail_bn=Lp["next_bn"], train=train)
+                d = None if drop is None else (drop[0], drop[1], s0 + 2 * l)
+                h = _run_mlp(Lp["mlp"], a.view(N * K, -1), tail_bn=Lp["next_bn"], train=train, drop=d,
+                             tail_drop=s0 + 2 * l + 1 if l < L - 1 else None, fuse_drop=True)
             outs.append(h)
         return outs
 
@@ -464,7 +506,8 @@ class _DeepSignsBase(nn.Module):
         """Differentiable train-mode forward: the same launches as the value path, recorded as
         torch.autograd.Function nodes whose backward are the hand-written adjoints of csrc/backward.hip, so that the
         gradient a DGL base network sends back into `p = sign_inv_net(g, pos_enc)` (train_ZINC_graph_regression.py:20-25)
-        reaches these parameters.  Dropout is not applied (the shipped configs use 0.0).
+        reaches these parameters.  With `p_drop` > 0 (dropout_signinv.py) every site of the reference draws its mask: a post-BatchNorm
+        site is ONE launch with the BatchNorm apply (AG.bn_drop), an inter-layer site AG.dropout in front of the BatchNorm.
 
         Under the switch `_bucket` (train_graph.DGLBucketedStep) `g` is a PADDED batch: the plan gives the padding graphs no slot
         (sn_batch_plan_padded), the ops over the N*K slot rows take the node-slot vector (K on valid nodes, 0 on padding nodes: every
@@ -480,14 +523,20 @@ class _DeepSignsBase(nn.Module):
         enc = self.enc
         sv, sk = (None, 0) if pad is None else (pad.node_slots, K)               # the N*K slot rows
         vN, _, _, k1 = _bucket_rows(self)                                        # the N rows of rho
+        drop = self._drop_begin(True, x.device)
 
-        def run_mlp(mlp, h, tail_bn=None, nv=None, kv=0):
+        def run_mlp(mlp, h, tail_bn=None, nv=None, kv=0, site0=0, tail_site=None):
             n = len(mlp.lins)
             for i, lin in enumerate(mlp.lins):
                 last = i == n - 1
                 h = AG.linear(h, lin.weight, lin.bias, nv, kv, relu=not last)     # mlp.py:40-46: bias -> relu -> BN
                 bn = tail_bn if last else (mlp.bns[i] if mlp.use_bn else None)
-                if bn is not None:
+                if drop is not None and last and tail_site is not None:
+                    h = AG.dropout(h, drop[0], drop[1], tail_site)                # gnns.py:105: in front of the next layer's BatchNorm
+                if drop is not None and not last:                                 # mlp.py:51
+                    h = AG.bn_drop(h, bn, drop[0], drop[1], site0 + i, nv, kv) if bn is not None else \
+                        AG.dropout(h, drop[0], drop[1], site0 + i)
+                elif bn is not None:
                     h = AG.bn_act(h, bn, nv, kv, relu=False)                       # statistics over ALL rows, as the reference
             return h
 
@@ -496,16 +545,19 @@ class _DeepSignsBase(nn.Module):
         x = x.contiguous().float()
         for sign in (0, 1):
             h = x
+            s0 = ops.SIGNINV_DROP_SITE + sign * self._enc_sites()
             for l, conv in enumerate(enc.layers):
                 a = AG.gin_aggregate(h.reshape(N, -1), conv.eps, plan, rplan, negate=(sign == 1 and l == 0))
-                h = run_mlp(conv.apply_func, a.view(N * K, -1), enc.bns[l] if (enc.use_bn and l < L - 1) else None, sv, sk)
+                h = run_mlp(conv.apply_func, a.view(N * K, -1), enc.bns[l] if (enc.use_bn and l < L - 1) else None, sv, sk,
+                            s0 + 2 * l, s0 + 2 * l + 1 if l < L - 1 else None)
             outs.append(h)
+        r0 = self._rho_site0()
         if self.masked:
             z = AG.masked_add(outs[0], outs[1], plan.nvalid, K)
-            y = run_mlp(self.rho, AG.slot_sum(z, N, K, plan.nvalid), nv=vN, kv=k1)
+            y = run_mlp(self.rho, AG.slot_sum(z, N, K, plan.nvalid), nv=vN, kv=k1, site0=r0)
         else:
             z = AG.masked_add(outs[0], outs[1], sv, sk)
-            y = run_mlp(self.rho, z.view(N, -1), nv=vN, kv=k1)
+            y = run_mlp(self.rho, z.view(N, -1), nv=vN, kv=k1, site0=r0)
         return y.view(N, K, 1)
 
     def _phi_eval_merged(self, P, plan, x, N, K):
@@ -548,12 +600,13 @@ class _DeepSignsBase(nn.Module):
         return y
 
     def forward(self, g, x):
-        train = self.training     # train: batch statistics + running-statistics update (dropout 0)
+        train = self.training     # train: batch statistics + running-statistics update, dropout where `p_drop` > 0
         ops.require_cuda(x)
         if x.dim() != 3 or x.shape[1] != self.k or x.shape[2] != 1:
             raise ValueError(f"expected x of shape [N, {self.k}, 1]")
         if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return self._forward_grad(g, x)
+        drop = self._drop_begin(train, x.device)
         if train:
             P = self._prepare(True)          # parameters may change between training-mode calls: nothing is cached
         else:
@@ -577,13 +630,14 @@ class _DeepSignsBase(nn.Module):
             if self.masked:
                 z = ops.masked_affine(z, plan.nvalid, K)                     # x[~mask] = 0       (deepsigns.py:76-80)
         else:
-            zp, zm = self._phi(P, plan, x.contiguous().float(), N, K, train)
+            zp, zm = self._phi(P, plan, x.contiguous().float(), N, K, train, drop)
             z = ops.masked_affine(zp, plan.nvalid, K, residual=zm) if self.masked else ops.masked_affine(zp, residual=zm)
+        rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
         if self.masked:
             # sum over K ; rho(c -> hidden -> K)                              (deepsigns.py:81-84)
-            y = _run_mlp(P["rho"], ops.slot_sum(z, N, K), train=train)
+            y = _run_mlp(P["rho"], ops.slot_sum(z, N, K), train=train, drop=rd, fuse_drop=True)
         else:
-            y = _run_mlp(P["rho"], z.view(N, -1), train=train)                 # deepsigns.py:47-49
+            y = _run_mlp(P["rho"], z.view(N, -1), train=train, drop=rd, fuse_drop=True)     # deepsigns.py:47-49
         return y.view(N, K, 1)
 
 
@@ -591,7 +645,7 @@ class GINDeepSigns(_DeepSignsBase):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, k, use_bn=False, use_ln=False, dropout=0.5,
                  activation="relu"):
         super().__init__()
-        _no_dropout(dropout, "GINDeepSigns")
+        self._init_dropout(dropout, "GINDeepSigns")
         self.enc = GIN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
         self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
         self.k = k
@@ -604,7 +658,7 @@ class MaskedGINDeepSigns(_DeepSignsBase):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, k, device=None, use_bn=False, use_ln=False,
                  dropout=0.5, activation="relu"):
         super().__init__()
-        _no_dropout(dropout, "MaskedGINDeepSigns")
+        self._init_dropout(dropout, "MaskedGINDeepSigns")
         self.device = device
         self.enc = GIN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
         self.rho = MLP(out_channels, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
@@ -704,7 +758,7 @@ class SetTransformerEncoder(nn.Module):
         self.layers = nn.ModuleList([_SetAttentionBlock(d_model, n_heads, d_head, d_ff) for _ in range(n_layers)])
 
 
-class _SignInvBase(nn.Module):
+class _SignInvBase(_EncoderDropout, nn.Module):
     """What the sign-invariant nets WITHOUT stage kernels share (nothing here looks into `enc`): the forward contract, the three forward
     paths (eval / train value / train under autograd), and the cache invalidation of _DeepSignsBase."""
 
@@ -759,19 +813,28 @@ class _SignInvBase(nn.Module):
         ei = torch.stack([src.long(), dst.long()])
         return ops.build_plan(batch, ei, B, 0), ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
 
-    def _rho_grad(self, z):
-        """rho under autograd (mlp.py:37-56, dropout 0): padded rows of a bucketed batch enter no statistic and no gradient."""
+    def _rho_grad(self, z, drop=None):
+        """rho under autograd (mlp.py:37-56): padded rows of a bucketed batch enter no statistic and no gradient.  drop = (p, snap):
+        hidden layer i is followed by site `_rho_site0() + i` — one launch with the BatchNorm apply where there is one."""
         from . import autograd as AG
         vN, _, _, k1 = _bucket_rows(self)
         mlp, n = self.rho, len(self.rho.lins)
+        r0 = self._rho_site0()
         for i, lin in enumerate(mlp.lins):
             z = AG.linear(z, lin.weight, lin.bias, vN, k1, relu=i < n - 1)
-            if mlp.use_bn and i < n - 1:
-                z = AG.bn_act(z, mlp.bns[i], vN, k1, relu=False)
+            bn = mlp.bns[i] if (mlp.use_bn and i < n - 1) else None
+            if drop is not None and i < n - 1:
+                z = AG.bn_drop(z, bn, drop[0], drop[1], r0 + i, vN, k1) if bn is not None else AG.dropout(z, drop[0], drop[1], r0 + i)
+            elif bn is not None:
+                z = AG.bn_act(z, bn, vN, k1, relu=False)
         return z
 
+    def _rho_value(self, P, z, train, drop):
+        rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
+        return _run_mlp(P["rho"], z, train=train, drop=rd, fuse_drop=True)
+
     def forward(self, g, x):
-        train = self.training     # train: batch statistics + running-statistics update (dropout 0)
+        train = self.training     # train: batch statistics + running-statistics update, dropout where `p_drop` > 0
         ops.require_cuda(x)
         if x.dim() != 3 or x.shape[1] != self.k or x.shape[2] != 1:
             raise ValueError(f"expected x of shape [N, {self.k}, 1]")
@@ -784,7 +847,7 @@ class _SignInvBase(nn.Module):
             if self._prep is None:
                 self._prep = self._prepare(False)
             P = self._prep
-        return self._forward_value(P, g, x, train)
+        return self._forward_value(P, g, x, train, self._drop_begin(train, x.device))
 
 
 _ZERO_IN_DEGREE = ("There are 0-in-degree nodes in the graph: GraphConv's normalised sum is undefined for them (DGL raises DGLError here "
@@ -801,12 +864,16 @@ class GCNDeepSigns(_SignInvBase):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, k, use_bn=False, use_ln=False, dropout=0.5,
                  activation="relu"):
         super().__init__()
-        _no_dropout(dropout, "GCNDeepSigns")
+        self._init_dropout(dropout, "GCNDeepSigns")
         if use_ln:
             raise ValueError("HIP path: only relu / no LayerNorm / no residual (what every shipped config uses)")
         self.enc = GCN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
         self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
         self.k = k
+
+    def _enc_sites(self):
+        """Dropout sites of ONE enc call: in front of every layer but the first (gnns.py:36)."""
+        return len(self.enc.layers) - 1
 
     def _prepare(self, train=False):
         enc, L = self.enc, len(self.enc.layers)
@@ -832,16 +899,21 @@ class GCNDeepSigns(_SignInvBase):
         elif bool(zero):
             raise ValueError(_ZERO_IN_DEGREE)
 
-    def _enc_value(self, P, plan, rplan, h, N, S, train):
-        """GCN.forward on [N, S, c] features held as rows node * S + slot (eval: folded BatchNorm in the GEMM epilogue)."""
-        for Lp in P["layers"]:
+    def _enc_value(self, P, plan, rplan, h, N, S, train, drop=None):
+        """GCN.forward on [N, S, c] features held as rows node * S + slot (eval: folded BatchNorm in the GEMM epilogue).
+        drop = (p, snap, first site) in train mode: layer l's output is dropped (site first + l, gnns.py:36) in front of the BatchNorm."""
+        n_layers = len(P["layers"])
+        for l, Lp in enumerate(P["layers"]):
             site = Lp["next_bn"]
+            dsite = drop[2] + l if (drop is not None and l < n_layers - 1) else None
             if Lp["first"]:
                 z = ops.masked_linear(h, Lp["pl"])
                 h = ops.gcn_propagate(z.view(N, -1), plan, rplan, Lp["bias"], Lp["width"]).view(N * S, -1)
                 if train:
                     if Lp["relu"]:
                         h = ops.masked_affine(h, relu=True)
+                    if dsite is not None:
+                        h = ops.dropout(h, drop[0], drop[1], dsite)
                     if site is not None:
                         sc, sh = site.affine(h, True)
                         h = ops.masked_affine(h, scale=sc, shift=sh)
@@ -855,12 +927,14 @@ class GCNDeepSigns(_SignInvBase):
                 h = ops.masked_linear(a, Lp["pl"], relu_pre=Lp["relu"], scale=sc, shift=sh)
             else:
                 h = ops.masked_linear(a, Lp["pl"], relu=Lp["relu"])
+                if dsite is not None:
+                    h = ops.dropout(h, drop[0], drop[1], dsite)
                 if site is not None:
                     sc, sh = site.affine(h, True)
                     h = ops.masked_affine(h, scale=sc, shift=sh)
         return h
 
-    def _forward_value(self, P, g, x, train):
+    def _forward_value(self, P, g, x, train, drop=None):
         N, K = x.shape[0], self.k
         plan = cached_plan(g, N)
         rplan = _cached_rplan(g, N)
@@ -873,10 +947,11 @@ class GCNDeepSigns(_SignInvBase):
             z = ops.slot_sum(h.view(N * 2, -1), N, 2)                                  # sum over the sign axis -> [N, K * out]
         else:
             # enc(g, x) then enc(g, -x): each call normalises with its own batch statistics and moves the running statistics
-            zp = self._enc_value(P, plan, rplan, x2, N, K, True)
-            zm = self._enc_value(P, plan, rplan, self._neg(x2), N, K, True)
+            S0, ns = ops.SIGNINV_DROP_SITE, self._enc_sites()
+            zp = self._enc_value(P, plan, rplan, x2, N, K, True, None if drop is None else (drop[0], drop[1], S0))
+            zm = self._enc_value(P, plan, rplan, self._neg(x2), N, K, True, None if drop is None else (drop[0], drop[1], S0 + ns))
             z = ops.masked_affine(zp, residual=zm).view(N, -1)
-        return _run_mlp(P["rho"], z, train=train).view(N, K, 1)                        # deepsigns.py:27-30
+        return self._rho_value(P, z, train, drop).view(N, K, 1)                        # deepsigns.py:27-30
 
     def _forward_grad(self, g, x):
         """Differentiable train-mode forward: the launches of the value path as autograd nodes (the propagation's adjoint is the same
@@ -890,9 +965,11 @@ class GCNDeepSigns(_SignInvBase):
         enc, L = self.enc, len(self.enc.layers)
         sv, sk = (None, 0) if pad is None else (pad.node_slots, K)
         x2 = x.view(N * K, 1)
+        drop = self._drop_begin(True, x.device)
         outs = []
         for sign in (0, 1):
             h = x2 if sign == 0 else self._neg(x2)
+            s0 = ops.SIGNINV_DROP_SITE + sign * self._enc_sites()
             for l, conv in enumerate(enc.layers):
                 d_in, d_out = conv.weight.shape
                 bn = enc.bns[l] if (enc.use_bn and l < L - 1) else None
@@ -906,11 +983,13 @@ class GCNDeepSigns(_SignInvBase):
                 else:
                     a = AG.gcn_propagate(h.view(N, -1), plan, rplan).view(N * K, -1)
                     h = AG.linear(a, Wt, conv.bias, sv, sk, relu=conv.relu)
+                if drop is not None and l < L - 1:
+                    h = AG.dropout(h, drop[0], drop[1], s0 + l)                    # gnns.py:36, in front of the BatchNorm
                 if bn is not None:
                     h = AG.bn_act(h, bn, sv, sk, relu=False)
             outs.append(h)
         z = AG.masked_add(outs[0], outs[1], sv, sk)
-        return self._rho_grad(z.view(N, -1)).view(N, K, 1)
+        return self._rho_grad(z.view(N, -1), drop).view(N, K, 1)
 
 
 class TransformerDeepSigns(_SignInvBase):
@@ -924,7 +1003,7 @@ class TransformerDeepSigns(_SignInvBase):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, k, use_bn=False, use_ln=False, dropout=0.5,
                  activation="relu"):
         super().__init__()
-        _no_dropout(dropout, "TransformerDeepSigns")
+        self._init_dropout(dropout, "TransformerDeepSigns")
         if use_ln:
             raise ValueError("HIP path: only relu / no LayerNorm / no residual (what every shipped config uses)")
         heads = 2
@@ -935,6 +1014,10 @@ class TransformerDeepSigns(_SignInvBase):
         self.embed = nn.Linear(1, hidden_channels)
         self.rho = MLP(hidden_channels * k, hidden_channels, k, 4, use_bn=use_bn, dropout=dropout, activation=activation)
         self.k = k
+
+    def _enc_sites(self):
+        """None: the reference builds SetTransformerEncoder with dropouth = dropouta = 0, and a call with p = 0 takes no ordinal."""
+        return 0
 
     def _prepare(self, train=False):
         layers = []
@@ -947,7 +1030,7 @@ class TransformerDeepSigns(_SignInvBase):
                                ln2=(m.norm_inter.weight.detach(), m.norm_inter.bias.detach(), m.norm_inter.eps)))
         return dict(embed=_pack(self.embed), layers=layers, rho=_prep_mlp(self.rho, train))
 
-    def _forward_value(self, P, g, x, train):
+    def _forward_value(self, P, g, x, train, drop=None):
         """Eval and the train-mode value: the encoder has no BatchNorm, so both signs ride in the slot axis in either mode (rho's
         BatchNorms see the batch once per forward, as in the reference)."""
         N, K = x.shape[0], self.k
@@ -963,7 +1046,7 @@ class TransformerDeepSigns(_SignInvBase):
             f = ops.masked_linear(ops.masked_linear(h, Lp["f0"], relu=True), Lp["f3"])
             h = ops.masked_layernorm(f, h, *Lp["ln2"])
         z = ops.slot_sum(h.view(N * 2, -1), N, 2)                                      # sum over the sign axis -> [N, K * hidden]
-        return _run_mlp(P["rho"], z, train=train).view(N, K, 1)                        # deepsigns.py:116-118
+        return self._rho_value(P, z, train, drop).view(N, K, 1)                        # deepsigns.py:116-118
 
     def _forward_grad(self, g, x):
         """Differentiable train-mode forward: one attention launch per block forward, one backward.  Under `_bucket` the padding nodes
@@ -987,7 +1070,7 @@ class TransformerDeepSigns(_SignInvBase):
             f = AG.linear(AG.linear(h, m.ffn[0].weight, m.ffn[0].bias, sv, sk, relu=True), m.ffn[3].weight, m.ffn[3].bias, sv, sk)
             h = AG.masked_layernorm(f, h, m.norm_inter.weight, m.norm_inter.bias, m.norm_inter.eps, sv, sk)
         z = AG.slot_sum(h.view(N * 2, -1), N, 2)
-        return self._rho_grad(z).view(N, K, 1)
+        return self._rho_grad(z, self._drop_begin(True, x.device)).view(N, K, 1)
 
 
 def get_sign_inv_net(net_params):

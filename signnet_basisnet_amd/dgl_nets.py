@@ -143,6 +143,7 @@ class _DGLNet(ops.DropoutHolder, _PackCache, nn.Module):
     `_init_tail`; its forward is `_prologue`, then `_encode` / its layer loop / `_readout` (or their `_grad` forms)."""
 
     _feature_dropout = False # dropout / in_feat_dropout > 0 are refused, as before; dropout_models.py's subclasses set True
+    _sign_inv_factory = staticmethod(get_sign_inv_net)     # builds `sign_inv_net`; dropout_signinv.py's subclasses hand in their own
     _stage_cls = None        # the packer of the net's one-launch eval kernel (_FusedGin, _FusedGated, _FusedTransformer), if it has one
     _stage_edges = 192       # the most in-edges of a graph that kernel holds; None: the packer's own `max_edges`
     _malformed_note = ""     # check_last()'s wording of a malformed batch and of the size limit
@@ -185,7 +186,7 @@ class _DGLNet(ops.DropoutHolder, _PackCache, nn.Module):
         self.MLP_layer = MLPReadout(net_params["out_dim"], 1)
         self.g = None
         if self.lap_method == "sign_inv":
-            self.sign_inv_net = get_sign_inv_net(net_params)
+            self.sign_inv_net = self._sign_inv_factory(net_params)
         if getattr(self, "pe_aggregate", "add") == "concat":
             self.pe_proj = nn.Linear(2 * net_params["hidden_dim"], net_params["hidden_dim"])
 

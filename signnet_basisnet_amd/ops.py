@@ -1916,6 +1916,40 @@ def dropout(x, p, snap, site, residual=None, base=0):
     return out
 
 
+SIGNINV_DROP_SITE = 0x53490000   # + ordinal of the dropout call within one forward of a sign-invariant encoder (signnet_hip.h)
+
+
+def affine_dropout(x, scale, shift, p, snap, site, nvalid=None, K=0, base=0):
+    """BatchNorm apply and train-mode dropout of the row matrix x [..., C] in ONE launch (sn_affine_dropout_f32):
+    y = rowvalid && keep ? fma(x, scale, shift) / (1 - p) : 0 — bit for bit `dropout(masked_affine(x, nvalid, K, scale=, shift=), p,
+    snap, site)`.  scale = shift = None: dropout with a row mask.  p == 0: masked_affine itself, no new launch; p == 1: zeros."""
+    p = float(p)
+    if p < 0.0 or p > 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    if (scale is None) != (shift is None):
+        raise ValueError("affine_dropout: scale and shift go together")
+    if p == 0.0:
+        return masked_affine(x, nvalid, K, scale=scale, shift=shift)
+    require_cuda(x)
+    if p == 1.0:
+        return torch.zeros_like(x, dtype=torch.float32)
+    require_cuda(snap)
+    if snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous():
+        raise ValueError("affine_dropout: snap must be the int64 [2] {seed, step} tensor of a DropoutState")
+    x = _f32c(x, "x")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    Cc = x.shape[-1]
+    if scale is not None and (scale.numel() != Cc or shift.numel() != Cc):
+        raise ValueError(f"affine_dropout: scale / shift must have {Cc} elements")
+    thr, ps = dropout_threshold(p)
+    with _span("sn_affine_dropout_f32"):
+        check(lib().sn_affine_dropout_f32(ptr(x), Cc, x.numel() // Cc, Cc, ptr(nvalid), int(K), ptr(scale), ptr(shift), thr, ps, ptr(snap),
+                                          int(site), int(base), ptr(out), Cc, stream()), "sn_affine_dropout_f32")
+    return out
+
+
 class DropoutHolder:
     """Mixin of the models with feature dropout: a lazily created DropoutState kept OUT of the module's buffers (plain attribute: no
     state_dict key, not in model.buffers()).  A train-mode forward calls `_dropout_begin` once at its start: the step advances, and

@@ -133,7 +133,7 @@ def _capture(step, fwd_bwd, dev, warmup, check=None):
     """Warm up `fwd_bwd` on a side stream (lazy one-time setup: LDS limits, allocator pools) and capture it, under `step._scoped()`,
     without touching the model's state: buffers (running statistics, counters), the generator and the step word of the model's feature
     dropout (ops.DropoutHolder: its advance and snapshot are recorded inside `fwd_bwd`, so every replay draws the next step's masks) are
-    restored afterwards.
+    restored afterwards — the step word of the `sign_inv_net`'s own state included.
     `check`: what raises for a bad batch after the warm-up (default: the model's check_train()).
     -> (graph, loss, y, the captured forward's status words)."""
     model = step.model
@@ -142,8 +142,10 @@ def _capture(step, fwd_bwd, dev, warmup, check=None):
     side.wait_stream(torch.cuda.current_stream())
     rng = torch.cuda.get_rng_state(dev) if step._masks is not None else None
     # (the state exists before the capture: its creation copies from the host)
-    drop = model.dropout_state(dev) if getattr(model, "_dropout_active", lambda: False)() else None
-    drop_saved = None if drop is None else drop.t.clone()
+    # (likewise the state of a sign-invariant encoder with dropout of its own: dropout_signinv.py)
+    holders = [m for m in (model, getattr(model, "sign_inv_net", None)) if getattr(m, "_dropout_active", lambda: False)()]
+    drops = [m.dropout_state(dev) for m in holders]
+    drops_saved = [d.t.clone() for d in drops]
     with step._scoped():
         with torch.cuda.stream(side):
             for _ in range(warmup):
@@ -152,7 +154,13 @@ def _capture(step, fwd_bwd, dev, warmup, check=None):
         torch.cuda.current_stream().wait_stream(side)
         (check or model.check_train)()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        # With a process group up, its watchdog THREAD polls the events of earlier collectives (WorkNCCL::isCompleted) whenever it wakes.
+        # A capture in the default "global" error mode forbids an event query from every thread of the process: a poll that lands inside
+        # the capture invalidates it and the watchdog's exception ends the process.  "thread_local" holds this thread to the same rules
+        # and leaves the other thread alone; without a process group the mode stays as it was.
+        import torch.distributed as D
+        mode = "thread_local" if (D.is_available() and D.is_initialized()) else "global"
+        with torch.cuda.graph(graph, capture_error_mode=mode):
             loss, y = fwd_bwd()
         # the captured forward's status words (static memory of the graph): every replay rewrites them, check() reads them
         status, model._train_status = getattr(model, "_train_status", None), None
@@ -161,8 +169,8 @@ def _capture(step, fwd_bwd, dev, warmup, check=None):
             b.copy_(sv)
     if rng is not None:
         torch.cuda.set_rng_state(rng, dev)      # the warm-up's draws do not count: the first step draws what an eager one would
-    if drop is not None:
-        drop.t.copy_(drop_saved)                # nor do its dropout steps
+    for d, sv in zip(drops, drops_saved):
+        d.t.copy_(sv)                           # nor do its dropout steps
     return graph, loss.detach(), y.detach(), status
 
 
