@@ -1377,6 +1377,52 @@ int sn_set_attention_drop_bwd_f32(const float* q, const float* k, const float* v
                                   int dk, const int32_t* nvalid, uint32_t threshold, float scale, const int64_t* state, uint32_t site,
                                   float* dq, float* dk_out, float* dv, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Full-graph attention of the graph Transformer (GraphPrediction/layers/transformer.py:155-228 with full_graph True; the dataset step
+ * data/molecules.py:211-235 make_full_graph).  For an in-edge e = (j -> i) with code[e] = 2 * class + real and a head h of width dk:
+ *     t   = sum_c ((A[j,h,c] * B[i,h,c]) / sqrt(dk)) * T[class,h,c]     real: A, B, T = K, Q, T_real;  fake: K_2, Q_2, T_fake
+ *     L   = clamp(gamma[0], 0, 1)
+ *     s   = exp(clamp(t, -5, 5)) / (L + 1)  (real),   (L * exp(clamp(t, -5, 5))) / (L + 1)  (fake)
+ *     out[i,h,:] = sum_e s * V[j,h,:] / (sum_e s + 1e-6)      in-edges in edge-id order; a node without in-edges gets exactly 0
+ * T_real = E(embedding_e.weight), T_fake = E_2(embedding_e.weight): [C, heads*dk] class tables (E, E_2 have no bias, so the projection
+ * of an edge's embedding is a table row); nothing of size [E, heads*dk] is read, written or kept, forward or backward.  codes: int32 [E]
+ * in edge-id order; rowptr / col / eperm: the destination-sorted CSR of sn_batch_plan over whatever edge list the plan was built
+ * from — completeness is not assumed; any pattern of real, any class on a fake edge, directed pairs and multi-edges follow the
+ * formula.  Q, K, V, Q2, K2: [N, heads*dk] blocks with the common row stride ld (floats): separate matrices or the column blocks of
+ * one projection.  gamma: DEVICE float[1], read when the kernel runs.  den [N, heads]: sum_e s, kept for the backward.
+ * A class outside [0, C) is never dereferenced: the edge contributes nothing and bit 0 of *status (may be NULL) is raised.
+ * dk <= 32 and C <= 16, else SN_ERR_ARG; any in-degree, any N.  One thread per (node, head); no atomics in any sum.
+ *
+ * sn_full_attention_bwd_f32: with g = dout[i,h,:], Z = den + 1e-6:  ds_e = (g . V_j - g . out_i) / Z,  dV_j += s_e g / Z,
+ *   dt_e = ds_e s_e where |t_e| < 5 else 0 (the clamp convention of sn_edge_attention_bwd_f32),
+ *   dL = sum_e ds_e exp(clamp t_e) (-/+ 1 / (L + 1)^2)  (- real, + fake),  dgamma = dL if 0 <= gamma <= 1 else 0.
+ *   Writes dQ, dK, dV, dQ2, dK2 [N, heads*dk] (contiguous), dT_real, dT_fake [C, heads*dk], dgamma [1].  Destination pass, source pass
+ *   over rev_* (the CSR of the flipped edge list), a table pass whose workgroups add into private LDS cells and write partial tables,
+ *   and one finish launch that adds the partials in workgroup order: one owner per output element, bit-identical on repeated calls.
+ *   scratch: sn_full_attention_bwd_scratch_floats(N, E, heads, dk, C) floats, 8-byte aligned (per-(edge, head) scalars and the
+ *   partials — [E, heads] and [workgroups, 2C, heads*dk]).
+ *
+ * sn_make_full_graph: the complete directed graph of every graph of a batch in one launch (a workgroup per graph).  Per graph the
+ *   pairs are numbered u-major, v ascending, v != u (networkx.complete_graph(n).to_directed().edges()); src / dst / real / e_full:
+ *   int64 [E_full], E_full = sum_b n_b (n_b - 1) from the caller's host-side node counts.  real = 1 and the sparse edge's class e[.]
+ *   where the sparse graph (rowptr / col / eperm of its plan, e int64 [E] in edge-id order) has the edge u -> v, else real = 0, class 0.
+ *   *status: bit 0 a self loop, bit 1 a repeated (u, v) — the reference's assignment gives neither a meaning —, bit 2 E_full does
+ *   not fit the node counts (nothing is written past it). */
+int sn_full_attention_f32(const float* Q, const float* K, const float* V, const float* Q2, const float* K2, int64_t ld,
+                          const float* T_real, const float* T_fake, int C, const int32_t* codes, const float* gamma, int64_t N, int heads,
+                          int dk, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, float* out, float* den, int32_t* status,
+                          void* stream);
+int64_t sn_full_attention_bwd_scratch_floats(int64_t N, int64_t E, int heads, int dk, int C);
+int sn_full_attention_bwd_f32(const float* Q, const float* K, const float* V, const float* Q2, const float* K2, int64_t ld,
+                              const float* T_real, const float* T_fake, int C, const int32_t* codes, const float* gamma, const float* out,
+                              const float* den, const float* dout, int64_t N, int64_t E, int heads, int dk, const int32_t* rowptr,
+                              const int32_t* col, const int32_t* eperm, const int32_t* rev_rowptr, const int32_t* rev_col,
+                              const int32_t* rev_eperm, float* dQ, float* dK, float* dV, float* dQ2, float* dK2, float* dT_real,
+                              float* dT_fake, float* dgamma, float* scratch, void* stream);
+int sn_make_full_graph(const int32_t* graph_ptr, int64_t B, int64_t N, const int32_t* rowptr, const int32_t* col, const int32_t* eperm,
+                       const int64_t* e, int64_t E, int64_t E_full, int64_t* src, int64_t* dst, int64_t* real, int64_t* e_full,
+                       int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -603,6 +603,34 @@ def edge_attention(Q, K, V, Ee, plan, rplan, heads):
     return _EdgeAttention.apply(Q, K, V, Ee, plan, rplan, heads)
 
 
+class _FullAttention(Function):
+    """ops.full_attention as an autograd node.  Saved: the five node blocks, the two [C, d] class tables, gamma, out and the [N, heads]
+    denominators — nothing with a row per edge but the int32 codes."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, Q2, K2, T_real, T_fake, gamma, codes, plan, rplan, heads, status):
+        Q, K, V, Q2, K2 = _c(Q), _c(K), _c(V), _c(Q2), _c(K2)
+        T_real, T_fake = _c(T_real), _c(T_fake)
+        out, den = ops.full_attention(Q, K, V, Q2, K2, T_real, T_fake, codes, gamma.detach(), plan, heads, status=status, want_den=True)
+        ctx.save_for_backward(Q, K, V, Q2, K2, T_real, T_fake, gamma, out, den)
+        ctx.meta = (codes, plan, rplan, heads)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, K, V, Q2, K2, T_real, T_fake, gamma, out, den = ctx.saved_tensors
+        codes, plan, rp, heads = ctx.meta
+        grads = ops.full_attention_bwd(Q, K, V, Q2, K2, T_real, T_fake, codes, gamma.detach(), out, den, _c(g), plan, rp, heads)
+        dgamma = grads[7].reshape(gamma.shape)
+        return grads[:7] + (dgamma, None, None, None, None, None)
+
+
+def full_attention(Q, K, V, Q2, K2, T_real, T_fake, gamma, codes, plan, rplan, heads, status=None):
+    """Differentiable ops.full_attention: gradients reach Q, K, V, Q_2, K_2, the class tables T_real / T_fake (and through the GEMM that
+    made them E.weight, E_2.weight and embedding_e.weight) and gamma."""
+    return _FullAttention.apply(Q, K, V, Q2, K2, T_real, T_fake, gamma, codes, plan, rplan, heads, status)
+
+
 class _GatAggregate(Function):
     """dgl GATConv after its fc (gat_net.py:62-66): edge softmax of leaky_relu(el[src] + er[dst]) + weighted sum + bias + ReLU."""
 

@@ -299,9 +299,22 @@ class DGLGraphStore(_Store):
             raise ValueError("DGLGraphStore: one float32 score per graph")
         self._init_tables(dev)
 
+    @staticmethod
+    def _refuse_full_graph(g):
+        ed = getattr(g, "edata", None)
+        try:
+            flagged = ed is not None and "real" in ed
+        except TypeError:
+            flagged = False
+        if flagged:
+            raise NotImplementedError("DGLGraphStore does not carry the edge flag edata['real'] of a full graph (TransformerNet with "
+                                      "full_graph=True) through its gather: collate such batches with ops.make_full_graph")
+
     @classmethod
     def from_samples(cls, samples, device):
         """`samples`: per-graph tuples (g, h, p, e or None, snorm_n or None, target) — g's edges carry local node ids."""
+        for s in samples:
+            cls._refuse_full_graph(s[0])
         _device(device)
         sizes = GraphSizes.from_samples(samples, dgl=True)
         flat = lambda i: None if samples[0][i] is None else torch.cat([torch.as_tensor(s[i]).reshape(-1) for s in samples])
@@ -313,8 +326,9 @@ class DGLGraphStore(_Store):
     def from_batch(cls, batch, y, device):
         """`batch`: (g, h, p, e or None, snorm_n or None) of a collated DGL batch (only g.edges() and g.batch_num_nodes() — and
         batch_num_edges() where g has it — are read); y: the targets [G, 1]."""
-        _device(device)
         g, h, p, e, snorm_n = batch[:5]
+        cls._refuse_full_graph(g)
+        _device(device)
         sizes = GraphSizes.from_batch(batch, dgl=True)
         src, dst = (t.reshape(-1).long() for t in g.edges())
         first = torch.from_numpy(np.repeat(sizes.node_ptr[:-1], sizes.n_edges)).to(src.device)

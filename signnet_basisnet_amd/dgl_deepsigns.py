@@ -33,6 +33,16 @@ class Graph:
         self.src, self.dst = src, dst
         self._bnn = torch.as_tensor(batch_num_nodes)
         self._bne = None if batch_num_edges is None else torch.as_tensor(batch_num_edges)    # per-graph edge counts, as DGL keeps them
+        self._edata, self._ndata = {}, {}
+
+    @property
+    def edata(self):
+        """Per-edge tensors by name, as DGL's g.edata (a full graph's 'real' flags: ops.make_full_graph)."""
+        return self._edata
+
+    @property
+    def ndata(self):
+        return self._ndata
 
     def edges(self):
         return self.src, self.dst
@@ -44,7 +54,10 @@ class Graph:
         return self._bne
 
     def to(self, device):
-        return Graph(self.src.to(device), self.dst.to(device), self._bnn.to(device), None if self._bne is None else self._bne.to(device))
+        g = Graph(self.src.to(device), self.dst.to(device), self._bnn.to(device), None if self._bne is None else self._bne.to(device))
+        g._edata.update({k: v.to(device) for k, v in self._edata.items()})
+        g._ndata.update({k: v.to(device) for k, v in self._ndata.items()})
+        return g
 
 
 class MLP(nn.Module):

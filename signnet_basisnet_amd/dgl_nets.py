@@ -981,12 +981,17 @@ class PNANet(_DGLNet):
 # ---------------------------------------------------------------------------------------------------------------
 # Sparse graph Transformer: layers/transformer.py:112-317, nets/ZINC_graph_regression/transformer_net.py:21-150
 class MultiHeadAttentionLayer(nn.Module):
-    def __init__(self, gamma, in_dim, out_dim, num_heads):
+    def __init__(self, gamma, in_dim, out_dim, num_heads, full_graph=False):
         super().__init__()
         self.out_dim, self.num_heads, self.gamma = out_dim, num_heads, gamma        # gamma: the owner's Parameter, registered here too
+        self.full_graph = full_graph
         self.Q = nn.Linear(in_dim, out_dim * num_heads, bias=False)
         self.K = nn.Linear(in_dim, out_dim * num_heads, bias=False)
         self.E = nn.Linear(in_dim, out_dim * num_heads, bias=False)
+        if full_graph:                                                              # (transformer.py:147-150: the fake pairs' own projections)
+            self.Q_2 = nn.Linear(in_dim, out_dim * num_heads, bias=False)
+            self.K_2 = nn.Linear(in_dim, out_dim * num_heads, bias=False)
+            self.E_2 = nn.Linear(in_dim, out_dim * num_heads, bias=False)
         self.V = nn.Linear(in_dim, out_dim * num_heads, bias=False)
 
 
@@ -999,13 +1004,14 @@ class BatchedTransformerLayer(nn.Module):
     def __init__(self, in_dim, out_dim, num_heads, full_graph, dropout=0.0, use_edge=True):
         super().__init__()
         self.dropout = ops.check_dropout_p(dropout, "HIP BatchedTransformerLayer")
-        if full_graph or not use_edge:
+        if not use_edge:
             raise NotImplementedError("HIP graph Transformer: full_graph False with edge features (the shipped sign_inv configs)")
         if out_dim % num_heads or out_dim // num_heads > 32:
             raise ValueError("num_heads must divide out_dim and the head width must be <= 32")
         self.in_channels, self.out_channels, self.num_heads = in_dim, out_dim, num_heads
+        self.full_graph = bool(full_graph)
         self.gamma = nn.Parameter(torch.FloatTensor([0.1]))          # unused when full_graph is False, but part of the state_dict
-        self.attention_h = MultiHeadAttentionLayer(self.gamma, in_dim, out_dim // num_heads, num_heads)
+        self.attention_h = MultiHeadAttentionLayer(self.gamma, in_dim, out_dim // num_heads, num_heads, self.full_graph)
         self.O_h = nn.Linear(out_dim, out_dim)
         self.batch_norm1_h = nn.BatchNorm1d(out_dim)
         self.FFN_h_layer1 = nn.Linear(out_dim, out_dim * 2)
@@ -1094,9 +1100,12 @@ class TransformerNet(_DGLNet):
     (Transformer_ZINC_LapPE_signinv_GIN[_masked].json): embedding_h / embedding_p with `add` or `concat` + pe_proj, edge
     embedding, L x [Q/K/V/E projections -> sn_edge_attention_f32 -> O_h + residual -> BatchNorm -> FFN + residual -> BatchNorm],
     sum / mean readout, MLPReadout.  Same constructor, forward contract, state_dict keys and attached `sign_inv_net`.
-    Eval, train-mode value and — with gradients enabled — the differentiable path (`_forward_grad`)."""
+    Eval, train-mode value and — with gradients enabled — the differentiable path (`_forward_grad`).
+    full_graph True (`--full_graph`): `g` is the complete graph of every molecule with g.edata['real'] (ops.make_full_graph); bonds go
+    through Q / K / E, all other pairs through Q_2 / K_2 / E_2, mixed by each layer's gamma — `_forward_full`, one sn_full_attention_f32
+    launch per layer on the layer path (no one-launch stage kernel)."""
 
-    fused_layers = True      # eval: fused projections / epilogues (False: one launch per op, as the train-mode value path)
+    fused_layers = True     # eval: fused projections / epilogues (False: one launch per op, as the train-mode value path)
     fused_stages = True      # eval, the shipped shape: everything behind the E projection in ONE launch (sn_transformer_net_fused_f32)
     _stage_cls = _FusedTransformer
 
@@ -1110,9 +1119,12 @@ class TransformerNet(_DGLNet):
         self.layers = nn.ModuleList([BatchedTransformerLayer(hidden, hidden, p["n_heads"], p["full_graph"], use_edge=True)
                                      for _ in range(self.n_layers - 1)] +
                                     [BatchedTransformerLayer(hidden, out_dim, p["n_heads"], p["full_graph"], use_edge=True)])
+        self.full_graph = bool(p["full_graph"])
         self._init_tail(p)
 
     def _stage(self, g):
+        if self.full_graph:                  # full-graph nets take the layer path: the one-launch stage kernel has no fake-pair form
+            return None
         return super()._stage(g) if self._fusable() else None          # (the kernel reads the stacked E projections of `_fused_eval`)
 
     def _fusable(self):
@@ -1140,6 +1152,8 @@ class TransformerNet(_DGLNet):
         return ops.pointwise(s, scale=sc, shift=sh)
 
     def forward(self, g, h, p, e, snorm_n=None):
+        if self.full_graph:
+            return self._forward_full(g, h, p, e)
         pe, N, hidx, p, train, grad = self._prologue(g, h, p)
         eidx = e.long().reshape(-1)
         if grad:
@@ -1210,6 +1224,108 @@ class TransformerNet(_DGLNet):
             Q, K, V = (AG.linear(x, getattr(A, n).weight, None, vN, k1) for n in "QKV")
             Ee = AG.linear(ef, A.E.weight, None, vE, k1)
             a = AG.edge_attention(Q, K, V, Ee, plan, rplan, L.num_heads)
+            pd = L.dropout
+            if pd:
+                a = AG.dropout(a, pd, snap, 1 + 2 * li)
+            o = AG.linear(a, L.O_h.weight, L.O_h.bias, vN, k1)
+            x1 = AG.bn_act(AG.masked_add(o, x, vN, k1), L.batch_norm1_h, vN, k1, relu=False)
+            f = AG.linear(x1, L.FFN_h_layer1.weight, L.FFN_h_layer1.bias, vN, k1, relu=True)
+            if pd:
+                f = AG.dropout(f, pd, snap, 2 + 2 * li)
+            f = AG.linear(f, L.FFN_h_layer2.weight, L.FFN_h_layer2.bias, vN, k1)
+            x = AG.bn_act(AG.masked_add(f, x1, vN, k1), L.batch_norm2_h, vN, k1, relu=False)
+        self._h_last = x.detach()
+        return self._readout_grad(x, plan, vB, k1)
+
+    # ------------------------------------------------------------------ full_graph True: every node attends to its whole molecule
+    def _full_eval(self):
+        """Eval cache of a full-graph net: cat[W_Q; W_K; W_V; W_Q2; W_K2] per layer as ONE packed [5d, d] Linear, and the layer's two
+        class tables E(embedding_e.weight), E_2(embedding_e.weight) [C, d] — in eval they depend on parameters only."""
+        def build():
+            emb = self.embedding_e.weight.detach().float().contiguous()
+            out = {"proj": [], "tab": []}
+            for L in self.layers:
+                A = L.attention_h
+                W = torch.cat([getattr(A, n).weight.detach().float() for n in ("Q", "K", "V", "Q_2", "K_2")], 0).contiguous()
+                out["proj"].append(ops.PackedLinear(ops.pack_weight(W), W.shape[0], W.shape[1], None))
+                out["tab"].append((ops.masked_linear(emb, _pack(A.E)), ops.masked_linear(emb, _pack(A.E_2))))
+            return out
+        return self._cached("full", build)
+
+    def _forward_full(self, g, h, p, e):
+        """transformer_net.py:86-150 with full_graph True: `g` is the complete graph of every molecule (ops.make_full_graph), g.edata['real']
+        marks the bonds and `e` holds a class for every pair.  Per layer the five node projections, the two [C, d] class tables and ONE
+        sn_full_attention_f32 launch — no per-edge projection exists.  Dropout sites and their ordinals as in the sparse net."""
+        try:
+            real = g.edata["real"]
+        except (AttributeError, KeyError, TypeError):
+            raise ValueError("TransformerNet with full_graph=True reads g.edata['real'] (1 for a bond, 0 for any other pair of the "
+                             "complete graph): build the graph with ops.make_full_graph") from None
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
+        if real.numel() != e.numel():
+            raise ValueError("TransformerNet: g.edata['real'] and e must both have one entry per edge")
+        codes = ops.full_graph_codes(e, real)
+        status = torch.zeros(1, dtype=torch.int32, device=h.device)     # a bond class outside embedding_e: one word for all layers
+        if grad:
+            batch, ei, B = self._plan(g, N)
+            hg = self._forward_full_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, hidx, p, codes, status)
+        else:
+            plan = cached_plan(g, N)
+            with torch.no_grad():
+                snap = self._drop_snap(train, h.device)
+                x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)
+                if not train and self._fusable():
+                    fz = self._full_eval()
+                    for li, L in enumerate(self.layers):
+                        d = L.out_channels
+                        P5 = ops.masked_linear(x, fz["proj"][li])                 # [N, 5d] = Q | K | V | Q_2 | K_2, read in place
+                        Q, K, V, Q2, K2 = (P5[:, i * d:(i + 1) * d] for i in range(5))
+                        Tr, Tf = fz["tab"][li]
+                        a = ops.full_attention(Q, K, V, Q2, K2, Tr, Tf, codes, L.gamma.detach(), plan, L.num_heads, status=status)
+                        s1, s2 = self._bn(L.batch_norm1_h, False), self._bn(L.batch_norm2_h, False)
+                        x1 = ops.masked_linear(a, self._pk(L.O_h), residual=x, residual_pre=True, scale=s1.scale, shift=s1.shift)
+                        f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
+                        x = ops.masked_linear(f, self._pk(L.FFN_h_layer2), residual=x1, residual_pre=True, scale=s2.scale, shift=s2.shift)
+                else:
+                    emb = self.embedding_e.weight.detach().float().contiguous()
+                    for li, L in enumerate(self.layers):
+                        A = L.attention_h
+                        Q, K, V, Q2, K2 = (ops.masked_linear(x, self._pk(getattr(A, n))) for n in ("Q", "K", "V", "Q_2", "K_2"))
+                        Tr, Tf = ops.masked_linear(emb, self._pk(A.E)), ops.masked_linear(emb, self._pk(A.E_2))
+                        a = ops.full_attention(Q, K, V, Q2, K2, Tr, Tf, codes, L.gamma.detach(), plan, L.num_heads, status=status)
+                        pd = L.dropout if train else 0.0
+                        if pd:
+                            a = ops.dropout(a, pd, snap, 1 + 2 * li)
+                        o = ops.masked_linear(a, self._pk(L.O_h))
+                        x1 = self._bn_res(o, x, L.batch_norm1_h, train)
+                        f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
+                        if pd:
+                            f = ops.dropout(f, pd, snap, 2 + 2 * li)
+                        f = ops.masked_linear(f, self._pk(L.FFN_h_layer2))
+                        x = self._bn_res(f, x1, L.batch_norm2_h, train)
+                hg = self._readout(x, plan)
+            self._h_last = x
+        if ops.deferring():
+            ops.defer("embed", status)
+        elif int(status.item()):
+            raise IndexError(ops.EMBEDDING_INDEX_ERROR)
+        self.g = g
+        return hg, g
+
+    def _forward_full_grad(self, plan, batch, ei, B, hidx, p, codes, status):
+        """Differentiable train-mode forward of a full-graph net: AG.full_attention's adjoint (sn_full_attention_bwd_f32) hands back the
+        gradients of the five projections, of the two class tables — which reach E.weight, E_2.weight and embedding_e.weight through
+        the [C, d] Linears that made them — and of gamma."""
+        vN, _, vB, k1 = _bucket_rows(self)          # (all rows valid: DGLBucketedStep refuses a full-graph net)
+        rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
+        snap = self._drop_snap(True, hidx.device)
+        x = self._encode_grad(hidx, p, vN, k1, snap)
+        emb = self.embedding_e.weight
+        for li, L in enumerate(self.layers):
+            A = L.attention_h
+            Q, K, V, Q2, K2 = (AG.linear(x, getattr(A, n).weight, None, vN, k1) for n in ("Q", "K", "V", "Q_2", "K_2"))
+            Tr, Tf = AG.linear(emb, A.E.weight), AG.linear(emb, A.E_2.weight)
+            a = AG.full_attention(Q, K, V, Q2, K2, Tr, Tf, L.gamma, codes, plan, rplan, L.num_heads, status)
             pd = L.dropout
             if pd:
                 a = AG.dropout(a, pd, snap, 1 + 2 * li)

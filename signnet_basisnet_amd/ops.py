@@ -924,6 +924,133 @@ def edge_attention_fused(qkv, Ee_all, layer: int, plan: GraphPlan, heads: int):
     return out
 
 
+FULL_ATTENTION_MAX_CLASSES = 16
+
+
+def _full_attention_blocks(fn, Q, K, V, Q2, K2):
+    """The five [N, d] float32 blocks of a full-graph attention and their common row stride: separate contiguous matrices (stride d) or
+    column views of one projection (unit column stride, one common row stride) — read in place, no copies."""
+    N, d = Q.shape
+    ld = Q.stride(0) if N > 1 else d
+    for t, n in ((Q, "Q"), (K, "K"), (V, "V"), (Q2, "Q_2"), (K2, "K_2")):
+        if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (N, d) or t.stride(1) != 1 or (N > 1 and t.stride(0) != ld) or ld < d:
+            raise ValueError(f"{fn}: {n} must be a float32 [N, heads*dk] block with unit column stride and the row stride of Q")
+    return N, d, ld
+
+
+def _full_attention_check(fn, d, heads, T_real, T_fake, codes, gamma, plan):
+    if d % heads or d // heads > 32:
+        raise ValueError(f"{fn}: heads must divide the width and the head width must be <= 32")
+    T_real, T_fake = _f32c(T_real, "T_real"), _f32c(T_fake, "T_fake")
+    Cc = T_real.shape[0]
+    if T_real.dim() != 2 or T_real.shape != T_fake.shape or T_real.shape[1] != d:
+        raise ValueError(f"{fn}: T_real and T_fake must both be [C, heads*dk]")
+    if not 1 <= Cc <= FULL_ATTENTION_MAX_CLASSES:
+        raise ValueError(f"{fn}: {Cc} edge classes not in [1, {FULL_ATTENTION_MAX_CLASSES}]")
+    if codes.dtype != torch.int32 or not codes.is_contiguous() or codes.numel() != plan.E:
+        raise ValueError(f"{fn}: codes must be a contiguous int32 vector with one entry (2 * class + real) per edge of the plan")
+    if gamma.dtype != torch.float32 or gamma.numel() != 1 or not gamma.is_cuda:
+        raise ValueError(f"{fn}: gamma must be one float32 in device memory")
+    return T_real, T_fake, Cc
+
+
+def full_attention(Q, K, V, Q2, K2, T_real, T_fake, codes, gamma, plan: GraphPlan, heads: int, status=None, want_den=False):
+    """Full-graph attention of the graph Transformer (layers/transformer.py:155-228, full_graph True) -> [N, heads*dk]: real pairs through
+    Q / K / T_real, fake pairs through Q_2 / K_2 / T_fake, mixed by clamp(gamma, 0, 1) — sn_full_attention_f32.  T_*: [C, heads*dk] class
+    tables (E(embedding_e.weight), E_2(embedding_e.weight)); codes int32 [E] = 2 * class + real in edge-id order; gamma: the Parameter
+    (read on the device).  Q .. K_2 may be column views of one projection.  A class outside [0, C) sets bit 0 of `status` (device
+    int32); with status=None the op checks it itself — one host sync, or ops.defer_status — and raises IndexError like nn.Embedding."""
+    require_cuda(Q, codes, gamma)
+    N, d, ld = _full_attention_blocks("full_attention", Q, K, V, Q2, K2)
+    if N != plan.N:
+        raise ValueError("full_attention: the blocks must have one row per node of the plan")
+    T_real, T_fake, Cc = _full_attention_check("full_attention", d, heads, T_real, T_fake, codes, gamma, plan)
+    out = torch.empty(N, d, dtype=torch.float32, device=Q.device)
+    den = torch.empty(N, int(heads), dtype=torch.float32, device=Q.device)
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=Q.device)
+    with _span("sn_full_attention_f32"):
+        check(lib().sn_full_attention_f32(ptr(Q), ptr(K), ptr(V), ptr(Q2), ptr(K2), ld, ptr(T_real), ptr(T_fake), Cc, ptr(codes), ptr(gamma), N,
+                                          int(heads), d // heads, ptr(plan.rowptr), ptr(plan.col), ptr(plan.eperm), ptr(out), ptr(den),
+                                          ptr(status), stream()), "sn_full_attention_f32")
+    if own and _DEFERRED_STATUS is not None:
+        defer("embed", status)
+    elif own and plan.E and int(status.item()):
+        raise IndexError(EMBEDDING_INDEX_ERROR)
+    return (out, den) if want_den else out
+
+
+def full_attention_bwd(Q, K, V, Q2, K2, T_real, T_fake, codes, gamma, out, den, dout, plan: GraphPlan, rplan: GraphPlan, heads: int):
+    """Adjoint of full_attention (sn_full_attention_bwd_f32) -> dQ, dK, dV, dQ_2, dK_2 [N, heads*dk], dT_real, dT_fake [C, heads*dk],
+    dgamma [1]; rplan: the plan of the flipped edge list.  No atomics: bit-identical on repeated calls."""
+    require_cuda(Q, dout)
+    N, d, ld = _full_attention_blocks("full_attention_bwd", Q, K, V, Q2, K2)
+    T_real, T_fake, Cc = _full_attention_check("full_attention_bwd", d, heads, T_real, T_fake, codes, gamma, plan)
+    out, den, dout = _f32c(out, "out"), _f32c(den, "den"), _f32c(dout, "dout")
+    dev = Q.device
+    new = lambda r: torch.empty(r, d, dtype=torch.float32, device=dev)
+    dQ, dK, dV, dQ2, dK2, dTr, dTf = new(N), new(N), new(N), new(N), new(N), new(Cc), new(Cc)
+    dgamma = torch.empty(1, dtype=torch.float32, device=dev)
+    scratch = torch.empty(max(int(lib().sn_full_attention_bwd_scratch_floats(N, plan.E, int(heads), d // heads, Cc)), 2), dtype=torch.float32,
+                          device=dev)
+    with _span("sn_full_attention_bwd_f32"):
+        check(lib().sn_full_attention_bwd_f32(ptr(Q), ptr(K), ptr(V), ptr(Q2), ptr(K2), ld, ptr(T_real), ptr(T_fake), Cc, ptr(codes), ptr(gamma),
+                                              ptr(out), ptr(den), ptr(dout), N, plan.E, int(heads), d // heads, ptr(plan.rowptr), ptr(plan.col),
+                                              ptr(plan.eperm), ptr(rplan.rowptr), ptr(rplan.col), ptr(rplan.eperm), ptr(dQ), ptr(dK), ptr(dV),
+                                              ptr(dQ2), ptr(dK2), ptr(dTr), ptr(dTf), ptr(dgamma), ptr(scratch), stream()),
+              "sn_full_attention_bwd_f32")
+    return dQ, dK, dV, dQ2, dK2, dTr, dTf, dgamma
+
+
+def full_graph_codes(e, real):
+    """The int32 edge codes full_attention reads: 2 * class + real (index plumbing only)."""
+    return (e.long().reshape(-1) * 2 + (real.reshape(-1) != 0).long()).to(torch.int32)
+
+
+MAKE_FULL_GRAPH_ERROR = ("make_full_graph: the sparse graph has a self loop or a repeated (u, v) edge — the reference's assignment of the "
+                         "real edges (data/molecules.py:233-234) gives neither a meaning")
+
+
+def make_full_graph(g, e, status=None):
+    """data/molecules.py:211-235 for a whole batch in one launch (sn_make_full_graph): the complete directed graph of every graph of
+    `g` -> a dgl_deepsigns.Graph over sum n (n - 1) edges — per graph u-major, v ascending, v != u, the order of
+    networkx.complete_graph(n).to_directed().edges() — with edata['real'] (int64 0 / 1) and edata['feat'] = the full `e` (int64: a real
+    edge keeps its class, a fake edge gets 0), which is also returned: (full_g, e_full).  The sizes come from the graph object's
+    batch_num_nodes() (free when it is a host tensor).  A self loop or a repeated (u, v) sets `status` (device int32 [1]); with
+    status=None the op checks it itself — one host sync, or ops.defer_status — and raises ValueError."""
+    from .dgl_deepsigns import Graph, cached_plan
+    src, _ = g.edges()
+    require_cuda(src, e)
+    if e.dtype != torch.int64:
+        raise ValueError("make_full_graph: the bond classes must be int64")
+    e = e.reshape(-1).contiguous()
+    bnn = g.batch_num_nodes()
+    counts = bnn.detach().to("cpu", torch.int64)
+    N = int(counts.sum())
+    bne = counts * (counts - 1)
+    E_full = int(bne.sum())
+    plan = cached_plan(g, N)
+    if e.numel() != plan.E:
+        raise ValueError("make_full_graph: one bond class per edge of the graph expected")
+    dev = src.device
+    buf = torch.empty(4, E_full, dtype=torch.int64, device=dev)
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _span("sn_make_full_graph"):
+        check(lib().sn_make_full_graph(ptr(plan.graph_ptr), plan.B, N, ptr(plan.rowptr), ptr(plan.col), ptr(plan.eperm), ptr(e), plan.E, E_full,
+                                       ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(buf[3]), ptr(status), stream()), "sn_make_full_graph")
+    if own and _DEFERRED_STATUS is not None:
+        defer("flag", status, MAKE_FULL_GRAPH_ERROR)
+    elif own and int(status.item()):
+        raise ValueError(MAKE_FULL_GRAPH_ERROR)
+    full = Graph(buf[0], buf[1], bnn, bne)
+    full.edata["real"] = buf[2]
+    full.edata["feat"] = buf[3]
+    return full, buf[3]
+
+
 def gat_aggregate(feat, attn_l, attn_r, bias, plan: GraphPlan, heads: int, negative_slope=0.2, relu=True, want_lse=False):
     """DGL GATConv after its fc (gat_net.py:62-66): feat [N, heads*C] -> [N, heads*C]; see sn_gat_aggregate_f32."""
     require_cuda(feat)

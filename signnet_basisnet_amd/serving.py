@@ -41,6 +41,8 @@ class GraphedDGLForward:
         from .train_graph import GraphedForward
         if net.training:
             raise ValueError("GraphedDGLForward records the eval forward: call net.eval() first")
+        if getattr(net, "full_graph", False):
+            raise NotImplementedError("GraphedDGLForward does not carry the edge flag edata['real'] of a full_graph=True net into its static buffers")
         dev = h.device
         src, dst = g.edges()
         bnn = torch.as_tensor(g.batch_num_nodes())

@@ -613,6 +613,8 @@ class DGLBucketedStep(_CaptureLRU):
     def __init__(self, net, optimizer, max_graphs=128, granule=None, max_captures=4, warmup=2, flip_rng="host"):
         from . import dgl_nets
         from .optim import FlatAdam
+        if getattr(net, "full_graph", False):
+            raise NotImplementedError("DGLBucketedStep does not carry the edge flag edata['real'] of a full_graph=True net through its pack launch")
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("DGLBucketedStep needs optim.FlatAdam (static flat parameter / gradient buffers)")
         if not isinstance(net, tuple(getattr(dgl_nets, n) for n in _DGL_NETS)):
