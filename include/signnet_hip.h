@@ -901,7 +901,10 @@ int sn_gnn_fused_f32(const sn_gnn_params* params, const void* x, int ldx, const 
  * workgroup to finish copies flags_src[0 .. n_flags) (device; typically sn_batch_plan's status words followed by
  * sn_plan_bins.meta) to it, after every workgroup's own flag updates, and then — behind a system-scope fence — stores 1 to
  * flags_host[n_flags] (so flags_host holds n_flags + 1 ints).  A caller that zeroed that word before the launch can poll
- * it from the host: once it reads 1 the flags are there; no event / marker packet on the stream is needed. */
+ * it from the host: once it reads 1 the flags are there; no event / marker packet on the stream is needed.  (Lanes 0 .. n_flags-1
+ * of one wave copy one word each, then one system-scope fence, then the ready word.)  The launch cannot retire before those
+ * stores have crossed the host link, so a caller with a one-launch plan does better to take the same verdicts from the plan
+ * launch (sn_plan_early: written in the first microseconds of the forward) and pass flags_host = NULL here. */
 
 /* Front records: the part of the stage above that depends on the batch and the weights alone — the graph-local CSR of GNN.forward's
  * edge_index (model.py:47-55), the (layer, class) rows of the edge encoders, the input encoder and the x half of
@@ -913,7 +916,10 @@ int sn_gnn_fused_f32(const sn_gnn_params* params, const void* x, int ldx, const 
  *                           (more than 64 nodes or 192 in-edges, an id outside its table, an edge across graphs, an unsorted batch
  *                           vector) gets valid = 0 and nothing else; no flag is raised here
  *   sn_gnn_fused_front_f32  sn_gnn_fused_f32 reading the records: a graph with a valid record starts at the slot sum; any other runs
- *                           the stage's own prologue, flags included.  Same arithmetic in the same order: bit-identical outputs */
+ *                           the stage's own prologue, flags included.  Same arithmetic in the same order: bit-identical outputs.
+ *                           The kernel that reads the records carries no flag report (a plan with records is a one-launch plan:
+ *                           arm sn_plan_early for the report).  With flags_host != NULL the call is served by sn_gnn_fused_f32's
+ *                           kernel and its report: the records are validated but not read, the outputs are the same bits */
 int64_t sn_gnn_front_bytes(const sn_gnn_params* params);
 int sn_batch_plan_front(const int64_t* batch, int64_t N, int64_t B, const int64_t* edge_index, int64_t E,
                         int kmax, int32_t* graph_ptr, int32_t* node_graph, int32_t* nvalid, int64_t* evoff,

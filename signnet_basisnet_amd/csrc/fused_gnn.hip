@@ -325,17 +325,28 @@ __global__ __launch_bounds__(GNN_WAVES * 64, 2) void k_gnn_coop(GnnStruct S, sn_
   } else {
     gnn_graph<NT, MODE>(S, P);
   }
-  if (S.flags_host != nullptr) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __threadfence();                                              // my flag updates are visible device-wide
-      if (atomicAdd(&S.status[4], 1) == (int)gridDim.x - 1) {       // every other workgroup has passed its fence
-        __threadfence();
-        for (int i = 0; i < S.n_flags; ++i)
-          S.flags_host[i] = __hip_atomic_load(&S.flags_src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence_system();
-        __hip_atomic_store(&S.flags_host[S.n_flags], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // "ready": a host polling
-        __threadfence_system();                                                                        // this word sees the flags
+  // Flag report by the last workgroup to finish.  The FRONT form carries none: a plan with front records is a one-launch plan, whose
+  // own workgroups report the same verdicts in the first microseconds of the forward (sn_plan_early) — a launch with front records
+  // and flags_host is served by the form below (gnn_fused_impl).
+  if constexpr (!FRONT) {
+    if (S.flags_host != nullptr) {
+      __syncthreads();
+      if (threadIdx.x < 64) {                                         // wave 0
+        int last = 0;
+        if (threadIdx.x == 0) {
+          __threadfence();                                            // my flag updates are visible device-wide
+          last = atomicAdd(&S.status[4], 1) == (int)gridDim.x - 1;    // every other workgroup has passed its fence
+        }
+        if (__shfl(last, 0, 64)) {
+          __threadfence();
+          // one word per lane (n_flags <= 64): one load and one store in flight per lane instead of n_flags dependent round trips
+          // over the host link; the fence below waits for all of the wave's stores before lane 0 publishes the ready word
+          if ((int)threadIdx.x < S.n_flags)
+            S.flags_host[threadIdx.x] = __hip_atomic_load(&S.flags_src[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __threadfence_system();
+          if (threadIdx.x == 0)                                       // "ready": a host polling this word sees the flags
+            __hip_atomic_store(&S.flags_host[S.n_flags], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
       }
     }
   }
@@ -410,6 +421,9 @@ static int gnn_fused_impl(const sn_gnn_params* params, const void* x, int ldx, c
     SN_REQUIRE(P.d == FR_D && P.node_discrete == 1 && P.node_nf == 1 && P.edge_discrete == 1 && P.edge_nf == 1 && P.n_layers >= 1,
                "sn_gnn_fused_front_f32: the front record serves d = 128 with one discrete node and one discrete edge feature column");
     SN_REQUIRE((reinterpret_cast<uintptr_t>(front) & 15) == 0, "sn_gnn_fused_front_f32: the record buffer must be 16-byte aligned");
+  }
+  // (front records + flags_host: the form without records below — it carries the in-kernel report, and its outputs are the same bits)
+  if (front != nullptr && flags_host == nullptr) {
     S.front = reinterpret_cast<const unsigned char*>(front);
     S.front_stride = front_stride(front_ee_cap(P));
     rc = launch_gnn<8, 0, true>(S, P, B, st);

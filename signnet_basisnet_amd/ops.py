@@ -165,25 +165,62 @@ class EarlyReport:
     are normally set by the time the host has queued the stage kernels) and returns the flag words as a list."""
     ERR, NMAX, DEGMAX, EDGES, PHI, RHO, IDS, DONE = 0, 1, 2, 3, 4, 5, 6, 8
     _pool = []
+    _made = 0           # pinned slots ever allocated (= slots in the pool + slots of reports not yet released)
 
     def __init__(self):
+        # (a pooled slot keeps its ctypes mirror: arming it again only rewrites the fields — the serving mode arms one per forward)
         if EarlyReport._pool:
-            self.t, self.v = EarlyReport._pool.pop()
+            self.t, self.v, self._cbuf = EarlyReport._pool.pop()
         else:
             self.t = torch.zeros(16, dtype=torch.int32, pin_memory=True)
             self.v = self.t.numpy()
+            self._cbuf = _PlanEarlyC(None, 0, 0, None, 0, 0, 0, 0, self.t.data_ptr())
+            EarlyReport._made += 1
         self.v[:] = 0
         self.cstruct = None
         self._keep = None
+        self.kword = 0      # serving mode: the slot count an all-eigenvector forward sized its tensors with (0: max_k given)
+
+    def poll(self):
+        """The 16 words as a list once all four done words are set, else None (never blocks; one read of the pinned words)."""
+        w = self.v.tolist()
+        return w if (w[8] and w[9] and w[10] and w[11]) else None
+
+    def done(self):
+        """All four done words are set (never blocks): the plan launch has written everything it writes to this slot."""
+        return self.poll() is not None
+
+    @classmethod
+    def words_bad(cls, fl, kword=0):
+        """Whether the polled words report anything check_last() raises for (the clean case: no list is built)."""
+        return bool(fl[0] or fl[3] or fl[4] or fl[5] or fl[6] or (kword and fl[1] > kword))
+
+    def status_words(self, fl=None):
+        """The report in the layout of the stage kernels' flag block ([status(8) | bins meta(8)] + the host's slot-count word, what
+        SignNetGNN._flags_bad / _flags_error judge) — call once done().  status[3] carries the GINE stage's bits as that stage would
+        have set them: 1 a graph beyond the node / in-edge limits, 4 a feature id outside its table, 8 a graph without nodes."""
+        if fl is None:
+            fl = self.v.tolist()
+        w = [0] * 32
+        w[0], w[1], w[2] = fl[self.ERR], fl[self.NMAX], fl[self.DEGMAX]
+        w[3] = (1 if (fl[self.EDGES] or (fl[self.PHI] & 1)) else 0) | (4 if fl[self.IDS] else 0) | (fl[self.PHI] & 8)
+        w[9], w[13] = fl[self.PHI] & 5, fl[self.RHO]
+        w[24] = int(self.kword)
+        return w
 
     def arm(self, node_ids=None, node_vocab=0, edge_ids=None, edge_vocab=0, max_graph_edges=0):
         self._keep = (node_ids, edge_ids)
-        self.cstruct = _PlanEarlyC(ptr(node_ids), 0 if node_ids is None else node_ids.numel(), int(node_vocab),
-                                   ptr(edge_ids), 0 if edge_ids is None else edge_ids.numel(), int(edge_vocab),
-                                   int(max_graph_edges), 0, self.t.data_ptr())
+        c = self._cbuf
+        c.node_ids, c.n_node_ids, c.node_vocab = ptr(node_ids), 0 if node_ids is None else node_ids.numel(), int(node_vocab)
+        c.edge_ids, c.n_edge_ids, c.edge_vocab = ptr(edge_ids), 0 if edge_ids is None else edge_ids.numel(), int(edge_vocab)
+        c.max_graph_edges = int(max_graph_edges)
+        self.cstruct = c
         return self
 
     def wait(self, timeout_s=5.0):
+        w = self.poll()
+        if w is not None:
+            return w[:8]
         v = self.v
         if not (v[8] and v[9] and v[10] and v[11]):
             import time
@@ -211,11 +248,20 @@ class EarlyReport:
     def release(self):
         """Back to the pool (only once the launch that writes it has completed: after wait())."""
         self._keep = self.cstruct = None
-        EarlyReport._pool.append((self.t, self.v))
+        EarlyReport._pool.append((self.t, self.v, self._cbuf))
+
+
+_early_ok = {}      # (N, E, B) -> sn_batch_plan_early_supported: a serving loop asks for the same shapes at every forward
 
 
 def early_supported(N: int, E: int, B: int) -> bool:
-    return bool(lib().sn_batch_plan_early_supported(int(N), int(E), int(B)))
+    key = (N, E, B)
+    r = _early_ok.get(key)
+    if r is None:
+        if len(_early_ok) >= 4096:
+            _early_ok.clear()
+        r = _early_ok[key] = bool(lib().sn_batch_plan_early_supported(int(N), int(E), int(B)))
+    return r
 
 
 def build_plan(batch: torch.Tensor, edge_index: torch.Tensor, num_graphs: int, kmax: int = 0, bins: bool = False,

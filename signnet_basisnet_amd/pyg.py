@@ -522,7 +522,9 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         #   strict=False: the serving / throughput mode (bench.py): no host wait.  The outputs of every graph that could not
         #                 be evaluated are NaN (never uninitialised memory: the GINE kernel fills them), and the error itself
         #                 is raised at the next forward, at check_last() or at train()/eval(), whichever comes first (a
-        #                 module deleted with an unreported error warns).
+        #                 module deleted with an unreported error warns).  With a one-launch plan the queued report is the plan
+        #                 kernel's too (the same pinned words strict mode waits for, read later); beyond it, in the overlap mode and
+        #                 on padded plans the GINE kernel's last workgroup posts the flags at the end of the forward.
         self.strict = True
         # overlap_front: see _forward_overlapped (serving loops over resident batches; needs strict = False)
         self.overlap_front, self.overlap_inputs_ready, self._side_streams = False, True, None
@@ -531,6 +533,7 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         self.attn_dropout = 0.1
         self._attn_dropout_source = self.DEFAULT_ATTN_DROPOUT_SOURCE     # see the property below
         self._pending, self._free_hosts, self._flags_host = [], [], None
+        self._limbo = []            # plan reports dropped unread whose launch may still be writing them (check_last)
         self.sign_net = SignNet(n_hid, nl_signnet, self.nl_rho, variant, ignore_eigval)
         self.gnn = GNN(node_feat, edge_feat, n_hid, n_out, nl_gnn, variant)
         self._prep = None
@@ -706,16 +709,44 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
     def check_last(self, wait=True):
         """Raise if an earlier forward's batch could not be served by the fused kernels (wait=False: only look at
         status reports that have already arrived)."""
+        if getattr(self, "_limbo", None):
+            self._sweep_limbo()
         while self._pending:
             ev, host = self._pending[0]
-            if not wait and len(self._pending) <= 4 and not self._arrived(ev, host):
-                break
-            self._wait_status(ev, host)
-            self._pending.pop(0)
-            self._free_hosts.append(host)
-            if self._flags_bad(host[1]):
+            if isinstance(host, ops.EarlyReport):      # the plan launch's report: one read of its pinned words
+                fl = host.poll()
+                if fl is None:
+                    if not wait and len(self._pending) <= 4:
+                        break
+                    self._wait_status(ev, host)
+                    fl = host.poll()
+                self._pending.pop(0)
+                flags = host.status_words(fl) if host.words_bad(fl, host.kword) else None
+                host.release()
+            else:
+                if not wait and len(self._pending) <= 4 and not self._arrived(ev, host):
+                    break
+                self._wait_status(ev, host)
+                self._pending.pop(0)
+                self._free_hosts.append(host)
+                flags = host[1] if self._flags_bad(host[1]) else None
+            if flags is not None and self._flags_bad(flags):
+                # the reports behind it are dropped unread; a pinned slot whose plan launch may still be in flight is parked, not pooled
+                self._limbo = getattr(self, "_limbo", []) + [h for _, h in self._pending if isinstance(h, ops.EarlyReport)]
                 self._pending.clear()
-                raise self._flags_error(host[1])
+                self._sweep_limbo()
+                raise self._flags_error(flags)
+
+    def _sweep_limbo(self):
+        """Dropped plan reports go back to the pool once their done words are set — never while the launch may still write to them."""
+        limbo = getattr(self, "_limbo", None)
+        if limbo:
+            self._limbo = []
+            for h in limbo:
+                if h.done():
+                    h.release()
+                else:
+                    self._limbo.append(h)
 
     _READY = 16          # word of the pinned buffer the GINE kernel sets to 1 after the 16 flags (sn_gnn_fused_f32)
     _KWORD = 24          # word the HOST writes: the slot count an all-eigenvector forward sized its tensors with (0: max_k given)
@@ -733,10 +764,15 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
 
     @classmethod
     def _arrived(cls, ev, host):
+        if isinstance(host, ops.EarlyReport):
+            return host.done()
         return bool(host[1][cls._READY]) if ev is None else ev.query()
 
     @classmethod
     def _wait_status(cls, ev, host):
+        if isinstance(host, ops.EarlyReport):
+            host.wait()
+            return
         if ev is not None:
             ev.synchronize()
             return
@@ -794,18 +830,15 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         if not capturing:
             self.check_last(wait=False)
         self._early = None            # (a report armed by a forward that raised must never be read as this batch's)
+        self._cap = capturing
         try:
             with _lib_mod.stream_scope():
                 y = self._forward(data, return_stages)
         except BaseException:
-            stale, self._early = self._early, None
-            if stale is not None:     # the plan kernel may still write to the pinned words: hand them back only once it has
-                try:
-                    stale.wait()
-                    stale.release()
-                except Exception:
-                    pass              # (left to the garbage collector: never recycled while a launch may write to it)
+            self._drop_early()
             raise
+        finally:
+            self._cap = None
         early, self._early = self._early, None
         if capturing:
             # A forward being captured into a HIP graph never waits on the host — whatever `strict` says: the flags stay on the device
@@ -813,7 +846,11 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
             self._captured_plan, self._captured_K = self._last_plan, self._last_K
             self._last_plan = None
             return y
-        if early is not None:
+        if early is not None and not self.strict:
+            # serving mode, flags from the plan kernel: queued unread — check_last() / the next forward's check_last(wait=False) look
+            self._early = early
+            self._queue_status()
+        elif early is not None:
             # strict mode, flags from the plan kernel (already in pinned memory: the stage kernels were queued in the meantime)
             fl = early.wait()
             early.release()
@@ -843,6 +880,29 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
                 self._pending.append((ev, host))
         self._last_plan = None
         return y
+
+    def _drop_early(self):
+        """A forward that raised with a plan report armed: the plan kernel may still write to the pinned words — they go back to the
+        pool only once it has."""
+        stale, self._early = self._early, None
+        if stale is not None:
+            try:
+                stale.wait()
+                stale.release()
+            except Exception:
+                pass              # (left to the garbage collector: never recycled while a launch may write to it)
+
+    def _queue_status(self):
+        """Serving mode: queue this forward's flags in _pending — the plan launch's armed report when there is one (a one-launch plan),
+        else the GINE kernel's own report / a stream copy (_post_status)."""
+        early, self._early = self._early, None
+        if early is not None:
+            early.kword = 0 if self.max_k else int(self._last_K)
+            self._pending.append((None, early))
+            return
+        ev, host = self._post_status(self._last_plan)
+        host[1][self._KWORD] = 0 if self.max_k else int(self._last_K)
+        self._pending.append((ev, host))
 
     def _serve_beyond_limits(self, data):
         """Strict mode, a batch the stage kernels refused (a graph of more than 64 nodes or 192 in-edges, or without nodes — the
@@ -874,11 +934,10 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
                 sub = D.slice_graphs(data, lo, hi, sizes)
                 outs.append(self._forward(sub, False, force_layer=is_bad))
                 if not is_bad and self._used_fused:
-                    ev, host = self._post_status(self._last_plan)
-                    host[1][self._KWORD] = 0 if self.max_k else int(self._last_K)
-                    self._pending.append((ev, host))
+                    self._queue_status()
         finally:
             self.strict = saved_strict
+            self._drop_early()       # (a sub-forward that raised with its report armed)
         return torch.cat(outs, 0)
 
     # ------------------------------------------------------------------ differentiable train-mode forward
@@ -1052,11 +1111,14 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         a graph with more than 192 in-edges, discrete feature ids outside their embedding tables (nn.Embedding's IndexError)."""
         xi = ei = None
         nv = ev = 0
-        if gplan.node_discrete and data.x.dtype == torch.int64 and data.x.is_cuda:
-            xi, nv = data.x.contiguous(), int(gplan.params.node_vocab)
-        if gplan.edge_discrete and int(gplan.params.n_layers) > 0 and data.edge_attr.dtype == torch.int64 and data.edge_attr.is_cuda \
-                and data.edge_attr.numel() > 0:
-            ei, ev = data.edge_attr.contiguous(), int(gplan.params.edge_vocab)
+        st = getattr(gplan, "_early_static", None)      # (what does not change from forward to forward, read from the ctypes struct once)
+        if st is None:
+            st = gplan._early_static = (bool(gplan.node_discrete), int(gplan.params.node_vocab),
+                                        bool(gplan.edge_discrete) and int(gplan.params.n_layers) > 0, int(gplan.params.edge_vocab))
+        if st[0] and data.x.dtype == torch.int64 and data.x.is_cuda:
+            xi, nv = data.x.contiguous(), st[1]
+        if st[2] and data.edge_attr.dtype == torch.int64 and data.edge_attr.is_cuda and data.edge_attr.numel() > 0:
+            ei, ev = data.edge_attr.contiguous(), st[3]
         return ops.EarlyReport().arm(xi, nv, ei, ev, fused.GNN_MAX_EDGES)
 
     def _forward_overlapped(self, data, P, B):
@@ -1133,8 +1195,13 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         early = None
         N_, E_n = int(data.batch.numel()), (int(data.edge_index.shape[1]) if data.edge_index.numel() else 0)
         # (a forward being captured into a HIP graph must not wait on the host: no early report, the flags stay on the device)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if all_fused and self.strict and not capturing and ops.early_supported(N_, E_n, B):
+        capturing = getattr(self, "_cap", None)          # (forward() has asked already)
+        if capturing is None:
+            capturing = torch.cuda.is_current_stream_capturing()
+        # One-launch plans report from the plan kernel in either status mode: strict mode waits for the words below, the serving mode
+        # (strict = False) queues the armed report in _pending — the GINE kernel then carries no report of its own at its end, where
+        # the launch could not retire before the words had crossed the host link.
+        if all_fused and not capturing and ops.early_supported(N_, E_n, B):
             early = self._arm_early(P["gnn_fused"], data)
         K_host = None if self.max_k else host_max_nodes(data)
         if not self.max_k and K_host is None and early is None and not return_stages and not capturing and ops.early_supported(N_, E_n, B):
@@ -1154,7 +1221,7 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
             K = early.wait_nmax()        # N_max as the plan kernel reports it to pinned memory (the reference's to_dense_EVD reads it back too)
         else:
             K = plan.check()[1]          # N_max: one host sync, as the reference's to_dense_EVD does
-        if early is not None and not (all_fused and self.strict):
+        if early is not None and not all_fused:      # (armed for the largest graph only)
             early.wait()
             early.release()
             early = None
@@ -1219,7 +1286,9 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
                 x = ops.masked_layernorm(z, y, L["ln2"][0], L["ln2"][1], LN_EPS, nv, K)
             s = ops.slot_sum(x, N, K)
         if use_gnn_fused and not return_stages:
-            self._flags_host = self._host_flags() if (plan.bins is not None and not _NO_KERNEL_FLAGS and self._early is None) else None
+            # (a forward being captured posts nothing to the host: its flags stay in the plan's status words for check_captured())
+            self._flags_host = self._host_flags() if (plan.bins is not None and not _NO_KERNEL_FLAGS and self._early is None
+                                                      and not capturing) else None
             if self._flags_host is not None:
                 self._flags_host[1][:] = 0        # host-side; the kernel's last workgroup overwrites it, ready word last
             return P["gnn_fused"].run(plan, data.x, data.edge_attr, s, None if self._flags_host is None else self._flags_host[0])
