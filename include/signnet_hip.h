@@ -1429,6 +1429,42 @@ int sn_make_full_graph(const int32_t* graph_ptr, int64_t B, int64_t N, const int
                        const int64_t* e, int64_t E, int64_t E_full, int64_t* src, int64_t* dst, int64_t* real, int64_t* e_full,
                        int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Full-graph attention from the molecular (bond) graph: what sn_full_attention_f32 computes on the output of sn_make_full_graph,
+ * without the edge list of sum n (n - 1) pairs.  The complete graph of graph g is its node range graph_ptr[g] .. graph_ptr[g + 1]; the
+ * pair (j -> i), j != i, is real exactly when j -> i is a bond — an in-edge of i in rowptr / col / eperm, the destination-sorted plan of
+ * the BOND graph — and is then scored through K / Q / T_real[e[edge]]; every other pair through K_2 / Q_2 / T_fake[0].  The operations
+ * per pair and out = sum s V / (sum s + 1e-6), den = sum s are those of sn_full_attention_f32; a one-node graph gets exact zeros.
+ *   e: the bond classes, int64 [E] in edge-id order, read in place.  graph_valid [B] / edge_valid [E]: int32 0 / 1, NULL = all valid.
+ *   A graph with graph_valid 0 is skipped whatever it holds: its out / den rows (and its rows of dQ .. dK_2) are zeros and it raises no
+ *   flag.  An edge with edge_valid 0 is not a bond.  status: NULL or int32 [2].  status[0] bit 0: a bond class outside [0, C) — never
+ *   dereferenced, the pair contributes nothing.  status[1]: bit 0 a self loop, bit 1 a repeated (u, v) (both as sn_make_full_graph; a
+ *   self loop is ignored, a repeated bond keeps its first class), bit 2 a bond whose source lies outside its destination's graph (ignored).
+ * One workgroup per (graph, head): the head's K | K_2 | V columns of the graph's rows and an n x n byte table of pair codes are staged
+ * in LDS once.  Whether a graph fits is decided in the kernel from graph_ptr: sn_bond_full_attention_staged_nodes(dk, bwd) is the
+ * largest staged graph; a larger one takes a global-memory path with the same arithmetic — same bits.  Any graph size; dk <= 32 and
+ * C <= 16, else SN_ERR_ARG.  A graph's result does not depend on the other graphs of the batch: padding changes no bit.
+ *
+ * sn_bond_full_attention_bwd_f32: dQ, dK, dV, dQ2, dK2 [N, heads*dk] (contiguous), dT_real, dT_fake [C, heads*dk] (rows >= 1 of dT_fake
+ *   are zero), dgamma [1] (0 outside 0 <= gamma <= 1).  The pairs are re-scored in the workgroup (a destination pass and a source
+ *   pass); each node's share of the class-table gradients goes to its own scratch rows, which the workgroup adds in node order into a
+ *   per-graph table; a finish launch adds those (16 interleaved runs of graphs per element, each in graph order, then the 16 sums in
+ *   order) and the float64 per-(graph, head) dgamma partials in a fixed order that depends on an entry's index only: trailing padding
+ *   graphs change no bit.  No atomics in any sum.  scratch: sn_bond_full_attention_bwd_scratch_floats(N, B, heads, dk, C) floats, 8-byte aligned. */
+int64_t sn_bond_full_attention_staged_nodes(int dk, int bwd);
+int sn_bond_full_attention_f32(const float* Q, const float* K, const float* V, const float* Q2, const float* K2, int64_t ld,
+                               const float* T_real, const float* T_fake, int C, const int64_t* e, const float* gamma, int64_t N, int64_t B,
+                               int64_t E, int heads, int dk, const int32_t* graph_ptr, const int32_t* rowptr, const int32_t* col,
+                               const int32_t* eperm, const int32_t* graph_valid, const int32_t* edge_valid, float* out, float* den,
+                               int32_t* status, void* stream);
+int64_t sn_bond_full_attention_bwd_scratch_floats(int64_t N, int64_t B, int heads, int dk, int C);
+int sn_bond_full_attention_bwd_f32(const float* Q, const float* K, const float* V, const float* Q2, const float* K2, int64_t ld,
+                                   const float* T_real, const float* T_fake, int C, const int64_t* e, const float* gamma, const float* out,
+                                   const float* den, const float* dout, int64_t N, int64_t B, int64_t E, int heads, int dk,
+                                   const int32_t* graph_ptr, const int32_t* rowptr, const int32_t* col, const int32_t* eperm,
+                                   const int32_t* graph_valid, const int32_t* edge_valid, float* dQ, float* dK, float* dV, float* dQ2,
+                                   float* dK2, float* dT_real, float* dT_fake, float* dgamma, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,9 +168,15 @@ SIGNATURES = {
     "sn_full_attention_bwd_f32": [_p, _p, _p, _p, _p, _l, _p, _p, _i, _p, _p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p,
                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_make_full_graph": [_p, _l, _l, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p],
+    "sn_bond_full_attention_staged_nodes": [_i, _i],                     # (int64 counts: _SPECIAL_RESTYPE)
+    "sn_bond_full_attention_bwd_scratch_floats": [_l, _l, _i, _i, _i],
+    "sn_bond_full_attention_f32": [_p, _p, _p, _p, _p, _l, _p, _p, _i, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "sn_bond_full_attention_bwd_f32": [_p, _p, _p, _p, _p, _l, _p, _p, _i, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p,
+                                       _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 _SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64,
-                    "sn_gnn_front_bytes": C.c_int64, "sn_full_attention_bwd_scratch_floats": C.c_int64}
+                    "sn_gnn_front_bytes": C.c_int64, "sn_full_attention_bwd_scratch_floats": C.c_int64,
+                    "sn_bond_full_attention_staged_nodes": C.c_int64, "sn_bond_full_attention_bwd_scratch_floats": C.c_int64}
 
 _lib = None
 
@@ -216,6 +222,8 @@ def lib():
         L.sn_evd_large_work_ints.restype = _SPECIAL_RESTYPE["sn_evd_large_work_ints"]
         L.sn_gnn_front_bytes.restype = _SPECIAL_RESTYPE["sn_gnn_front_bytes"]
         L.sn_full_attention_bwd_scratch_floats.restype = _SPECIAL_RESTYPE["sn_full_attention_bwd_scratch_floats"]
+        for name in ("sn_bond_full_attention_staged_nodes", "sn_bond_full_attention_bwd_scratch_floats"):
+            getattr(L, name).restype = _SPECIAL_RESTYPE[name]
         L.sn_ign_contract_scratch_floats.argtypes = [_l, _i]
         L.sn_ign_contract_scratch_floats.restype = C.c_int64
         L.sn_train_linear_bwd_part_floats.argtypes = [_l, _i, _i, _i]

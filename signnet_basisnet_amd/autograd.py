@@ -631,6 +631,35 @@ def full_attention(Q, K, V, Q2, K2, T_real, T_fake, gamma, codes, plan, rplan, h
     return _FullAttention.apply(Q, K, V, Q2, K2, T_real, T_fake, gamma, codes, plan, rplan, heads, status)
 
 
+class _BondFullAttention(Function):
+    """ops.bond_full_attention as an autograd node.  Saved: the five node blocks, the two [C, d] class tables, gamma, out and the
+    [N, heads] denominators — nothing with a row per pair, and no reverse plan."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, Q2, K2, T_real, T_fake, gamma, e, plan, heads, status, graph_valid, edge_valid):
+        Q, K, V, Q2, K2 = _c(Q), _c(K), _c(V), _c(Q2), _c(K2)
+        T_real, T_fake = _c(T_real), _c(T_fake)
+        out, den = ops.bond_full_attention(Q, K, V, Q2, K2, T_real, T_fake, e, gamma.detach(), plan, heads, status=status,
+                                           graph_valid=graph_valid, edge_valid=edge_valid, want_den=True)
+        ctx.save_for_backward(Q, K, V, Q2, K2, T_real, T_fake, gamma, out, den)
+        ctx.meta = (e, plan, heads, graph_valid, edge_valid)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, K, V, Q2, K2, T_real, T_fake, gamma, out, den = ctx.saved_tensors
+        e, plan, heads, gv, ev = ctx.meta
+        grads = ops.bond_full_attention_bwd(Q, K, V, Q2, K2, T_real, T_fake, e, gamma.detach(), out, den, _c(g), plan, heads,
+                                            graph_valid=gv, edge_valid=ev)
+        dgamma = grads[7].reshape(gamma.shape)
+        return grads[:7] + (dgamma, None, None, None, None, None, None)
+
+
+def bond_full_attention(Q, K, V, Q2, K2, T_real, T_fake, gamma, e, plan, heads, status=None, graph_valid=None, edge_valid=None):
+    """Differentiable ops.bond_full_attention: gradients reach Q, K, V, Q_2, K_2, the class tables T_real / T_fake and gamma."""
+    return _BondFullAttention.apply(Q, K, V, Q2, K2, T_real, T_fake, gamma, e, plan, heads, status, graph_valid, edge_valid)
+
+
 class _GatAggregate(Function):
     """dgl GATConv after its fc (gat_net.py:62-66): edge softmax of leaky_relu(el[src] + er[dst]) + weighted sum + bias + ReLU."""
 

@@ -1103,7 +1103,11 @@ class TransformerNet(_DGLNet):
     Eval, train-mode value and — with gradients enabled — the differentiable path (`_forward_grad`).
     full_graph True (`--full_graph`): `g` is the complete graph of every molecule with g.edata['real'] (ops.make_full_graph); bonds go
     through Q / K / E, all other pairs through Q_2 / K_2 / E_2, mixed by each layer's gamma — `_forward_full`, one sn_full_attention_f32
-    launch per layer on the layer path (no one-launch stage kernel)."""
+    launch per layer on the layer path (no one-launch stage kernel).
+    `full_graph_input` (a property of a full_graph=True net, default "edges"): "bonds" — `g` is the MOLECULAR graph and `e` its bond
+    classes [E], as the sparse net takes them; the attention works the complete graph out from each molecule's node range
+    (sn_bond_full_attention_f32: no sn_make_full_graph, nothing with a row per pair).  Such a batch is an ordinary DGL batch, which
+    train_graph.DGLBucketedStep, serving.GraphedDGLForward and data.DGLGraphStore carry.  Never a state_dict key."""
 
     fused_layers = True     # eval: fused projections / epilogues (False: one launch per op, as the train-mode value path)
     fused_stages = True      # eval, the shipped shape: everything behind the E projection in ONE launch (sn_transformer_net_fused_f32)
@@ -1121,6 +1125,21 @@ class TransformerNet(_DGLNet):
                                     [BatchedTransformerLayer(hidden, out_dim, p["n_heads"], p["full_graph"], use_edge=True)])
         self.full_graph = bool(p["full_graph"])
         self._init_tail(p)
+
+    FULL_GRAPH_INPUTS = ("edges", "bonds")
+
+    @property
+    def full_graph_input(self):
+        """"edges" | "bonds": what a full_graph=True net's forward takes (class docstring)."""
+        return self.__dict__.get("_full_graph_input", "edges")
+
+    @full_graph_input.setter
+    def full_graph_input(self, form):
+        if form not in self.FULL_GRAPH_INPUTS:
+            raise ValueError(f"TransformerNet.full_graph_input: {form!r} (one of {', '.join(self.FULL_GRAPH_INPUTS)})")
+        if not self.full_graph:
+            raise ValueError("TransformerNet.full_graph_input belongs to a full_graph=True net: the sparse net attends over the bonds only")
+        self.__dict__["_full_graph_input"] = form
 
     def _stage(self, g):
         if self.full_graph:                  # full-graph nets take the layer path: the one-launch stage kernel has no fake-pair form
@@ -1153,7 +1172,7 @@ class TransformerNet(_DGLNet):
 
     def forward(self, g, h, p, e, snorm_n=None):
         if self.full_graph:
-            return self._forward_full(g, h, p, e)
+            return self._forward_bonds(g, h, p, e) if self.full_graph_input == "bonds" else self._forward_full(g, h, p, e)
         pe, N, hidx, p, train, grad = self._prologue(g, h, p)
         eidx = e.long().reshape(-1)
         if grad:
@@ -1271,39 +1290,9 @@ class TransformerNet(_DGLNet):
             hg = self._forward_full_grad(ops.build_plan(batch, ei, B, 0), batch, ei, B, hidx, p, codes, status)
         else:
             plan = cached_plan(g, N)
-            with torch.no_grad():
-                snap = self._drop_snap(train, h.device)
-                x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)
-                if not train and self._fusable():
-                    fz = self._full_eval()
-                    for li, L in enumerate(self.layers):
-                        d = L.out_channels
-                        P5 = ops.masked_linear(x, fz["proj"][li])                 # [N, 5d] = Q | K | V | Q_2 | K_2, read in place
-                        Q, K, V, Q2, K2 = (P5[:, i * d:(i + 1) * d] for i in range(5))
-                        Tr, Tf = fz["tab"][li]
-                        a = ops.full_attention(Q, K, V, Q2, K2, Tr, Tf, codes, L.gamma.detach(), plan, L.num_heads, status=status)
-                        s1, s2 = self._bn(L.batch_norm1_h, False), self._bn(L.batch_norm2_h, False)
-                        x1 = ops.masked_linear(a, self._pk(L.O_h), residual=x, residual_pre=True, scale=s1.scale, shift=s1.shift)
-                        f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
-                        x = ops.masked_linear(f, self._pk(L.FFN_h_layer2), residual=x1, residual_pre=True, scale=s2.scale, shift=s2.shift)
-                else:
-                    emb = self.embedding_e.weight.detach().float().contiguous()
-                    for li, L in enumerate(self.layers):
-                        A = L.attention_h
-                        Q, K, V, Q2, K2 = (ops.masked_linear(x, self._pk(getattr(A, n))) for n in ("Q", "K", "V", "Q_2", "K_2"))
-                        Tr, Tf = ops.masked_linear(emb, self._pk(A.E)), ops.masked_linear(emb, self._pk(A.E_2))
-                        a = ops.full_attention(Q, K, V, Q2, K2, Tr, Tf, codes, L.gamma.detach(), plan, L.num_heads, status=status)
-                        pd = L.dropout if train else 0.0
-                        if pd:
-                            a = ops.dropout(a, pd, snap, 1 + 2 * li)
-                        o = ops.masked_linear(a, self._pk(L.O_h))
-                        x1 = self._bn_res(o, x, L.batch_norm1_h, train)
-                        f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
-                        if pd:
-                            f = ops.dropout(f, pd, snap, 2 + 2 * li)
-                        f = ops.masked_linear(f, self._pk(L.FFN_h_layer2))
-                        x = self._bn_res(f, x1, L.batch_norm2_h, train)
-                hg = self._readout(x, plan)
+            attend = lambda Q, K, V, Q2, K2, Tr, Tf, L: ops.full_attention(Q, K, V, Q2, K2, Tr, Tf, codes, L.gamma.detach(), plan,      # noqa: E731
+                                                                           L.num_heads, status=status)
+            x, hg = self._full_value(plan, hidx, p, train, h.device, attend)
             self._h_last = x
         if ops.deferring():
             ops.defer("embed", status)
@@ -1316,8 +1305,51 @@ class TransformerNet(_DGLNet):
         """Differentiable train-mode forward of a full-graph net: AG.full_attention's adjoint (sn_full_attention_bwd_f32) hands back the
         gradients of the five projections, of the two class tables — which reach E.weight, E_2.weight and embedding_e.weight through
         the [C, d] Linears that made them — and of gamma."""
-        vN, _, vB, k1 = _bucket_rows(self)          # (all rows valid: DGLBucketedStep refuses a full-graph net)
         rplan = ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
+        attend = lambda Q, K, V, Q2, K2, Tr, Tf, L: AG.full_attention(Q, K, V, Q2, K2, Tr, Tf, L.gamma, codes, plan, rplan, L.num_heads,     # noqa: E731
+                                                                      status)
+        return self._full_grad(plan, hidx, p, attend)
+
+    def _full_value(self, plan, hidx, p, train, dev, attend):
+        """The value paths of a full-graph net (eval with its cached packed projections, train mode) around `attend`, the form's
+        attention launch -> (x, hg)."""
+        with torch.no_grad():
+            snap = self._drop_snap(train, dev)
+            x = self._encode(ops.embedding_sum(hidx, [self.embedding_h.weight]), p, snap)
+            if not train and self._fusable():
+                fz = self._full_eval()
+                for li, L in enumerate(self.layers):
+                    d = L.out_channels
+                    P5 = ops.masked_linear(x, fz["proj"][li])                 # [N, 5d] = Q | K | V | Q_2 | K_2, read in place
+                    Q, K, V, Q2, K2 = (P5[:, i * d:(i + 1) * d] for i in range(5))
+                    Tr, Tf = fz["tab"][li]
+                    a = attend(Q, K, V, Q2, K2, Tr, Tf, L)
+                    s1, s2 = self._bn(L.batch_norm1_h, False), self._bn(L.batch_norm2_h, False)
+                    x1 = ops.masked_linear(a, self._pk(L.O_h), residual=x, residual_pre=True, scale=s1.scale, shift=s1.shift)
+                    f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
+                    x = ops.masked_linear(f, self._pk(L.FFN_h_layer2), residual=x1, residual_pre=True, scale=s2.scale, shift=s2.shift)
+            else:
+                emb = self.embedding_e.weight.detach().float().contiguous()
+                for li, L in enumerate(self.layers):
+                    A = L.attention_h
+                    Q, K, V, Q2, K2 = (ops.masked_linear(x, self._pk(getattr(A, n))) for n in ("Q", "K", "V", "Q_2", "K_2"))
+                    Tr, Tf = ops.masked_linear(emb, self._pk(A.E)), ops.masked_linear(emb, self._pk(A.E_2))
+                    a = attend(Q, K, V, Q2, K2, Tr, Tf, L)
+                    pd = L.dropout if train else 0.0
+                    if pd:
+                        a = ops.dropout(a, pd, snap, 1 + 2 * li)
+                    o = ops.masked_linear(a, self._pk(L.O_h))
+                    x1 = self._bn_res(o, x, L.batch_norm1_h, train)
+                    f = ops.masked_linear(x1, self._pk(L.FFN_h_layer1), relu=True)
+                    if pd:
+                        f = ops.dropout(f, pd, snap, 2 + 2 * li)
+                    f = ops.masked_linear(f, self._pk(L.FFN_h_layer2))
+                    x = self._bn_res(f, x1, L.batch_norm2_h, train)
+            return x, self._readout(x, plan)
+
+    def _full_grad(self, plan, hidx, p, attend):
+        """The differentiable train-mode layers of a full-graph net around `attend`, the form's attention node."""
+        vN, _, vB, k1 = _bucket_rows(self)          # (a padded batch: the bond form under DGLBucketedStep)
         snap = self._drop_snap(True, hidx.device)
         x = self._encode_grad(hidx, p, vN, k1, snap)
         emb = self.embedding_e.weight
@@ -1325,7 +1357,7 @@ class TransformerNet(_DGLNet):
             A = L.attention_h
             Q, K, V, Q2, K2 = (AG.linear(x, getattr(A, n).weight, None, vN, k1) for n in ("Q", "K", "V", "Q_2", "K_2"))
             Tr, Tf = AG.linear(emb, A.E.weight), AG.linear(emb, A.E_2.weight)
-            a = AG.full_attention(Q, K, V, Q2, K2, Tr, Tf, L.gamma, codes, plan, rplan, L.num_heads, status)
+            a = attend(Q, K, V, Q2, K2, Tr, Tf, L)
             pd = L.dropout
             if pd:
                 a = AG.dropout(a, pd, snap, 1 + 2 * li)
@@ -1338,6 +1370,32 @@ class TransformerNet(_DGLNet):
             x = AG.bn_act(AG.masked_add(f, x1, vN, k1), L.batch_norm2_h, vN, k1, relu=False)
         self._h_last = x.detach()
         return self._readout_grad(x, plan, vB, k1)
+
+    # ------------------------------------------------------------------ full_graph True from the molecular graph (full_graph_input "bonds")
+    def _forward_bonds(self, g, h, p, e):
+        """The full-graph net on the MOLECULAR graph and its bond classes [E]: the layers of `_forward_full` around
+        sn_bond_full_attention_f32 (its adjoint: sn_bond_full_attention_bwd_f32, no reverse plan).  Row validity of a padded batch from
+        `_bucket_rows`: the spare graph is skipped, padding edges are no bonds.  One two-word status for all layers (a bond class
+        outside embedding_e; a self loop or a repeated bond), handed to ops.defer_status where one collects — no host read then."""
+        pe, N, hidx, p, train, grad = self._prologue(g, h, p)
+        e = e.long().reshape(-1)
+        status = torch.zeros(2, dtype=torch.int32, device=h.device)
+        _, vE, vB, _ = _bucket_rows(self)
+        if grad:
+            batch, ei, B = self._plan(g, N)
+            plan = ops.build_plan(batch, ei, B, 0)
+            attend = lambda Q, K, V, Q2, K2, Tr, Tf, L: AG.bond_full_attention(Q, K, V, Q2, K2, Tr, Tf, L.gamma, e, plan, L.num_heads,     # noqa: E731
+                                                                               status, vB, vE)
+            hg = self._full_grad(plan, hidx, p, attend)
+        else:
+            plan = cached_plan(g, N)
+            attend = lambda Q, K, V, Q2, K2, Tr, Tf, L: ops.bond_full_attention(Q, K, V, Q2, K2, Tr, Tf, e, L.gamma.detach(), plan,     # noqa: E731
+                                                                                L.num_heads, status=status, graph_valid=vB, edge_valid=vE)
+            x, hg = self._full_value(plan, hidx, p, train, h.device, attend)
+            self._h_last = x
+        ops.check_bond_status(status)
+        self.g = g
+        return hg, g
 
 
 # ---------------------------------------------------------------------------------------------------------------

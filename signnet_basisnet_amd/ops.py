@@ -984,7 +984,7 @@ def _full_attention_blocks(fn, Q, K, V, Q2, K2):
     return N, d, ld
 
 
-def _full_attention_check(fn, d, heads, T_real, T_fake, codes, gamma, plan):
+def _full_attention_tables(fn, d, heads, T_real, T_fake, gamma):
     if d % heads or d // heads > 32:
         raise ValueError(f"{fn}: heads must divide the width and the head width must be <= 32")
     T_real, T_fake = _f32c(T_real, "T_real"), _f32c(T_fake, "T_fake")
@@ -993,10 +993,15 @@ def _full_attention_check(fn, d, heads, T_real, T_fake, codes, gamma, plan):
         raise ValueError(f"{fn}: T_real and T_fake must both be [C, heads*dk]")
     if not 1 <= Cc <= FULL_ATTENTION_MAX_CLASSES:
         raise ValueError(f"{fn}: {Cc} edge classes not in [1, {FULL_ATTENTION_MAX_CLASSES}]")
-    if codes.dtype != torch.int32 or not codes.is_contiguous() or codes.numel() != plan.E:
-        raise ValueError(f"{fn}: codes must be a contiguous int32 vector with one entry (2 * class + real) per edge of the plan")
     if gamma.dtype != torch.float32 or gamma.numel() != 1 or not gamma.is_cuda:
         raise ValueError(f"{fn}: gamma must be one float32 in device memory")
+    return T_real, T_fake, Cc
+
+
+def _full_attention_check(fn, d, heads, T_real, T_fake, codes, gamma, plan):
+    T_real, T_fake, Cc = _full_attention_tables(fn, d, heads, T_real, T_fake, gamma)
+    if codes.dtype != torch.int32 or not codes.is_contiguous() or codes.numel() != plan.E:
+        raise ValueError(f"{fn}: codes must be a contiguous int32 vector with one entry (2 * class + real) per edge of the plan")
     return T_real, T_fake, Cc
 
 
@@ -1095,6 +1100,94 @@ def make_full_graph(g, e, status=None):
     full.edata["real"] = buf[2]
     full.edata["feat"] = buf[3]
     return full, buf[3]
+
+
+BOND_GRAPH_ERROR = ("bond_full_attention: the bond graph has a self loop, a repeated (u, v) edge or a bond between two graphs — the "
+                    "reference's assignment of the real edges (data/molecules.py:233-234) gives none a meaning")
+
+
+def bond_attention_staged_nodes(dk: int, bwd: bool = False) -> int:
+    """The largest graph whose rows and pair table sn_bond_full_attention_f32 (bwd: its adjoint) stage in LDS for head width dk; a
+    larger graph takes the kernels' global-memory path (same arithmetic, same bits)."""
+    return int(lib().sn_bond_full_attention_staged_nodes(int(dk), int(bool(bwd))))
+
+
+def _bond_attention_check(fn, d, heads, T_real, T_fake, e, gamma, plan, graph_valid, edge_valid):
+    T_real, T_fake, Cc = _full_attention_tables(fn, d, heads, T_real, T_fake, gamma)
+    if e.dtype != torch.int64 or not e.is_cuda or e.numel() != plan.E:
+        raise ValueError(f"{fn}: e must be the int64 bond classes in device memory, one per edge of the plan")
+    for v, rows, n in ((graph_valid, plan.B, "graph_valid"), (edge_valid, plan.E, "edge_valid")):
+        if v is not None and (v.dtype != torch.int32 or not v.is_cuda or not v.is_contiguous() or v.numel() < rows):
+            raise ValueError(f"{fn}: {n} must be a contiguous int32 0/1 vector in device memory with an entry per row")
+    return T_real, T_fake, Cc, e.reshape(-1).contiguous()
+
+
+def bond_full_attention(Q, K, V, Q2, K2, T_real, T_fake, e, gamma, plan: GraphPlan, heads: int, status=None, graph_valid=None,
+                        edge_valid=None, want_den=False):
+    """Full-graph attention computed from the BOND graph (sn_bond_full_attention_f32) -> [N, heads*dk]: what full_attention gives on
+    make_full_graph's output, without its edge list.  plan: cached_plan of the molecular graph; e: its bond classes, int64 [E], read in
+    place; T_*, gamma and the five blocks as full_attention.  graph_valid / edge_valid: int32 0 / 1 (a padded batch): an invalid graph
+    gets zeros and raises no flag, an invalid edge is not a bond.  status: device int32 [2] — [0] a bond class outside [0, C), [1] a self
+    loop / repeated edge (make_full_graph's flags); with status=None the op checks both itself — one host sync, or ops.defer_status —
+    and raises IndexError / ValueError."""
+    require_cuda(Q, e, gamma)
+    N, d, ld = _full_attention_blocks("bond_full_attention", Q, K, V, Q2, K2)
+    if N != plan.N:
+        raise ValueError("bond_full_attention: the blocks must have one row per node of the plan")
+    T_real, T_fake, Cc, e = _bond_attention_check("bond_full_attention", d, heads, T_real, T_fake, e, gamma, plan, graph_valid, edge_valid)
+    out = torch.empty(N, d, dtype=torch.float32, device=Q.device)
+    den = torch.empty(N, int(heads), dtype=torch.float32, device=Q.device)
+    own = status is None
+    if own:
+        status = torch.zeros(2, dtype=torch.int32, device=Q.device)
+    elif status.dtype != torch.int32 or status.numel() < 2 or not status.is_contiguous():
+        raise ValueError("bond_full_attention: status must be a contiguous int32 [2] in device memory")
+    with _span("sn_bond_full_attention_f32"):
+        check(lib().sn_bond_full_attention_f32(ptr(Q), ptr(K), ptr(V), ptr(Q2), ptr(K2), ld, ptr(T_real), ptr(T_fake), Cc, ptr(e), ptr(gamma), N,
+                                               plan.B, plan.E, int(heads), d // heads, ptr(plan.graph_ptr), ptr(plan.rowptr), ptr(plan.col),
+                                               ptr(plan.eperm), ptr(graph_valid), ptr(edge_valid), ptr(out), ptr(den), ptr(status), stream()),
+              "sn_bond_full_attention_f32")
+    if own:
+        check_bond_status(status)
+    return (out, den) if want_den else out
+
+
+def check_bond_status(status):
+    """The two words of a bond_full_attention status: handed to ops.defer_status where one collects, else read now (one host wait)."""
+    if _DEFERRED_STATUS is not None:
+        defer("embed", status[0:1])
+        defer("flag", status[1:2], BOND_GRAPH_ERROR)
+        return
+    words = status.tolist()
+    if words[0]:
+        raise IndexError(EMBEDDING_INDEX_ERROR)
+    if words[1]:
+        raise ValueError(BOND_GRAPH_ERROR)
+
+
+def bond_full_attention_bwd(Q, K, V, Q2, K2, T_real, T_fake, e, gamma, out, den, dout, plan: GraphPlan, heads: int, graph_valid=None,
+                            edge_valid=None):
+    """Adjoint of bond_full_attention (sn_bond_full_attention_bwd_f32) -> dQ, dK, dV, dQ_2, dK_2 [N, heads*dk], dT_real, dT_fake
+    [C, heads*dk], dgamma [1].  No reverse plan, no per-pair array; no atomics: bit-identical on repeated calls."""
+    require_cuda(Q, dout)
+    N, d, ld = _full_attention_blocks("bond_full_attention_bwd", Q, K, V, Q2, K2)
+    if N != plan.N:
+        raise ValueError("bond_full_attention_bwd: the blocks must have one row per node of the plan")
+    T_real, T_fake, Cc, e = _bond_attention_check("bond_full_attention_bwd", d, heads, T_real, T_fake, e, gamma, plan, graph_valid, edge_valid)
+    out, den, dout = _f32c(out, "out"), _f32c(den, "den"), _f32c(dout, "dout")
+    dev = Q.device
+    new = lambda r: torch.empty(r, d, dtype=torch.float32, device=dev)
+    dQ, dK, dV, dQ2, dK2, dTr, dTf = new(N), new(N), new(N), new(N), new(N), new(Cc), new(Cc)
+    dgamma = torch.empty(1, dtype=torch.float32, device=dev)
+    scratch = torch.empty(max(int(lib().sn_bond_full_attention_bwd_scratch_floats(N, plan.B, int(heads), d // heads, Cc)), 2),
+                          dtype=torch.float32, device=dev)
+    with _span("sn_bond_full_attention_bwd_f32"):
+        check(lib().sn_bond_full_attention_bwd_f32(ptr(Q), ptr(K), ptr(V), ptr(Q2), ptr(K2), ld, ptr(T_real), ptr(T_fake), Cc, ptr(e), ptr(gamma),
+                                                   ptr(out), ptr(den), ptr(dout), N, plan.B, plan.E, int(heads), d // heads, ptr(plan.graph_ptr),
+                                                   ptr(plan.rowptr), ptr(plan.col), ptr(plan.eperm), ptr(graph_valid), ptr(edge_valid), ptr(dQ),
+                                                   ptr(dK), ptr(dV), ptr(dQ2), ptr(dK2), ptr(dTr), ptr(dTf), ptr(dgamma), ptr(scratch), stream()),
+              "sn_bond_full_attention_bwd_f32")
+    return dQ, dK, dV, dQ2, dK2, dTr, dTf, dgamma
 
 
 def gat_aggregate(feat, attn_l, attn_r, bias, plan: GraphPlan, heads: int, negative_slope=0.2, relu=True, want_lse=False):

@@ -10,6 +10,9 @@ from __future__ import annotations
 import torch
 
 
+_FULL_GRAPH_REFUSAL = "GraphedDGLForward does not carry the edge flag edata['real'] of a full_graph=True net into its static buffers"
+
+
 class GraphedDGLForward:
     """handle_lap + base network of the DGL tree (GraphPrediction/train/train_ZINC_graph_regression.py:13-51,109-112) in eval mode as
     ONE HIP-graph launch — the net's lap_method for pe_init 'lap_pe' (sign_inv_net, or the recorded sn_lap_pe_transform_f32 launch of
@@ -34,15 +37,20 @@ class GraphedDGLForward:
     `load_state_dict()` — anything that drops those caches — would free under the recorded graph, while the embedding tables are read
     in place.  This object therefore keeps the caches of the capture alive and remembers the version counter of every parameter and
     buffer: a replay after the net was switched to another mode, moved, re-loaded or trained in between raises instead of returning
-    scores of freed or half-updated weights — build a new GraphedDGLForward then."""
+    scores of freed or half-updated weights — build a new GraphedDGLForward then.
+
+    A full_graph=True TransformerNet is recorded in its bond form only (net.full_graph_input = "bonds": g is the molecular graph, e its
+    bond classes); the form is remembered and a call after it changed raises."""
 
     def __init__(self, net, g, h, pos_enc, e=None, snorm_n=None, warmup=2):
         from .dgl_deepsigns import Graph
-        from .train_graph import GraphedForward
+        from .train_graph import GraphedForward, carries_real_flag
         if net.training:
             raise ValueError("GraphedDGLForward records the eval forward: call net.eval() first")
-        if getattr(net, "full_graph", False):
-            raise NotImplementedError("GraphedDGLForward does not carry the edge flag edata['real'] of a full_graph=True net into its static buffers")
+        # (a full-graph net in its bond form takes the molecular graph, which the static buffers hold; the form is recorded)
+        self._full_form = getattr(net, "full_graph_input", "edges") if getattr(net, "full_graph", False) else None
+        if self._full_form not in (None, "bonds") or (self._full_form is not None and carries_real_flag(g)):
+            raise NotImplementedError(_FULL_GRAPH_REFUSAL)
         dev = h.device
         src, dst = g.edges()
         bnn = torch.as_tensor(g.batch_num_nodes())
@@ -130,6 +138,14 @@ class GraphedDGLForward:
 
     def __call__(self, g=None, h=None, pos_enc=None, e=None, snorm_n=None):
         self._assert_fresh()
+        if self._full_form is not None:
+            from .train_graph import carries_real_flag
+            now = getattr(self.net, "full_graph_input", "edges")
+            if now != self._full_form:
+                raise RuntimeError(f"GraphedDGLForward: the net's full_graph_input changed from {self._full_form!r} to {now!r} since the "
+                                   "forward was recorded: record a new GraphedDGLForward")
+            if g is not None and carries_real_flag(g):
+                raise NotImplementedError(_FULL_GRAPH_REFUSAL)
         todo = []
 
         def put(dst, src, what):

@@ -586,6 +586,18 @@ class _DGLBucketCapture:
         ops.raise_deferred(self._words)
 
 
+_FULL_GRAPH_REFUSAL = "DGLBucketedStep does not carry the edge flag edata['real'] of a full_graph=True net through its pack launch"
+
+
+def carries_real_flag(g):
+    """Whether a graph object holds edata['real']: the complete graph of ops.make_full_graph (the edge form of a full-graph net)."""
+    ed = getattr(g, "edata", None)
+    try:
+        return ed is not None and "real" in ed
+    except TypeError:
+        return False
+
+
 class DGLBucketedStep(_CaptureLRU):
     """The captured training step of the DGL tree's loop (GraphPrediction/train/train_ZINC_graph_regression.py:54-88): batches of any
     shape (N nodes, E edges, at most `max_graphs` graphs) are padded into fixed-capacity buffers and run through a step captured ONCE
@@ -594,7 +606,8 @@ class DGLBucketedStep(_CaptureLRU):
         step = DGLBucketedStep(net, flat_adam, max_graphs=128, granule=dict(N=256, E=512), max_captures=4)
         loss = step.step(g, h, p, e, snorm_n, targets)      # p: the raw pos_enc [N, pos_enc_dim]; e / snorm_n None where unused
 
-    `net`: GINNet, GatedGCNNet, GATNet, PNANet or TransformerNet of dgl_nets — pe_init 'lap_pe' with lap_method 'sign_inv' (and its
+    `net`: GINNet, GatedGCNNet, GATNet, PNANet or TransformerNet of dgl_nets (a full_graph=True TransformerNet in its bond form only —
+    net.full_graph_input = "bonds": `g` is then the molecular graph, the spare graph of a bucket is skipped by the attention) — pe_init 'lap_pe' with lap_method 'sign_inv' (and its
     sign_inv_net: GINDeepSigns / MaskedGINDeepSigns), 'sign_flip', 'abs_val', 'canonical' or 'none', or pe_init 'no_pe' (p may then be
     None in step(); step_from takes a store of any pos_enc width, gathered and ignored).  `flip_rng` ('sign_flip'): "host" — the k
     uniforms of a step are torch.rand(k) of the CPU default generator, the reference's sequence — or "device" —
@@ -613,8 +626,11 @@ class DGLBucketedStep(_CaptureLRU):
     def __init__(self, net, optimizer, max_graphs=128, granule=None, max_captures=4, warmup=2, flip_rng="host"):
         from . import dgl_nets
         from .optim import FlatAdam
-        if getattr(net, "full_graph", False):
-            raise NotImplementedError("DGLBucketedStep does not carry the edge flag edata['real'] of a full_graph=True net through its pack launch")
+        # (a full-graph net in its bond form takes the molecular graph: an ordinary DGL batch.  The form is recorded: the captured
+        #  launches are those of the form the net had here)
+        self._full_form = getattr(net, "full_graph_input", "edges") if getattr(net, "full_graph", False) else None
+        if self._full_form not in (None, "bonds"):
+            raise NotImplementedError(_FULL_GRAPH_REFUSAL)
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("DGLBucketedStep needs optim.FlatAdam (static flat parameter / gradient buffers)")
         if not isinstance(net, tuple(getattr(dgl_nets, n) for n in _DGL_NETS)):
@@ -655,6 +671,17 @@ class DGLBucketedStep(_CaptureLRU):
             z = self._zeros = torch.zeros(max(N, self.granule["N"]), self.K, dtype=torch.float32, device=dev)
         return z[:N]
 
+    def _check_form(self, g=None):
+        """A full-graph net keeps the input form it was given to this object with, and its batches are molecular graphs."""
+        if self._full_form is None:
+            return
+        now = getattr(self.model, "full_graph_input", "edges")
+        if now != self._full_form:
+            raise RuntimeError(f"DGLBucketedStep: the net's full_graph_input changed from {self._full_form!r} to {now!r} since this step was "
+                               "built: build a new DGLBucketedStep")
+        if g is not None and carries_real_flag(g):
+            raise NotImplementedError(_FULL_GRAPH_REFUSAL)
+
     def _num_graphs(self, g):
         B = int(g.batch_num_nodes().numel())
         if B > self.max_graphs:
@@ -671,6 +698,7 @@ class DGLBucketedStep(_CaptureLRU):
     def step(self, g, h, p, e, snorm_n, targets, bucket=None):
         """One training step on a batch (targets [num_graphs, 1]): returns the loss (a device scalar, rewritten by the next step of the
         same bucket).  `bucket`: explicit capacities (DGLBucket / (N_cap, E_cap)) instead of the granule rounding."""
+        self._check_form(g)
         self._num_graphs(g)
         b = self.bucket_of(g, h) if bucket is None else DGLBucket(*bucket)
         N = int(h.shape[0])
@@ -702,6 +730,7 @@ class DGLBucketedStep(_CaptureLRU):
         sn_store_gather launch in place of the pack launch); same LRU, capture, replay and check()."""
         if not getattr(store, "dgl", False):
             raise TypeError("DGLBucketedStep.step_from needs a data.DGLGraphStore")
+        self._check_form()
         if store.K != self.K:
             if self.lap_method is not None or self._lru:
                 raise ValueError(f"DGLBucketedStep: the store holds pos_enc of {store.K} columns, the net takes {self.K}" +
