@@ -150,6 +150,10 @@ typedef struct sn_bucket_pack_args {
   int64_t N_cap, E_cap, B_cap, S_cap;
 } sn_bucket_pack_args;
 int sn_bucket_pack(const sn_bucket_pack_args* args, void* stream);
+/* The same launch for a batch WITHOUT eigen data (the plain GNN baselines and NetGINE read none): eigen_values may be NULL, the
+ * capacity buffer eigen_values_out is then zero-filled; eigen_vectors may be NULL with S = 0 (S > 0 without a source is SN_ERR_ARG),
+ * eigen_vectors_out [S_cap] is zero-filled and counts[3] = 0.  Same argument struct, same padding convention. */
+int sn_bucket_pack_plain(const sn_bucket_pack_args* args, void* stream);
 /* The same for a DGL batch (train_graph.DGLBucketedStep: the loop body of GraphPrediction/train/train_ZINC_graph_regression.py:60-82,
  * one batch of main_ZINC_graph_regression.py's loader per step), same padding convention.  Copies src / dst [E], the atom ids h [N],
  * the bond ids e [E] (e_out NULL: none), pos_enc p [N, K], snorm_n [N] (snorm_n_out NULL: none) and the targets [B] into [E_cap],
@@ -1261,6 +1265,17 @@ int sn_gat_conv_bwd_f32(const float* feat, const float* att_l, const float* att_
                         const float* dout, int64_t N, int heads, int C, float negative_slope, int act, const int32_t* rowptr,
                         const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t, int64_t nnz, float* dfeat, float* part,
                         double* work, void* stream);
+/* The operator pair of sn_gat_conv_f32 / _bwd_f32 built on the device, with shapes that depend on capacities only (a captured step:
+ * no boolean indexing, no argsort, no host read).  Input: the destination-sorted CSR of sn_batch_plan for a batch of N nodes and E edge
+ * slots (rowptr / col, rows in edge-id order) and the one of the FLIPPED edge list (rowptr_t / col_t).  Output, in buffers of the same
+ * sizes (rowptr_out, rowptr_t_out: [N + 1]; col_out, col_t_out: [E]): both CSRs without the entries col == row (the input's self loops;
+ * the padding edges of sn_bucket_pack are self loops and vanish too), multi-edges kept, every row ordered by (source, input position).
+ * The live entry count is rowptr_out[N], a device value: pass nnz = E to the attention launches, which take their ranges from rowptr
+ * alone and use nnz as a capacity.  col_out beyond the live entries is zero-filled.  Entries of col outside [0, N) are dropped, rowptr
+ * is clamped to [0, E].  Any in-degree (a row ranks its own entries); one owner per output element, no atomics: identical bytes on
+ * every call.  Three launches for both operators. */
+int sn_csr_drop_loops(int64_t N, int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t,
+                      int32_t* rowptr_out, int32_t* col_out, int32_t* rowptr_t_out, int32_t* col_t_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The message side of SimplifiedPNAConv with aggregators=['mean'] (GINESignNetPyG/core/model_utils/pyg_gnn_wrapper.py:53-106; built by
@@ -1303,6 +1318,21 @@ int sn_spna_bwd_f32(const float* A, int64_t lda, const float* B, int64_t ldb, co
                     const int32_t* eperm_t, const float* dr, int64_t lddr, const float* scale, const float* shift,
                     const float* state, const float* gamma, float* dA, int64_t ldda, float* dB, int64_t lddb, float* dQ,
                     int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream);
+/* The train-mode launches over a PADDED batch (train_graph.BucketedStep: N, E are the capacities of the bucket).  node_valid: the 0/1
+ * vector of sn_bucket_pack [N]; counts: its device count block (counts[1] = the valid edge rows).  A node with node_valid 0 is left out
+ * with all its in-edges (padding edges end in padding nodes only): they enter no statistic and no adjoint sum.  The row count of the
+ * biased variance, of the unbiased running variance, of count[0] and of the two adjoint means is counts[1], read on the device.  The
+ * adjoint writes zero dQ rows for the in-edges of invalid nodes and zero dA rows for those nodes (their dB rows sum zero dQ rows).
+ * sn_spna_mean_f32 runs unchanged between the two: the rows it writes for padding nodes are finite and masked by the caller. */
+int sn_spna_stats_masked_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                             int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* node_valid,
+                             const int32_t* counts, const float* gamma, const float* beta, float eps, float momentum,
+                             float* running_mean, float* running_var, float* state, float* count, float* work, void* stream);
+int sn_spna_bwd_masked_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                           int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* rowptr_t,
+                           const int32_t* eperm_t, const int32_t* node_valid, const int32_t* counts, const float* dr, int64_t lddr,
+                           const float* state, const float* gamma, float* dA, int64_t ldda, float* dB, int64_t lddb, float* dQ,
+                           int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The propagation of torch_geometric's GCNConv (gcn_norm, add_self_loops=True, unit edge weights) behind its Linear, which GNN builds

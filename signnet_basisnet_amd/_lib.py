@@ -31,6 +31,7 @@ SIGNATURES = {
     "sn_batch_plan_early_supported": [_l, _l, _l],                # (returns 0 / 1, not a status)
     "sn_pack_eig_f32": [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p],
     "sn_bucket_pack": [_p, _p],
+    "sn_bucket_pack_plain": [_p, _p],
     "sn_bucket_pack_dgl": [_p, _p],
     "sn_store_gather": [_p, _p],
     "sn_store_gather_max_graphs": [],                    # (returns the limit, not a status)
@@ -151,12 +152,16 @@ SIGNATURES = {
     "sn_gat_conv_bwd_blocks": [_l, _i, _i],
     "sn_gat_conv_f32": [_p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _l, _p, _p, _p],
     "sn_gat_conv_bwd_f32": [_p, _p, _p, _p, _p, _p, _l, _i, _i, _f, _i, _p, _p, _p, _p, _l, _p, _p, _p, _p],
+    "sn_csr_drop_loops": [_l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_spna_blocks": [_l, _i],                          # (the two below return a count / 0 or 1, not a status)
     "sn_spna_vector_path": [_i, _l, _l, _l, _l, _p, _p, _p, _p],
     "sn_spna_stats_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p],
     "sn_spna_mean_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p, _l, _p],
     "sn_spna_bwd_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _l, _p, _l, _p, _l, _p, _p,
                         _p, _p],
+    "sn_spna_stats_masked_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p],
+    "sn_spna_bwd_masked_f32": [_p, _l, _p, _l, _p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _l, _p, _l, _p, _l,
+                               _p, _p, _p, _p],
     "sn_gcn_pyg_coef_f32": [_l, _l, _p, _p, _p, _p],
     "sn_gcn_pyg_propagate_f32": [_p, _l, _l, _i, _l, _p, _p, _p, _p, _l, _p],
     "sn_dropout_f32": [_p, _i, _l, _i, C.c_uint32, _f, _p, C.c_uint32, _l, _p, _i, _p, _i, _p],

@@ -1057,34 +1057,40 @@ def gat_conv(feat, att_l, att_r, bias, graph, heads, act="elu", negative_slope=0
 # ----------------------------------------------------------------------------- SimplifiedPNAConv's message side (csrc/simplified_pna.hip)
 class _SpnaMean(Function):
     """r = mean over in-edges of relu(BatchNorm1d_train(a[dst] + b[src] + q[e])) with ab = [a | b] one [N, 2C] block: the statistics
-    launch and the mean launch forward, ops.spna_bwd backward (z recomputed; dQ is the one [E, C] temporary)."""
+    launch and the mean launch forward, ops.spna_bwd backward (z recomputed; dQ is the one [E, C] temporary).  `mask` = (node_valid,
+    counts) of a padded batch: the masked statistics and adjoint launches (padding rows of r are finite; the caller masks them)."""
 
     @staticmethod
-    def forward(ctx, ab, q, gamma, beta, bn, plan, rplan):
+    def forward(ctx, ab, q, gamma, beta, bn, plan, rplan, mask=None):
         ab, q = _c(ab.detach()), _c(q.detach())
         Cc = q.shape[1]
         a, b = ab[:, :Cc], ab[:, Cc:]
-        state, _ = ops.spna_stats(a, b, q, plan, bn)
+        nv, cnt = mask if mask is not None else (None, None)
+        state, _ = ops.spna_stats(a, b, q, plan, bn, nv, cnt)
         r = ops.spna_mean(a, b, q, plan, state[3], state[4])
         ctx.save_for_backward(ab, q, state, gamma)
-        ctx.meta = (plan, rplan, gamma is not None)
+        ctx.meta = (plan, rplan, gamma is not None, nv, cnt)
         return r
 
     @staticmethod
     def backward(ctx, g):
         ab, q, state, gamma = ctx.saved_tensors
-        plan, rplan, affine = ctx.meta
+        plan, rplan, affine, nv, cnt = ctx.meta
         Cc = q.shape[1]
         dab = torch.empty_like(ab)
         dq = torch.empty_like(q)
         _, _, _, dg, db = ops.spna_bwd(ab[:, :Cc], ab[:, Cc:], q, plan, rplan, _c(g), state=state,
-                                       gamma=None if gamma is None else gamma.detach(), out=(dab[:, :Cc], dab[:, Cc:], dq))
-        return dab, dq, dg if affine else None, db if affine else None, None, None, None
+                                       gamma=None if gamma is None else gamma.detach(), out=(dab[:, :Cc], dab[:, Cc:], dq),
+                                       node_valid=nv, counts=cnt)
+        return dab, dq, dg if affine else None, db if affine else None, None, None, None, None
 
 
-def spna_mean(ab, q, bn, plan, rplan):
-    """Train mode, differentiable: [N, C] mean of relu(bn(z_e)) over each node's in-edges; moves bn's running statistics."""
-    return _SpnaMean.apply(ab, q, bn.weight, bn.bias, bn, plan, rplan)
+def spna_mean(ab, q, bn, plan, rplan, node_valid=None, counts=None):
+    """Train mode, differentiable: [N, C] mean of relu(bn(z_e)) over each node's in-edges; moves bn's running statistics.
+    node_valid / counts: a padded batch (ops.spna_stats)."""
+    if node_valid is None:
+        return _SpnaMean.apply(ab, q, bn.weight, bn.bias, bn, plan, rplan)
+    return _SpnaMean.apply(ab, q, bn.weight, bn.bias, bn, plan, rplan, (node_valid, counts))
 
 
 # ----------------------------------------------------------------------------- PyG's GCNConv propagation (csrc/pyg_gcn.hip)

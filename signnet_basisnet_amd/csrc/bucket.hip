@@ -198,8 +198,12 @@ static int launch_pack(const PackTab& tb, void* stream, const char* who) {
   return SN_OK;
 }
 
-extern "C" int sn_bucket_pack(const sn_bucket_pack_args* a, void* stream) {
+// `plain`: a batch without eigen data (sn_bucket_pack_plain): eigen_values / eigen_vectors may be NULL, S must then be 0 and the two
+// capacity buffers are zero-filled (a NULL source is the constant 0 of add_seg).
+static int bucket_pack(const sn_bucket_pack_args* a, void* stream, bool plain) {
   SN_REQUIRE(a, "sn_bucket_pack: null args");
+  SN_REQUIRE(!plain || a->eigen_vectors || a->S == 0, "sn_bucket_pack_plain: S = %lld eigenvector entries without a source array",
+             (long long)a->S);
   const int64_t N = a->N, E = a->E, B = a->B, S = a->S, Nc = a->N_cap, Ec = a->E_cap, Bc = a->B_cap, Sc = a->S_cap;
   SN_REQUIRE(N >= 0 && E >= 0 && B >= 0 && S >= 0, "sn_bucket_pack: negative size");
   SN_REQUIRE(N < Nc && E <= Ec && B < Bc && S <= Sc, "sn_bucket_pack: batch (N %lld, E %lld, B %lld, S %lld) does not fit the bucket "
@@ -207,14 +211,14 @@ extern "C" int sn_bucket_pack(const sn_bucket_pack_args* a, void* stream) {
              (long long)Nc, (long long)Ec, (long long)Bc, (long long)Sc);
   SN_REQUIRE(Nc < (1ll << 31) && Ec < (1ll << 31) && Bc < (1ll << 31) && Sc < (1ll << 31), "sn_bucket_pack: capacities exceed int32");
   SN_REQUIRE(a->x_row_bytes >= 0 && a->edge_row_bytes >= 0 && a->target_row_bytes >= 0, "sn_bucket_pack: negative row size");
-  SN_REQUIRE((N == 0 || (a->batch && a->eigen_values)) && (E == 0 || a->edge_index) && (S == 0 || a->eigen_vectors) &&
+  SN_REQUIRE((N == 0 || (a->batch && (a->eigen_values || plain))) && (E == 0 || a->edge_index) && (S == 0 || a->eigen_vectors) &&
              (N == 0 || a->x_row_bytes == 0 || a->x) && (E == 0 || a->edge_row_bytes == 0 || a->edge_attr) &&
              (B == 0 || a->target_row_bytes == 0 || a->target),
              "sn_bucket_pack: null source array");
   SN_REQUIRE(a->batch_out && a->eigen_values_out && a->node_valid && a->graph_valid && a->counts && (Ec == 0 || (a->edge_index_out && a->edge_valid)),
              "sn_bucket_pack: null capacity buffer");
   PackTab tb{};
-  const char* who = "sn_bucket_pack";
+  const char* who = plain ? "sn_bucket_pack_plain" : "sn_bucket_pack";
   // padding edge i (0-based) is a self-loop on padding node N + i % (N_cap - N): spread over the padding nodes, never hundreds of
   // in-edges on one node (the aggregations walk a node's in-edges serially: one node with 250 self-loops was a 0.3 ms tail per step)
   const uint32_t pad_node = (uint32_t)N, pad_graph = (uint32_t)(Bc - 1);
@@ -238,6 +242,10 @@ extern "C" int sn_bucket_pack(const sn_bucket_pack_args* a, void* stream) {
   tb.cnt[3] = (int32_t)S;
   return launch_pack(tb, stream, who);
 }
+
+extern "C" int sn_bucket_pack(const sn_bucket_pack_args* a, void* stream) { return bucket_pack(a, stream, false); }
+
+extern "C" int sn_bucket_pack_plain(const sn_bucket_pack_args* a, void* stream) { return bucket_pack(a, stream, true); }
 
 extern "C" int sn_bucket_pack_dgl(const sn_bucket_pack_dgl_args* a, void* stream) {
   SN_REQUIRE(a, "sn_bucket_pack_dgl: null args");

@@ -37,6 +37,7 @@ struct Msg {                 // the operands of z_e
   const float* Q; int64_t ldq;
   int C; int64_t N; int64_t E;
   const int32_t* rowptr; const int32_t* col; const int32_t* eperm;
+  const int32_t* valid;      // masked forms: 0/1 per node, a node with 0 is left out with all its in-edges; NULL: every node counts
 };
 
 // A malformed batch is reported by the plan's own status word, and its arrays may then hold anything: the row range is clamped to the
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void k_spna_stats(Msg m, Cut cut, float* __res
     for (int64_t n = n0 + slot; n < n1; n += cut.slots) {
       int lo, hi;
       row_range(m.rowptr, n, m.E, lo, hi);
-      if (lo == hi) continue;
+      if (lo == hi || (m.valid && !m.valid[n])) continue;
       const Vec<V> a = Vec<V>::ld(m.A + n * m.lda + c);
       for (int e = lo; e < hi; ++e) {
         int64_t j, eid;
@@ -140,11 +141,13 @@ __global__ __launch_bounds__(256) void k_spna_stats(Msg m, Cut cut, float* __res
   }
 }
 
-// merge in block order; state[0..4][C] = mean, biased variance, rstd, scale, shift; count[0] = E; running statistics (unbiased variance)
+// merge in block order; state[0..4][C] = mean, biased variance, rstd, scale, shift; count[0] = E; running statistics (unbiased variance).
+// counts != NULL (masked form): the row count of both variances and of count[0] is the device count block's counts[1].
 __global__ __launch_bounds__(256) void k_spna_stats_finish(const float* __restrict__ part, int nblk, int C, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, float momentum,
                                                            float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                           float* __restrict__ state, float* __restrict__ count) {
+                                                           float* __restrict__ state, float* __restrict__ count,
+                                                           const int32_t* __restrict__ counts) {
   // a workgroup owns 16 columns; its 16 lanes per column merge 16 consecutive ranges of the partials, then lane 0 merges the 16 range
   // results in order: the serial chain is nblk / 16 + 16 merges instead of nblk (measured at 369 partials: the chain was the launch)
   __shared__ double sh[3][16][17];
@@ -162,6 +165,7 @@ __global__ __launch_bounds__(256) void k_spna_stats_finish(const float* __restri
   __syncthreads();
   if (c >= C || lane != 0) return;
   for (int l = 1; l < 16; ++l) chan(n, mu, m2, sh[0][l][cl], sh[1][l][cl], sh[2][l][cl]);
+  if (counts != nullptr) n = (double)counts[1];
   const double var = n > 0.0 ? m2 / n : 0.0;
   const float rstd = 1.0f / sqrtf((float)var + eps);
   const float sc = (gamma ? gamma[c] : 1.f) * rstd;
@@ -235,7 +239,7 @@ __global__ __launch_bounds__(256) void k_spna_bwd_sums(Msg m, const float* __res
     for (int64_t n = n0 + slot; n < n1; n += cut.slots) {
       int lo, hi;
       row_range(m.rowptr, n, m.E, lo, hi);
-      if (lo == hi) continue;
+      if (lo == hi || (m.valid && !m.valid[n])) continue;
       const Vec<V> a = Vec<V>::ld(m.A + n * m.lda + c), d = Vec<V>::ld(dr + n * lddr + c);
       const float inv = 1.0f / (float)(hi - lo);
       for (int e = lo; e < hi; ++e) {
@@ -275,7 +279,8 @@ __global__ __launch_bounds__(256) void k_spna_bwd_sums(Msg m, const float* __res
 // d beta = sum g, d gamma = sum g xhat (block order); coef[0..2][C] = gamma * rstd, d beta / E, d gamma / E
 __global__ __launch_bounds__(256) void k_spna_bwd_finish(const float* __restrict__ sums, int nblk, int C, const float* __restrict__ state,
                                                          const float* __restrict__ gamma, int64_t E, float* __restrict__ coef,
-                                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                         const int32_t* __restrict__ counts) {
   __shared__ double sh[2][16][17];                       // 16 columns x 16 consecutive ranges of the partials, as k_spna_stats_finish
   const int cl = threadIdx.x & 15, lane = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
@@ -291,6 +296,7 @@ __global__ __launch_bounds__(256) void k_spna_bwd_finish(const float* __restrict
   __syncthreads();
   if (c >= C || lane != 0) return;
   for (int l = 1; l < 16; ++l) { a1 += sh[0][l][cl]; a2 += sh[1][l][cl]; }
+  if (counts != nullptr) E = counts[1] > 0 ? counts[1] : 1;      // (masked form: the valid edge rows, a device value)
   coef[c] = (gamma ? gamma[c] : 1.f) * state[2 * C + c];
   coef[C + c] = (float)(a1 / (double)E);
   coef[2 * C + c] = (float)(a2 / (double)E);
@@ -315,7 +321,12 @@ __global__ __launch_bounds__(256) void k_spna_bwd_apply(Msg m, const float* __re
   Vec<V> acc;
 #pragma unroll
   for (int k = 0; k < V; ++k) acc.v[k] = 0.f;
-  if (hi > lo) {
+  if (m.valid && !m.valid[n]) {                         // masked form, padding node: zero dQ rows for its in-edges, a zero dA row
+    for (int e = lo; e < hi; ++e) {
+      int64_t j, eid;
+      if (slot_ok(m, e, j, eid)) acc.st(dQ + eid * lddq + c);
+    }
+  } else if (hi > lo) {
     const bool train = state != nullptr;
     const Vec<V> a = Vec<V>::ld(m.A + n * m.lda + c), d = Vec<V>::ld(dr + n * lddr + c);
     const Vec<V> sc = Vec<V>::ld(scale + c), sf = Vec<V>::ld(shift + c);
@@ -398,27 +409,45 @@ extern "C" int sn_spna_vector_path(int C, int64_t lda, int64_t ldb, int64_t ldq,
   return (C % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldq % 4 == 0 && ldo % 4 == 0 && a16(a) && a16(b) && a16(q) && a16(o)) ? 1 : 0;
 }
 
-extern "C" int sn_spna_stats_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
-                                 int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const float* gamma,
-                                 const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* state,
-                                 float* count, float* work, void* stream) {
-  int rc = check_msg("sn_spna_stats_f32", A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm);
+static int spna_stats(const char* fn, const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                      int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* valid,
+                      const int32_t* counts, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                      float* running_var, float* state, float* count, float* work, void* stream) {
+  int rc = check_msg(fn, A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm);
   if (rc != SN_OK) return rc;
-  SN_REQUIRE(state && count && work, "sn_spna_stats_f32: null output");
-  SN_REQUIRE(E >= 2, "sn_spna_stats_f32: train-mode BatchNorm needs more than one edge row (E = %lld)", (long long)E);
-  SN_REQUIRE(N >= 1, "sn_spna_stats_f32: edges without nodes");
-  SN_REQUIRE((running_mean != nullptr) == (running_var != nullptr), "sn_spna_stats_f32: running_mean / running_var go together");
-  const Msg m{A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm};
+  SN_REQUIRE(state && count && work, "%s: null output", fn);
+  SN_REQUIRE(E >= 2, "%s: train-mode BatchNorm needs more than one edge row (E = %lld)", fn, (long long)E);
+  SN_REQUIRE(N >= 1, "%s: edges without nodes", fn);
+  SN_REQUIRE((running_mean != nullptr) == (running_var != nullptr), "%s: running_mean / running_var go together", fn);
+  const Msg m{A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, valid};
   hipStream_t st = (hipStream_t)stream;
   const bool vec = sn_spna_vector_path(C, lda, ldb, ldq, 4, A, B, Q, nullptr) != 0;
   const Cut cut = make_cut(N, vec ? C / 4 : C);
   if (vec) hipLaunchKernelGGL(k_spna_stats<4>, dim3((unsigned)cut.nblk, (unsigned)cut.ny), dim3(256), 0, st, m, cut, work);
   else hipLaunchKernelGGL(k_spna_stats<1>, dim3((unsigned)cut.nblk, (unsigned)cut.ny), dim3(256), 0, st, m, cut, work);
-  SN_CHECK_LAUNCH("sn_spna_stats_f32");
+  SN_CHECK_LAUNCH(fn);
   hipLaunchKernelGGL(k_spna_stats_finish, dim3((unsigned)cdiv(C, 16)), dim3(256), 0, st, work, cut.nblk, C, gamma, beta, eps, momentum,
-                     running_mean, running_var, state, count);
-  SN_CHECK_LAUNCH("sn_spna_stats_f32");
+                     running_mean, running_var, state, count, counts);
+  SN_CHECK_LAUNCH(fn);
   return SN_OK;
+}
+
+extern "C" int sn_spna_stats_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                                 int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const float* gamma,
+                                 const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* state,
+                                 float* count, float* work, void* stream) {
+  return spna_stats("sn_spna_stats_f32", A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, nullptr, nullptr, gamma, beta, eps, momentum,
+                    running_mean, running_var, state, count, work, stream);
+}
+
+extern "C" int sn_spna_stats_masked_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C,
+                                        int64_t N, int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm,
+                                        const int32_t* node_valid, const int32_t* counts, const float* gamma, const float* beta, float eps,
+                                        float momentum, float* running_mean, float* running_var, float* state, float* count, float* work,
+                                        void* stream) {
+  SN_REQUIRE(node_valid && counts, "sn_spna_stats_masked_f32: null validity vector or count block");
+  return spna_stats("sn_spna_stats_masked_f32", A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, node_valid, counts, gamma, beta, eps,
+                    momentum, running_mean, running_var, state, count, work, stream);
 }
 
 extern "C" int sn_spna_mean_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
@@ -428,7 +457,7 @@ extern "C" int sn_spna_mean_f32(const float* A, int64_t lda, const float* B, int
   if (rc != SN_OK) return rc;
   SN_REQUIRE(scale && shift && r && ldr >= C, "sn_spna_mean_f32: bad arguments");
   if (N == 0) return SN_OK;
-  const Msg m{A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm};
+  const Msg m{A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, nullptr};
   hipStream_t st = (hipStream_t)stream;
   const bool vec = sn_spna_vector_path(C, lda, ldb, ldq, ldr, A, B, Q, r) != 0 && a16(scale) && a16(shift);
   if (vec) hipLaunchKernelGGL(k_spna_mean<4>, dim3((unsigned)cdiv(N * (C / 4), 256)), dim3(256), 0, st, m, scale, shift, r, ldr);
@@ -437,18 +466,18 @@ extern "C" int sn_spna_mean_f32(const float* A, int64_t lda, const float* B, int
   return SN_OK;
 }
 
-extern "C" int sn_spna_bwd_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
-                               int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* rowptr_t,
-                               const int32_t* eperm_t, const float* dr, int64_t lddr, const float* scale, const float* shift,
-                               const float* state, const float* gamma, float* dA, int64_t ldda, float* dB, int64_t lddb, float* dQ,
-                               int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream) {
-  int rc = check_msg("sn_spna_bwd_f32", A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm);
+static int spna_bwd(const char* fn, const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                    int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* rowptr_t,
+                    const int32_t* eperm_t, const int32_t* valid, const int32_t* counts, const float* dr, int64_t lddr, const float* scale,
+                    const float* shift, const float* state, const float* gamma, float* dA, int64_t ldda, float* dB, int64_t lddb, float* dQ,
+                    int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream) {
+  int rc = check_msg(fn, A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm);
   if (rc != SN_OK) return rc;
-  SN_REQUIRE(rowptr_t && eperm_t && dr && dA && dB && dQ && lddr >= C && ldda >= C && lddb >= C && lddq >= C, "sn_spna_bwd_f32: bad arguments");
-  SN_REQUIRE(state || (scale && shift), "sn_spna_bwd_f32: eval mode needs scale / shift");
-  SN_REQUIRE(!state || (work && E >= 2), "sn_spna_bwd_f32: train mode needs the work buffer and more than one edge row");
+  SN_REQUIRE(rowptr_t && eperm_t && dr && dA && dB && dQ && lddr >= C && ldda >= C && lddb >= C && lddq >= C, "%s: bad arguments", fn);
+  SN_REQUIRE(state || (scale && shift), "%s: eval mode needs scale / shift", fn);
+  SN_REQUIRE(!state || (work && E >= 2), "%s: train mode needs the work buffer and more than one edge row", fn);
   if (N == 0) return SN_OK;
-  const Msg m{A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm};
+  const Msg m{A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, valid};
   hipStream_t st = (hipStream_t)stream;
   if (state) { scale = state + 3 * (int64_t)C; shift = state + 4 * (int64_t)C; }
   const bool vec = sn_spna_vector_path(C, lda, ldb, ldq, lddr, A, B, Q, dr) != 0 && sn_spna_vector_path(C, ldda, lddb, lddq, 4, dA, dB, dQ, nullptr) != 0 &&
@@ -459,9 +488,10 @@ extern "C" int sn_spna_bwd_f32(const float* A, int64_t lda, const float* B, int6
     coef = work + (int64_t)sn_spna_blocks(N, C) * 2 * C;          // (a multiple of 4 floats when C is)
     if (vec) hipLaunchKernelGGL(k_spna_bwd_sums<4>, dim3((unsigned)cut.nblk, (unsigned)cut.ny), dim3(256), 0, st, m, dr, lddr, state, cut, work);
     else hipLaunchKernelGGL(k_spna_bwd_sums<1>, dim3((unsigned)cut.nblk, (unsigned)cut.ny), dim3(256), 0, st, m, dr, lddr, state, cut, work);
-    SN_CHECK_LAUNCH("sn_spna_bwd_f32");
-    hipLaunchKernelGGL(k_spna_bwd_finish, dim3((unsigned)cdiv(C, 16)), dim3(256), 0, st, work, cut.nblk, C, state, gamma, E, coef, dgamma, dbeta);
-    SN_CHECK_LAUNCH("sn_spna_bwd_f32");
+    SN_CHECK_LAUNCH(fn);
+    hipLaunchKernelGGL(k_spna_bwd_finish, dim3((unsigned)cdiv(C, 16)), dim3(256), 0, st, work, cut.nblk, C, state, gamma, E, coef, dgamma, dbeta,
+                       counts);
+    SN_CHECK_LAUNCH(fn);
   }
   if (vec) {
     hipLaunchKernelGGL(k_spna_bwd_apply<4>, dim3((unsigned)cdiv(N * (C / 4), 256)), dim3(256), 0, st, m, dr, lddr, scale, shift, state, coef, dA,
@@ -472,6 +502,25 @@ extern "C" int sn_spna_bwd_f32(const float* A, int64_t lda, const float* B, int6
                        dQ, lddq);
     hipLaunchKernelGGL(k_spna_rows_sum<1>, dim3((unsigned)cdiv(N * C, 256)), dim3(256), 0, st, dQ, lddq, C, N, E, rowptr_t, eperm_t, dB, lddb);
   }
-  SN_CHECK_LAUNCH("sn_spna_bwd_f32");
+  SN_CHECK_LAUNCH(fn);
   return SN_OK;
+}
+
+extern "C" int sn_spna_bwd_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                               int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* rowptr_t,
+                               const int32_t* eperm_t, const float* dr, int64_t lddr, const float* scale, const float* shift,
+                               const float* state, const float* gamma, float* dA, int64_t ldda, float* dB, int64_t lddb, float* dQ,
+                               int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream) {
+  return spna_bwd("sn_spna_bwd_f32", A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, rowptr_t, eperm_t, nullptr, nullptr, dr, lddr, scale,
+                  shift, state, gamma, dA, ldda, dB, lddb, dQ, lddq, dgamma, dbeta, work, stream);
+}
+
+extern "C" int sn_spna_bwd_masked_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Q, int64_t ldq, int C, int64_t N,
+                                      int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* eperm, const int32_t* rowptr_t,
+                                      const int32_t* eperm_t, const int32_t* node_valid, const int32_t* counts, const float* dr,
+                                      int64_t lddr, const float* state, const float* gamma, float* dA, int64_t ldda, float* dB,
+                                      int64_t lddb, float* dQ, int64_t lddq, float* dgamma, float* dbeta, float* work, void* stream) {
+  SN_REQUIRE(node_valid && counts && state, "sn_spna_bwd_masked_f32: null validity vector, count block or state (train mode only)");
+  return spna_bwd("sn_spna_bwd_masked_f32", A, lda, B, ldb, Q, ldq, C, N, E, rowptr, col, eperm, rowptr_t, eperm_t, node_valid, counts, dr,
+                  lddr, nullptr, nullptr, state, gamma, dA, ldda, dB, lddb, dQ, lddq, dgamma, dbeta, work, stream);
 }

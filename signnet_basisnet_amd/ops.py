@@ -137,14 +137,19 @@ class GraphPlan:
 
     def check(self):
         """Synchronising validity check (raises on malformed batches)."""
-        st = self.status.tolist()
-        if st[0]:
-            bits = [n for b, n in ((1, "batch not sorted"), (2, "graph id out of range"),
-                                   (4, "edge endpoint out of range"), (8, "edge crosses graphs")) if st[0] & b]
-            raise ValueError("malformed graph batch: " + ", ".join(bits))
-        if st[5] or (st[3] & 4):
-            raise IndexError(EMBEDDING_INDEX_ERROR)
-        return st
+        return check_plan_status(self.status)
+
+
+def check_plan_status(status):
+    """GraphPlan.check() on the status words alone (one host read): what a forward that deferred its check hands to check_train()."""
+    st = status.tolist()
+    if st[0]:
+        bits = [n for b, n in ((1, "batch not sorted"), (2, "graph id out of range"),
+                               (4, "edge endpoint out of range"), (8, "edge crosses graphs")) if st[0] & b]
+        raise ValueError("malformed graph batch: " + ", ".join(bits))
+    if st[5] or (st[3] & 4):
+        raise IndexError(EMBEDDING_INDEX_ERROR)
+    return st
 
 
 class _PlanBinsC(C.Structure):
@@ -1463,18 +1468,25 @@ def _row_bytes(t):
 
 def bucket_pack(data, target, out):
     """Copy a batch (and its target) of any shape into the capacity buffers `out` (a PaddedBatch of train_graph) in ONE launch
-    (sn_bucket_pack): the padding rows, the node / edge / graph validity vectors and the device count block [N, E, B, S] too."""
+    (sn_bucket_pack): the padding rows, the node / edge / graph validity vectors and the device count block [N, E, B, S] too.
+    A batch without eigen_vectors / eigen_values (the plain GNN baselines and NetGINE read none) goes through sn_bucket_pack_plain:
+    S = 0 and zero-filled eigen capacity buffers."""
     x, ei, ea, bt = data.x.contiguous(), data.edge_index.contiguous(), data.edge_attr.contiguous(), data.batch.contiguous()
-    ev, es = _f32c(data.eigen_vectors, "eigen_vectors"), _f32c(data.eigen_values, "eigen_values")
+    ev, es = getattr(data, "eigen_vectors", None), getattr(data, "eigen_values", None)
+    plain = ev is None or es is None
+    if plain:
+        ev = es = None
+    else:
+        ev, es = _f32c(ev, "eigen_vectors"), _f32c(es, "eigen_values")
     require_cuda(x, ei, ea, bt, ev, es)
-    N, E, B, S = bt.numel(), (ei.shape[1] if ei.numel() else 0), int(data.num_graphs), ev.numel()
+    N, E, B, S = bt.numel(), (ei.shape[1] if ei.numel() else 0), int(data.num_graphs), 0 if plain else ev.numel()
     for name, src, dst in (("x", x, out.x), ("edge_attr", ea, out.edge_attr), ("batch", bt, out.batch)):
         if src.dtype != dst.dtype or tuple(src.shape[1:]) != tuple(dst.shape[1:]):
             raise ValueError(f"bucket_pack: {name} is {src.dtype} {tuple(src.shape)}, the bucket holds {dst.dtype} {tuple(dst.shape)}")
     if ei.dtype != torch.int64 or ei.dim() != 2 or ei.shape[0] != 2:
         raise ValueError("bucket_pack: edge_index must be int64 [2, E]")
-    if es.numel() != N or x.shape[0] != N or ea.shape[0] != E:
-        raise ValueError(f"bucket_pack: x / eigen_values / edge_attr rows ({x.shape[0]}, {es.numel()}, {ea.shape[0]}) do not match "
+    if (N if plain else es.numel()) != N or x.shape[0] != N or ea.shape[0] != E:
+        raise ValueError(f"bucket_pack: x / eigen_values / edge_attr rows ({x.shape[0]}, {N if plain else es.numel()}, {ea.shape[0]}) do not match "
                          f"N = {N}, E = {E}")
     t = None
     if target is not None:
@@ -1488,7 +1500,10 @@ def bucket_pack(data, target, out):
                      ptr(out.eigen_vectors), ptr(out.target), ptr(out.node_valid), ptr(out.edge_valid), ptr(out.graph_valid),
                      ptr(out.counts), out.N_cap, out.E_cap, out.B_cap, out.S_cap)
     with _span("sn_bucket_pack"):
-        check(lib().sn_bucket_pack(C.byref(a), stream()), "sn_bucket_pack")
+        if plain:
+            check(lib().sn_bucket_pack_plain(C.byref(a), stream()), "sn_bucket_pack_plain")
+        else:
+            check(lib().sn_bucket_pack(C.byref(a), stream()), "sn_bucket_pack")
     return N, E, B, S
 
 
@@ -1906,6 +1921,25 @@ def gat_conv_bwd(feat, att_l, att_r, out, lse, dout, op: SparseOperator, heads, 
     return dfeat, dpar[:D], dpar[D:2 * D], dpar[2 * D:]
 
 
+def csr_drop_loops(plan: GraphPlan, rplan: GraphPlan):
+    """The operator pair of gat_conv / gat_conv_bwd from a batch's two plans, on the device (sn_csr_drop_loops): the CSR by destination
+    without the input self loops, rows in (source, input position) order — what pyg_gnn_types._gat_operator builds with boolean indexing
+    and argsort — and its transposed partner, in buffers of the plans' sizes ([N + 1], [E]).  No shape depends on the data and nothing
+    is read on the host: the form a captured step records.  The live entry count is rowptr[N] on the device; `nnz` is the capacity E.
+    rplan: the plan of the flipped edge list."""
+    if rplan.N != plan.N or rplan.E != plan.E or plan.N < 1:
+        raise ValueError("csr_drop_loops: rplan must be the plan of the flipped edge list of the same batch (N >= 1)")
+    N, E, dev = plan.N, plan.E, plan.rowptr.device
+    buf = torch.empty(2 * (N + 1) + 2 * E, dtype=torch.int32, device=dev)
+    rp, rpt, cl, clt = buf[:N + 1], buf[N + 1:2 * (N + 1)], buf[2 * (N + 1):2 * (N + 1) + E], buf[2 * (N + 1) + E:]
+    with _span("sn_csr_drop_loops"):
+        check(lib().sn_csr_drop_loops(N, E, ptr(plan.rowptr), ptr(plan.col), ptr(rplan.rowptr), ptr(rplan.col), ptr(rp), ptr(cl), ptr(rpt),
+                                      ptr(clt), stream()), "sn_csr_drop_loops")
+    fwd = SparseOperator(rp, cl, None, N)
+    fwd.t = SparseOperator(rpt, clt, None, N, fwd)
+    return fwd
+
+
 _ONES = {}
 
 
@@ -2020,9 +2054,18 @@ def _spna_operands(fn, a, b, q, plan):
     return (ptr(a), lda, ptr(b), ldb, ptr(q), ldq, Cc, N, plan.E, ptr(plan.rowptr), ptr(plan.col), ptr(plan.eperm)), N, Cc
 
 
-def spna_stats(a, b, q, plan: GraphPlan, bn):
+def _spna_mask(fn, node_valid, counts, N):
+    require_cuda(node_valid, counts)
+    if counts is None or node_valid.dtype != torch.int32 or counts.dtype != torch.int32 or node_valid.numel() != N or counts.numel() < 2 \
+            or not node_valid.is_contiguous() or not counts.is_contiguous():
+        raise ValueError(f"{fn}: node_valid must be a contiguous int32 [N] vector and counts the int32 count block of the padded batch")
+
+
+def spna_stats(a, b, q, plan: GraphPlan, bn, node_valid=None, counts=None):
     """Train-mode statistics of pre_nn.norms.0 over the E rows z_e = a[dst] + b[src] + q[e], formed on the fly (sn_spna_stats_f32): ->
-    (state [5, C] = mean | biased variance | rstd | scale | shift, count [1]); moves bn's running statistics as BatchNorm1d does."""
+    (state [5, C] = mean | biased variance | rstd | scale | shift, count [1]); moves bn's running statistics as BatchNorm1d does.
+    node_valid / counts (a padded batch: the bucket's 0/1 node vector and device count block): sn_spna_stats_masked_f32 — the in-edges of
+    invalid nodes are left out and the row count is counts[1], read on the device."""
     args, N, Cc = _spna_operands("spna_stats", a, b, q, plan)
     if plan.E < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size [{plan.E}, {Cc}]")
@@ -2033,10 +2076,15 @@ def spna_stats(a, b, q, plan: GraphPlan, bn):
     work = torch.empty(int(lib().sn_spna_blocks(N, Cc)) * 3 * Cc, dtype=torch.float32, device=a.device)
     g = None if bn.weight is None else bn.weight.detach()
     be = None if bn.bias is None else bn.bias.detach()
-    with _span("sn_spna_stats_f32"):
-        check(lib().sn_spna_stats_f32(*args, ptr(g), ptr(be), float(bn.eps), float(bn.momentum or 0.0),
-                                      ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None, ptr(out),
-                                      ptr(out[5 * Cc:]), ptr(work), stream()), "sn_spna_stats_f32")
+    tail = (ptr(g), ptr(be), float(bn.eps), float(bn.momentum or 0.0), ptr(bn.running_mean) if track else None,
+            ptr(bn.running_var) if track else None, ptr(out), ptr(out[5 * Cc:]), ptr(work), stream())
+    if node_valid is not None:
+        _spna_mask("spna_stats", node_valid, counts, N)
+        with _span("sn_spna_stats_masked_f32"):
+            check(lib().sn_spna_stats_masked_f32(*args, ptr(node_valid), ptr(counts), *tail), "sn_spna_stats_masked_f32")
+    else:
+        with _span("sn_spna_stats_f32"):
+            check(lib().sn_spna_stats_f32(*args, *tail), "sn_spna_stats_f32")
     if track:
         _count_batch(bn)
     return out[:5 * Cc].view(5, Cc), out[5 * Cc:5 * Cc + 1]
@@ -2057,10 +2105,12 @@ def spna_mean(a, b, q, plan: GraphPlan, scale, shift, out=None):
     return out
 
 
-def spna_bwd(a, b, q, plan: GraphPlan, rplan: GraphPlan, dr, *, scale=None, shift=None, state=None, gamma=None, out=None):
+def spna_bwd(a, b, q, plan: GraphPlan, rplan: GraphPlan, dr, *, scale=None, shift=None, state=None, gamma=None, out=None,
+             node_valid=None, counts=None):
     """Adjoint of spna_mean for dr [N, C] (sn_spna_bwd_f32).  state (from spna_stats): the train-mode BatchNorm backward, -> (dA, dB, dQ,
     dgamma, dbeta); state None: eval mode with the folded scale / shift, -> (dA, dB, dQ, None, None).  rplan: the plan of the flipped edge
-    list.  out: optional (dA, dB, dQ) blocks to write into."""
+    list.  out: optional (dA, dB, dQ) blocks to write into.  node_valid / counts (train mode over a padded batch, as spna_stats):
+    sn_spna_bwd_masked_f32 — invalid nodes' in-edges enter no sum, the means divide by counts[1], their dQ / dA / dB rows are zero."""
     args, N, Cc = _spna_operands("spna_bwd", a, b, q, plan)
     require_cuda(dr)
     lddr = _row_block(dr, "spna_bwd: dr")
@@ -2079,6 +2129,15 @@ def spna_bwd(a, b, q, plan: GraphPlan, rplan: GraphPlan, dr, *, scale=None, shif
         par = torch.empty(2, Cc, dtype=torch.float32, device=dev)
         dg, db = par[0], par[1]
         work = torch.empty(int(lib().sn_spna_blocks(N, Cc)) * 2 * Cc + 3 * Cc, dtype=torch.float32, device=dev)
+    if node_valid is not None:
+        _spna_mask("spna_bwd", node_valid, counts, N)
+        if state is None:
+            raise ValueError("spna_bwd: the masked form is the train-mode adjoint (state from spna_stats)")
+        with _span("sn_spna_bwd_masked_f32"):
+            check(lib().sn_spna_bwd_masked_f32(*args, ptr(rplan.rowptr), ptr(rplan.eperm), ptr(node_valid), ptr(counts), ptr(dr), lddr,
+                                               ptr(state), ptr(gamma), ptr(dA), ld[0], ptr(dB), ld[1], ptr(dQ), ld[2], ptr(dg), ptr(db),
+                                               ptr(work), stream()), "sn_spna_bwd_masked_f32")
+        return dA, dB, dQ, dg, db
     with _span("sn_spna_bwd_f32"):
         check(lib().sn_spna_bwd_f32(*args, ptr(rplan.rowptr), ptr(rplan.eperm), ptr(dr), lddr, ptr(scale), ptr(shift), ptr(state),
                                     ptr(gamma), ptr(dA), ld[0], ptr(dB), ld[1], ptr(dQ), ld[2], ptr(dg), ptr(db), ptr(work), stream()),

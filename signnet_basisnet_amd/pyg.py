@@ -332,33 +332,73 @@ class GNN(ops.DropoutHolder, nn.Module):
         plan.check()                        # one host sync: malformed batch, or an id outside its embedding table (nn.Embedding raises too)
         return y
 
+    @staticmethod
+    def _bucket_validity(pad):
+        """(node, edge, graph validity, K) of the masked ops: the 0/1 vectors of a padded batch with K = 1 under the switch `_bucket`
+        (train_graph.BucketedStep), (None, None, None, 0) — every row valid, the arguments of the eager step — without it."""
+        if pad is None:
+            return None, None, None, 0
+        return pad.node_valid, pad.edge_valid, pad.graph_valid, 1
+
+    @staticmethod
+    def _valid_ids(idx, valid):
+        """Device-derived or packed indices of a padded batch, forced into range on invalid rows (id 0: a row every table has), so only
+        a valid row can raise IndexError; their rows are masked by the op that follows, their table gradient is exactly 0."""
+        if valid is None:
+            return idx
+        v = valid.to(idx.dtype)
+        return idx * (v if idx.dim() == 1 else v.view(-1, *([1] * (idx.dim() - 1))))
+
+    def _finish_train(self, plan):
+        """The forward's one host read — malformed batch, an id outside its embedding table — or, under `_defer_status` (a captured
+        step must not synchronise), the status words handed to check_train()."""
+        if getattr(self, "_defer_status", False):
+            self._train_status = plan.status
+        else:
+            plan.check()
+
+    def check_train(self):
+        """What the last differentiable forward under `_defer_status` left unread: raises what plan.check() raises in the eager step."""
+        st, self._train_status = getattr(self, "_train_status", None), None
+        if st is not None:
+            ops.check_plan_status(st)
+
     def _forward_grad(self, data, ea, additional_x):
-        """Train mode under autograd: the launches and adjoints of SignNetGNN's differentiable GINE network (autograd.py, train_stage.py)."""
+        """Train mode under autograd: the launches and adjoints of SignNetGNN's differentiable GINE network (autograd.py, train_stage.py).
+        Under the switch `_bucket` (train_graph.BucketedStep) `data` is a padded batch: every op over node / edge / graph rows takes the
+        bucket's validity vector (K = 1), ids of invalid rows are forced to 0 and the embedded node rows masked, so padding rows enter no
+        statistic and no parameter sum.  Without it every launch and argument is as before."""
         from . import autograd as AG
         from . import train_stage as T
         B = int(data.num_graphs)
+        vN, vE, vB, k1 = self._bucket_validity(getattr(self, "_bucket", None))
         plan = ops.build_plan(data.batch, data.edge_index, B, 0)
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
         status = plan.status[5:6]
         d = self.linear.weight.shape[0]
         stage = T.supported(d, d)
+        ea = self._valid_ids(ea, vE) if not ea.dtype.is_floating_point else ea
 
-        def lin_bn(x, lin, norm, relu=True, residual=None):
+        def lin_bn(x, lin, norm, relu=True, residual=None, v=None):
+            kv = 0 if v is None else k1
             if isinstance(norm, _Identity):
-                y = AG.linear(x, lin.weight, lin.bias, None, 0, relu=relu)
-                return y if residual is None else AG.masked_add(y, residual, None, 0)
+                y = AG.linear(x, lin.weight, lin.bias, v, kv, relu=relu)
+                return y if residual is None else AG.masked_add(y, residual, v, kv)
             if stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
-                return T.lin_bn(x, lin, norm, None, 0, relu=relu, residual=residual)
-            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, None, 0, relu=relu, residual=residual)
+                return T.lin_bn(x, lin, norm, v, kv, relu=relu, residual=residual)
+            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, v, kv, relu=relu, residual=residual)
 
-        def encode(enc, v):
+        def encode(enc, v, valid=None):
             if isinstance(enc, DiscreteEncoder):
                 return AG.embedding_sum(v, [e.weight for e in enc.embeddings], status)
-            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0], v=valid)
 
-        h = encode(self.input_encoder, self._node_ids(data))
+        ids = self._node_ids(data)
+        h = encode(self.input_encoder, ids if ids.dtype.is_floating_point else self._valid_ids(ids, vN), vN)
+        if isinstance(self.input_encoder, DiscreteEncoder):
+            h = AG.mask_rows(h, vN, k1)             # (padded batch: the table rows of id 0 on padding nodes become zeros)
         if additional_x is not None:
-            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, None, 0)
+            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, vN, k1)
         staged = stage and all(isinstance(c.nn.norms[0], nn.BatchNorm1d) for c in self.convs)
         e_all = None
         if staged and all(isinstance(enc, DiscreteEncoder) for enc in self.edge_encoders) and 1 < len(self.edge_encoders) <= 16:
@@ -368,27 +408,39 @@ class GNN(ops.DropoutHolder, nn.Module):
         snap = self._dropout_begin(h.device) if drop else None
         for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
             if drop:
-                u = AG.gine_aggregate(h, encode(enc, ea), conv.layer.eps, plan, rplan)
+                u = AG.gine_aggregate(h, encode(enc, ea, vE), conv.layer.eps, plan, rplan)
                 if staged:
-                    u = T.mlp2_bn(u, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm)
+                    u = T.mlp2_bn(u, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, vN, k1)
                 else:
-                    u = lin_bn(lin_bn(u, conv.nn.layers[0], conv.nn.norms[0]), conv.nn.layers[1], norm)
+                    u = lin_bn(lin_bn(u, conv.nn.layers[0], conv.nn.norms[0], v=vN), conv.nn.layers[1], norm, v=vN)
+                # (the mask is a function of the logical element index and valid rows come first: the padded step draws the eager masks)
                 h = AG.dropout(u, drop, snap, li, residual=h)
             elif e_all is not None:
-                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li)
+                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li,
+                                 nvalid=vN, K=k1)
             elif staged:
-                h = T.gine_layer(h, encode(enc, ea), conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan)
+                h = T.gine_layer(h, encode(enc, ea, vE), conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan,
+                                 nvalid=vN, K=k1)
             else:
-                u = AG.gine_aggregate(h, encode(enc, ea), conv.layer.eps, plan, rplan)
-                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+                u = AG.gine_aggregate(h, encode(enc, ea, vE), conv.layer.eps, plan, rplan)
+                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0], v=vN)
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=h, v=vN)
+        return self._readout_grad(h, plan, status, lin_bn, vB, k1)
+
+    def _readout_grad(self, h, plan, status, lin_bn, vB, k1):
+        """Pooling, the graph-size embedding of pooling='mean', the output encoder and the status hand-over of the differentiable forward
+        (shared with pyg_gnn_types.GNN).  Padded batch: h is 0 on padding nodes, so the spare graph pools zeros; the empty graphs
+        [B, B_cap - 1) pool nothing (the mean divides by max(n, 1)); the size of an invalid graph — the spare graph may hold more nodes
+        than size_embedder has rows — is forced to 0 and its row masked."""
+        from . import autograd as AG
         pooled = AG.segment_pool(h, plan, self.pooling)
         if self.pooling == "mean":
-            pooled = AG.masked_add(pooled, AG.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight], status), None, 0)
+            sizes = self._valid_ids(self._graph_sizes(plan), vB)
+            pooled = AG.masked_add(pooled, AG.embedding_sum(sizes, [self.size_embedder.weight], status), vB, k1)
         oe = self.output_encoder
-        y = lin_bn(pooled, oe.layers[0], oe.norms[0])
-        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, None, 0)
-        plan.check()
+        y = lin_bn(pooled, oe.layers[0], oe.norms[0], v=vB)
+        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, vB, k1)
+        self._finish_train(plan)
         return y
 
 

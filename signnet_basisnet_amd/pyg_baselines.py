@@ -109,20 +109,38 @@ class NetGINE(nn.Module):
         return y
 
     def _forward_grad(self, data):
+        """Under the switch `_bucket` (train_graph.BucketedStep) `data` is a padded batch: every Linear takes the validity vector of its
+        rows (K = 1), so padding rows are zeros and enter no weight gradient.  The net has no BatchNorm: the empty graphs [B, B_cap - 1)
+        and the spare graph only have to read out finite values (Set2Set: r = 0 / 1e-16 = 0 on a graph without nodes, and the spare
+        graph's rows are zeros), which the masked Linears and the masked loss keep out of everything else.  Without the switch every
+        launch and argument is as before."""
         from . import autograd as AG
         B = int(data.num_graphs)
+        pad = getattr(self, "_bucket", None)
+        vN, vE, vB, k1 = (None, None, None, 0) if pad is None else (pad.node_valid, pad.edge_valid, pad.graph_valid, 1)
         plan = ops.build_plan(data.batch, data.edge_index, B, 0)
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
         x, ea = data.x.contiguous(), data.edge_attr.contiguous()
 
-        def lin(x_, m, relu=False):
-            return AG.linear(x_, m.weight, m.bias, None, 0, relu=relu)
+        def lin(x_, m, relu=False, v=None):
+            return AG.linear(x_, m.weight, m.bias, v, 0 if v is None else k1, relu=relu)
 
+        if pad is not None:
+            x = AG.mask_rows(x, vN, k1)             # (the first aggregation reads the raw rows: eps's gradient sums x * da over all rows)
         for conv in self._convs():
-            e = lin(lin(ea, conv.bond_encoder[0], relu=True), conv.bond_encoder[2])
+            e = lin(lin(ea, conv.bond_encoder[0], relu=True, v=vE), conv.bond_encoder[2], v=vE)
             a = AG.gine_aggregate(x, e, conv.eps, plan, rplan)
-            x = lin(lin(a, conv.mlp[0], relu=True), conv.mlp[2], relu=True)
+            x = lin(lin(a, conv.mlp[0], relu=True, v=vN), conv.mlp[2], relu=True, v=vN)
         q = self.set2set(x, plan.graph_ptr)
-        y = lin(lin(q, self.fc1, relu=True), self.fc4)
-        plan.check()
+        y = lin(lin(q, self.fc1, relu=True, v=vB), self.fc4, v=vB)
+        if getattr(self, "_defer_status", False):
+            self._train_status = plan.status        # (a captured step must not synchronise: check_train() reads it)
+        else:
+            plan.check()
         return y
+
+    def check_train(self):
+        """What the last differentiable forward under `_defer_status` left unread: raises what plan.check() raises in the eager step."""
+        st, self._train_status = getattr(self, "_train_status", None), None
+        if st is not None:
+            ops.check_plan_status(st)

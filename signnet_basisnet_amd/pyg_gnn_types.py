@@ -23,7 +23,8 @@ Launches per layer (eval; the train forward puts a statistics launch in front of
 dropout > 0 (core/model.py:65): wired as in pyg.GNN (site = the layer, between the ReLU and the residual) and, as there, refused by this
 class; dropout_models.GNN is the subclass that takes it.
 Not built, as in pyg.GNN: res=False, bn=False, dos_bins > 0; SimplifiedPNAConv with aggregators other than ['mean'] (GNN
-cannot reach them) or nhid > 128.  These nets train eagerly (no captured step).
+cannot reach them) or nhid > 128.  Training: the eager step, or train_graph.BucketedStep (one captured step per capacity bucket;
+`_forward_grad` reads the padded batch's validity vectors under the switch `_bucket`).
 """
 from __future__ import annotations
 
@@ -273,42 +274,59 @@ class GNN(_pyg.GNN):
 
     # ------------------------------------------------------------------ differentiable train mode
     def _forward_grad(self, data, ea, additional_x):
+        """Under the switch `_bucket` (train_graph.BucketedStep) `data` is a padded batch, as in pyg.GNN._forward_grad: validity vectors
+        on every op over node / edge / graph rows, ids and degrees of invalid rows forced to 0.  Per conv type:
+          GINConv   the padding self loops feed padding nodes only, whose rows are zeros; the Linears mask them.
+          GCNConv   needs no kernel of its own: sn_gcn_pyg_coef_f32 / _propagate_f32 skip self loops, and padding edges are self loops
+                    on padding nodes, so the degree of every valid node and every term of its sum are the eager step's.
+          GATConv   the operator pair comes from ops.csr_drop_loops (fixed shapes, no host read) in place of _gat_operator.
+          SimplifiedPNAConv   the edge-row BatchNorm runs its masked launches (statistics and adjoint sums over counts[1] rows)."""
         if self.gnn_type == "GINEConv":
             return super()._forward_grad(data, ea, additional_x)
         from . import autograd as AG
         from . import train_stage as T
         kind = self.gnn_type
         B = int(data.num_graphs)
+        pad = getattr(self, "_bucket", None)
+        vN, vE, vB, k1 = self._bucket_validity(pad)
         plan = ops.build_plan(data.batch, data.edge_index, B, 0)
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
         status = plan.status[5:6]
         d = self.linear.weight.shape[0]
         stage = T.supported(d, d)
+        ea = self._valid_ids(ea, vE) if not ea.dtype.is_floating_point else ea
 
-        def lin_bn(x, lin, norm, relu=True, residual=None):
+        def lin_bn(x, lin, norm, relu=True, residual=None, v=None):
+            kv = 0 if v is None else k1
             if isinstance(norm, _Identity):
-                y = AG.linear(x, lin.weight, lin.bias, None, 0, relu=relu)
-                return y if residual is None else AG.masked_add(y, residual, None, 0)
+                y = AG.linear(x, lin.weight, lin.bias, v, kv, relu=relu)
+                return y if residual is None else AG.masked_add(y, residual, v, kv)
             if stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
-                return T.lin_bn(x, lin, norm, None, 0, relu=relu, residual=residual)
-            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, None, 0, relu=relu, residual=residual)
+                return T.lin_bn(x, lin, norm, v, kv, relu=relu, residual=residual)
+            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, v, kv, relu=relu, residual=residual)
 
-        def encode(enc, v):
+        def encode(enc, v, valid=None):
             if isinstance(enc, DiscreteEncoder):
                 return AG.embedding_sum(v, [e.weight for e in enc.embeddings], status)
-            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0], v=valid)
 
-        h = encode(self.input_encoder, self._node_ids(data))
+        ids = self._node_ids(data)
+        h = encode(self.input_encoder, ids if ids.dtype.is_floating_point else self._valid_ids(ids, vN), vN)
+        if isinstance(self.input_encoder, DiscreteEncoder):
+            h = AG.mask_rows(h, vN, k1)             # (padded batch: the table rows of id 0 on padding nodes become zeros)
         if additional_x is not None:
-            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, None, 0)
+            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, vN, k1)
         if kind != "SimplifiedPNAConv":
             self._check_edge_ids(ea, status)
         if kind == "GCNConv":
             dis = ops.gcn_pyg_coef(plan)
         elif kind == "GATConv":
-            op = _gat_operator(data, plan.N)
+            op = _gat_operator(data, plan.N) if pad is None else ops.csr_drop_loops(plan, rplan)
         elif kind == "SimplifiedPNAConv":
             deg, has_in = self._degrees(plan)
+            if pad is not None:
+                # (a padding node can carry hundreds of padding edges — all of them when N_cap - N = 1 — and deg_embedder has 200 rows)
+                deg, has_in = self._valid_ids(deg, vN), self._valid_ids(has_in, vN)
         drop = self.dropout
         snap = self._dropout_begin(h.device) if drop else None
         for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
@@ -316,32 +334,29 @@ class GNN(_pyg.GNN):
             h_in = h
             if kind == "GINConv":
                 u = AG.gin_aggregate(h, conv.layer.eps, plan, rplan)
-                u = AG.linear(u, conv.nn.layers[0].weight, conv.nn.layers[0].bias, None, 0, relu=True)
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=res)
+                u = AG.linear(u, conv.nn.layers[0].weight, conv.nn.layers[0].bias, vN, k1, relu=True)
+                h = lin_bn(u, conv.nn.layers[1], norm, residual=res, v=vN)
             elif kind == "GCNConv":
-                h = lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), conv.layer.lin, norm, residual=res)
+                h = lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), conv.layer.lin, norm, residual=res, v=vN)
             elif kind == "GATConv":
                 L = conv.layer
-                f = AG.linear(h, L.lin_src.weight, None, None, 0)
+                f = AG.linear(h, L.lin_src.weight, None, vN, k1)
                 z = AG.gat_conv(f, L.att_src, L.att_dst, None, op, L.heads, None, L.negative_slope)
-                h = AG.bn_act(z, norm, None, 0, relu=True, residual=res)
+                h = AG.bn_act(z, norm, vN, k1, relu=True, residual=res)
             else:
                 W1 = conv.pre_nn.layers[0].weight
-                ab = AG.linear(h, torch.cat([W1[:, :d], W1[:, d:2 * d]], 0), None, None, 0)
-                q = AG.linear(encode(enc, ea), W1[:, 2 * d:], None, None, 0)
-                r = AG.spna_mean(ab, q, conv.pre_nn.norms[0], plan, rplan)
+                ab = AG.linear(h, torch.cat([W1[:, :d], W1[:, d:2 * d]], 0), None, vN, k1)
+                q = AG.linear(encode(enc, ea, vE), W1[:, 2 * d:], None, vE, k1)
+                if pad is None:
+                    r = AG.spna_mean(ab, q, conv.pre_nn.norms[0], plan, rplan)
+                else:
+                    r = AG.spna_mean(ab, q, conv.pre_nn.norms[0], plan, rplan, vN, pad.counts)
                 l1 = conv.pre_nn.layers[1]
                 m = AG.linear(r, l1.weight, l1.bias, has_in, 1)
                 de = AG.embedding_sum(deg, [conv.deg_embedder.weight], status)
-                u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0])
-                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=res)
+                u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0], v=vN)
+                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=res, v=vN)
             if drop:
+                # (the mask is a function of the logical element index and valid rows come first: the padded step draws the eager masks)
                 h = AG.dropout(h, drop, snap, li, residual=h_in)
-        pooled = AG.segment_pool(h, plan, self.pooling)
-        if self.pooling == "mean":
-            pooled = AG.masked_add(pooled, AG.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight], status), None, 0)
-        oe = self.output_encoder
-        y = lin_bn(pooled, oe.layers[0], oe.norms[0])
-        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, None, 0)
-        plan.check()
-        return y
+        return self._readout_grad(h, plan, status, lin_bn, vB, k1)

@@ -354,6 +354,26 @@ class _CaptureLRU:
         return self._replay(cap)
 
 
+_PLAIN_MODELS = "pyg.GNN (variant='gine'), pyg_gnn_types.GNN (any gnn_type), dropout_models.GNN, pyg_baselines.NetGINE"
+
+
+def _admit_model(model):
+    """Which models BucketedStep takes, by class: pyg.SignNetGNN -> False; the baseline models (_PLAIN_MODELS) -> True; anything else
+    TypeError.  (The check used to be `model.variant in ("gine", "alchemy")`, which also let pyg.GNN and pyg_gnn_types.GNN through at a
+    time when their forwards ignored the padded batch: padding rows entered every BatchNorm statistic.)"""
+    from . import pyg, pyg_baselines
+    if isinstance(model, pyg.SignNetGNN):
+        return False
+    if isinstance(model, pyg_baselines.NetGINE):
+        return True
+    if isinstance(model, pyg.GNN):                  # (pyg_gnn_types.GNN and dropout_models.GNN are subclasses)
+        if model.variant != "gine":
+            raise TypeError(f"BucketedStep: a pyg.GNN with variant={model.variant!r} is no model of its own (its forward is refused); "
+                            f"needs a pyg.SignNetGNN or one of {_PLAIN_MODELS}")
+        return True
+    raise TypeError(f"BucketedStep needs a pyg.SignNetGNN or one of the baseline models: {_PLAIN_MODELS} (got {type(model).__name__})")
+
+
 class BucketedStep(_CaptureLRU):
     """The captured training step for a real loader: batches of any shape (node count N, edge count E, eigenvector entries S, at most
     `max_graphs` graphs; max_k fixed or None = all eigenvectors) are padded into fixed-capacity buffers and run through a step captured
@@ -373,6 +393,11 @@ class BucketedStep(_CaptureLRU):
     (pyg.host_max_nodes: data.sizes, PyG's _slice_dict / a CPU ptr); otherwise ONE device read of the largest graph size per step, as
     the reference itself does (`int(num_nodes.max())`, GINESignNetPyG/core/transform.py:29-38).
 
+    Models: pyg.SignNetGNN, and the baselines of the two PyG trees — pyg.GNN (variant='gine'), pyg_gnn_types.GNN for every gnn_type,
+    dropout_models.GNN and pyg_baselines.NetGINE (target [B, 12]).  The baselines read no eigen data: a batch may come without
+    eigen_vectors / eigen_values (packed as S = 0), bucket_of returns S = K = 1 so only N and E pick a capture, and a GraphStore's
+    eigen data is gathered and ignored.
+
     Loss: the reference's L1 (mean |y - target| over the batch's graphs), divided by the device graph count.  Data parallel training is
     not supported (optimizer.dist must be None)."""
 
@@ -388,8 +413,7 @@ class BucketedStep(_CaptureLRU):
             raise ValueError(f"BucketedStep: loss {loss!r} is not supported (only 'l1', the reference's loss)")
         if int(max_graphs) < 1 or int(max_captures) < 1:
             raise ValueError("BucketedStep: max_graphs and max_captures must be >= 1")
-        if getattr(model, "variant", None) not in ("gine", "alchemy"):
-            raise TypeError("BucketedStep needs a pyg.SignNetGNN")
+        self.plain = _admit_model(model)            # a baseline model: reads no eigen data, so S and K never pick a capture
         self.model, self.optimizer = model, optimizer
         self.max_graphs, self.B_cap = int(max_graphs), int(max_graphs) + 1
         self.granule = dict(N=64, E=128, S=4096, K=8)
@@ -407,8 +431,10 @@ class BucketedStep(_CaptureLRU):
             raise ValueError(f"BucketedStep: a batch of {B} graphs exceeds max_graphs={self.max_graphs}")
         N = int(data.batch.numel())
         E = int(data.edge_index.shape[1]) if data.edge_index.numel() else 0
-        S = int(data.eigen_vectors.numel())
         g = self.granule
+        if self.plain:          # the smallest legal S and K: only N and E decide which capture a batch gets (eigen fields may be absent)
+            return Bucket(_round_up(N + 1, g["N"]), _round_up(max(E, 1), g["E"]), 1, 1)
+        S = int(data.eigen_vectors.numel())
         mk = getattr(self.model, "max_k", None)
         if mk:
             K = int(mk)
@@ -426,6 +452,11 @@ class BucketedStep(_CaptureLRU):
         b = self.bucket_of(data) if bucket is None else Bucket(*bucket)
         if bucket is not None and int(data.num_graphs) > self.max_graphs:
             raise ValueError(f"BucketedStep: a batch of {int(data.num_graphs)} graphs exceeds max_graphs={self.max_graphs}")
+        if self.plain and getattr(data, "eigen_vectors", None) is not None:
+            # a baseline model reads no eigen data: a batch that carries some is packed without it (S = 0), so S_cap = 1 holds it
+            import types
+            data = types.SimpleNamespace(x=data.x, edge_index=data.edge_index, edge_attr=data.edge_attr, batch=data.batch,
+                                         num_graphs=data.num_graphs)
         if self._admit(b):
             cap = self._lru[b]
             from . import ops
@@ -448,6 +479,11 @@ class BucketedStep(_CaptureLRU):
         e.g. store.covering_bucket(...) — one capture for a whole run."""
         if getattr(store, "dgl", True):
             raise TypeError("BucketedStep.step_from needs a data.GraphStore")
+        if self.plain and bucket is None:
+            # a store's batch carries eigen data: gathered and ignored (as the DGL store's pos_enc is for 'no_pe'), so S_cap holds it;
+            # K = 1, the smallest legal value
+            from .data import _resolve
+            bucket = store.bucket_of(_resolve(idx, store.device)[0], self.granule, 1)
         return self._step_from(store, idx, bucket, Bucket,
                                lambda b, fill: _BucketCapture(self, b, *store.proto(), self.warmup, fill=fill))
 
