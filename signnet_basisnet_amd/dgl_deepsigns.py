@@ -364,15 +364,7 @@ def _max_in_edges(g):
     return me
 
 
-def _bucket_rows(mod):
-    """Row validity of a PADDED batch while train_graph.DGLBucketedStep runs the module (its switch `_bucket`, set only during the
-    step's warm-up and capture): (node, edge, graph) 0/1 vectors and K = 1 — the nvalid, K every op over plain node / edge / graph rows
-    takes, so padding rows enter no batch statistic and no parameter gradient.  Without the switch (None, None, None, 0): all rows
-    valid, every launch as it was."""
-    pad = getattr(mod, "_bucket", None)
-    if pad is None:
-        return None, None, None, 0
-    return pad.node_valid, pad.edge_valid, pad.graph_valid, 1
+_bucket_rows = ops.bucket_validity          # (vN, vE, vB, k1) of a module under train_graph.DGLBucketedStep
 
 
 def _await_side(g, plan=None):

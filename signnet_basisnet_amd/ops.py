@@ -152,6 +152,24 @@ def check_plan_status(status):
     return st
 
 
+class DeferredStatus:
+    """Mixin of the plain models of the PyG trees (pyg.GNN, pyg_baselines.NetGINE): where the differentiable forward's status words go."""
+
+    def _finish_train(self, plan):
+        """The forward's one host read — malformed batch, an id outside its embedding table — or, under `_defer_status` (a captured
+        step must not synchronise), the status words handed to check_train()."""
+        if getattr(self, "_defer_status", False):
+            self._train_status = plan.status
+        else:
+            plan.check()
+
+    def check_train(self):
+        """What the last differentiable forward under `_defer_status` left unread: raises what plan.check() raises in the eager step."""
+        st, self._train_status = getattr(self, "_train_status", None), None
+        if st is not None:
+            check_plan_status(st)
+
+
 class _PlanBinsC(C.Structure):
     _fields_ = [("phi_bin_col", C.c_void_p), ("phi_max_bins", C.c_int64), ("phi_col_bin0", C.c_void_p),
                 ("phi_col_mem", C.c_void_p), ("phi_col_off", C.c_void_p), ("rho_bin0", C.c_void_p), ("meta", C.c_void_p),
@@ -1505,6 +1523,17 @@ def bucket_pack(data, target, out):
         else:
             check(lib().sn_bucket_pack(C.byref(a), stream()), "sn_bucket_pack")
     return N, E, B, S
+
+
+def bucket_validity(module):
+    """Row validity of a PADDED batch while a bucketed step (train_graph.BucketedStep / DGLBucketedStep) runs `module` (its switch
+    `_bucket`, set only during the step's warm-up and capture): the (node, edge, graph) 0/1 vectors bucket_pack / bucket_pack_dgl
+    wrote and K = 1 — the nvalid, K every op over plain node / edge / graph rows takes, so padding rows enter no batch statistic and
+    no parameter gradient.  Without the switch (None, None, None, 0): all rows valid, the arguments of the eager step."""
+    pad = getattr(module, "_bucket", None)
+    if pad is None:
+        return None, None, None, 0
+    return pad.node_valid, pad.edge_valid, pad.graph_valid, 1
 
 
 class _BucketPackDglC(C.Structure):

@@ -18,7 +18,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib as _lib_mod
+from . import autograd as AG
 from . import fused, ops
+from . import train_stage as T
 
 import os as _os
 MAX_FUSED_GRAPHS = 6144      # sn_batch_plan's work-bin limit per call
@@ -213,14 +215,21 @@ class SignNet(nn.Module):
                 getattr(self, n).reset_parameters()
 
 
-class GNN(ops.DropoutHolder, nn.Module):
+class GNN(ops.DropoutHolder, ops.DeferredStatus, nn.Module):
     """Parameter holder of the GINE network inside SignNetGNN and — `variant='gine'` — a model of its own: `forward(data,
     additional_x=None)` is the plain GINE baseline GINESignNetPyG's default run trains (train/zinc.py:31-46 with model.gnn_type GINEConv:
     GNN(None, None, nhid, 1, nlayer, 'GINEConv', dropout, pool, res=True), core/model.py:44-79), layer at a time on the kernels
     SignNetGNN's layer path uses (the fused GINE stage is not involved).  res=False is not built.  dropout > 0 (core/model.py:65,
     between the ReLU and the residual) is site `layer` of the counter-based masks of ops.dropout on the logical [N, nhid] tensor: the
     layer's last link runs without its residual, which moves into the dropout launch.  Eval mode never reads it.  Opt-in: this class and
-    pyg_gnn_types.GNN keep refusing dropout > 0 as before; dropout_models.GNN (`_feature_dropout = True`) takes it."""
+    pyg_gnn_types.GNN keep refusing dropout > 0 as before; dropout_models.GNN (`_feature_dropout = True`) takes it.
+
+    Each mode's forward is written once.  Without autograd (eval, train-mode value): `_forward_layers` — input head, layer frame, readout
+    — over a `_ValueCtx`.  Differentiable: `_forward_grad` is the head (id forcing and row masks of a padded batch, the additional_x
+    link) and `_layers_grad` the layer frame and readout over a `_GradCtx`; SignNetGNN._forward_grad puts its own head in front of the
+    same `_layers_grad`.  The conv type enters through one hook per mode, `_conv_value` / `_conv_grad`: called once per forward (its
+    body is the per-forward setup), it returns the per-layer body `layer(li, h, res) -> h`.  The hooks here are GINEConv's;
+    pyg_gnn_types.GNN overrides them for the other four."""
 
     _feature_dropout = False
 
@@ -289,56 +298,38 @@ class GNN(ops.DropoutHolder, nn.Module):
     def _forward_layers(self, data, ea, additional_x, train):
         """Eval (BatchNorm folded into the GEMM epilogues) and the train-mode forward without autograd (batch statistics, running-statistics
         update): one launch per op."""
-        fold = not train
-        plan = ops.build_plan(data.batch, data.edge_index, int(data.num_graphs), 0)
-        status = plan.status[5:6]
-        cache = _eval_cache(self) if fold else {}       # eval: packed weights and folded BatchNorms live until a parameter or buffer changes
-
-        def pack(lin):
-            if id(lin) not in cache:
-                cache[id(lin)] = _pack(lin)
-            return cache[id(lin)]
-
-        def lin_bn(x, lin, norm, relu=True, residual=None):
-            if isinstance(norm, _Identity):
-                return ops.masked_linear(x, pack(lin), relu=relu, residual=residual)
-            if id(norm) not in cache:
-                cache[id(norm)] = _BN(norm, fold)
-            return _lin_bn(x, pack(lin), cache[id(norm)], train, relu=relu, residual=residual)
-
-        def encode(enc, v):
-            if isinstance(enc, DiscreteEncoder):
-                return ops.embedding_sum(v, [e.weight.detach() for e in enc.embeddings], status)
-            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
-
-        h = encode(self.input_encoder, self._node_ids(data))
+        c = _ValueCtx(self, data, train)
+        plan = c.plan
+        h = c.encode(self.input_encoder, self._node_ids(data))
         if additional_x is not None:
-            h = ops.masked_linear(torch.cat([h, additional_x], dim=-1), pack(self.linear))
+            h = ops.masked_linear(torch.cat([h, additional_x], dim=-1), c.pack(self.linear))
+        layer = self._conv_value(c, ea)
         drop = self.dropout if train else 0.0
         snap = self._dropout_begin(h.device) if drop else None
-        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
-            u = ops.gine_aggregate(h, encode(enc, ea), plan, conv.layer.eps.detach())
-            u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
-            if drop:
-                h = ops.dropout(lin_bn(u, conv.nn.layers[1], norm), drop, snap, li, residual=h)
-            else:
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=h)
+        for li in range(len(self.convs)):
+            # (dropout sits between the ReLU and the residual: the layer runs without it and the add moves into the dropout launch)
+            u = layer(li, h, None if drop else h)
+            h = ops.dropout(u, drop, snap, li, residual=h) if drop else u
         pooled = ops.segment_pool(h, plan, self.pooling)
         if self.pooling == "mean":
-            size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], status)
+            size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], c.status)
             pooled = ops.masked_affine(pooled, residual=size)
         oe = self.output_encoder
-        y = ops.masked_linear(lin_bn(pooled, oe.layers[0], oe.norms[0]), pack(oe.layers[1]))
+        y = ops.masked_linear(c.lin_bn(pooled, oe.layers[0], oe.norms[0]), c.pack(oe.layers[1]))
         plan.check()                        # one host sync: malformed batch, or an id outside its embedding table (nn.Embedding raises too)
         return y
 
-    @staticmethod
-    def _bucket_validity(pad):
-        """(node, edge, graph validity, K) of the masked ops: the 0/1 vectors of a padded batch with K = 1 under the switch `_bucket`
-        (train_graph.BucketedStep), (None, None, None, 0) — every row valid, the arguments of the eager step — without it."""
-        if pad is None:
-            return None, None, None, 0
-        return pad.node_valid, pad.edge_valid, pad.graph_valid, 1
+    def _conv_value(self, c, ea):
+        """The conv-type hook of `_forward_layers`: runs what the conv type needs once per forward and returns the layer body
+        `layer(li, h, res) -> h` (res: the residual the layer's last link adds, None under dropout).  Here GINEConv."""
+        encs, convs, norms = list(self.edge_encoders), list(self.convs), list(self.norms)
+
+        def layer(li, h, res):
+            conv = convs[li]
+            u = ops.gine_aggregate(h, c.encode(encs[li], ea), c.plan, conv.layer.eps.detach())
+            u = c.lin_bn(u, conv.nn.layers[0], conv.nn.norms[0])
+            return c.lin_bn(u, conv.nn.layers[1], norms[li], residual=res)
+        return layer
 
     @staticmethod
     def _valid_ids(idx, valid):
@@ -349,99 +340,151 @@ class GNN(ops.DropoutHolder, nn.Module):
         v = valid.to(idx.dtype)
         return idx * (v if idx.dim() == 1 else v.view(-1, *([1] * (idx.dim() - 1))))
 
-    def _finish_train(self, plan):
-        """The forward's one host read — malformed batch, an id outside its embedding table — or, under `_defer_status` (a captured
-        step must not synchronise), the status words handed to check_train()."""
-        if getattr(self, "_defer_status", False):
-            self._train_status = plan.status
-        else:
-            plan.check()
-
-    def check_train(self):
-        """What the last differentiable forward under `_defer_status` left unread: raises what plan.check() raises in the eager step."""
-        st, self._train_status = getattr(self, "_train_status", None), None
-        if st is not None:
-            ops.check_plan_status(st)
-
     def _forward_grad(self, data, ea, additional_x):
         """Train mode under autograd: the launches and adjoints of SignNetGNN's differentiable GINE network (autograd.py, train_stage.py).
         Under the switch `_bucket` (train_graph.BucketedStep) `data` is a padded batch: every op over node / edge / graph rows takes the
         bucket's validity vector (K = 1), ids of invalid rows are forced to 0 and the embedded node rows masked, so padding rows enter no
         statistic and no parameter sum.  Without it every launch and argument is as before."""
-        from . import autograd as AG
-        from . import train_stage as T
         B = int(data.num_graphs)
-        vN, vE, vB, k1 = self._bucket_validity(getattr(self, "_bucket", None))
         plan = ops.build_plan(data.batch, data.edge_index, B, 0)
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
-        status = plan.status[5:6]
         d = self.linear.weight.shape[0]
-        stage = T.supported(d, d)
-        ea = self._valid_ids(ea, vE) if not ea.dtype.is_floating_point else ea
-
-        def lin_bn(x, lin, norm, relu=True, residual=None, v=None):
-            kv = 0 if v is None else k1
-            if isinstance(norm, _Identity):
-                y = AG.linear(x, lin.weight, lin.bias, v, kv, relu=relu)
-                return y if residual is None else AG.masked_add(y, residual, v, kv)
-            if stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
-                return T.lin_bn(x, lin, norm, v, kv, relu=relu, residual=residual)
-            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, v, kv, relu=relu, residual=residual)
-
-        def encode(enc, v, valid=None):
-            if isinstance(enc, DiscreteEncoder):
-                return AG.embedding_sum(v, [e.weight for e in enc.embeddings], status)
-            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0], v=valid)
-
+        c = _GradCtx(self, data, plan, rplan, T.supported(d, d))
+        vN, k1 = c.vN, c.k1
+        ea = self._valid_ids(ea, c.vE) if not ea.dtype.is_floating_point else ea
         ids = self._node_ids(data)
-        h = encode(self.input_encoder, ids if ids.dtype.is_floating_point else self._valid_ids(ids, vN), vN)
+        h = c.encode(self.input_encoder, ids if ids.dtype.is_floating_point else self._valid_ids(ids, vN), vN)
         if isinstance(self.input_encoder, DiscreteEncoder):
             h = AG.mask_rows(h, vN, k1)             # (padded batch: the table rows of id 0 on padding nodes become zeros)
         if additional_x is not None:
             h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, vN, k1)
-        staged = stage and all(isinstance(c.nn.norms[0], nn.BatchNorm1d) for c in self.convs)
-        e_all = None
-        if staged and all(isinstance(enc, DiscreteEncoder) for enc in self.edge_encoders) and 1 < len(self.edge_encoders) <= 16:
-            # every layer embeds the same edge_attr with its own tables: one [L, E, C] block, one adjoint launch pair for all layers
-            e_all = AG.embedding_sum_layers(ea, [[t.weight for t in enc.embeddings] for enc in self.edge_encoders], status)
-        drop = self.dropout
-        snap = self._dropout_begin(h.device) if drop else None
-        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
-            if drop:
-                u = AG.gine_aggregate(h, encode(enc, ea, vE), conv.layer.eps, plan, rplan)
-                if staged:
-                    u = T.mlp2_bn(u, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, vN, k1)
-                else:
-                    u = lin_bn(lin_bn(u, conv.nn.layers[0], conv.nn.norms[0], v=vN), conv.nn.layers[1], norm, v=vN)
-                # (the mask is a function of the logical element index and valid rows come first: the padded step draws the eager masks)
-                h = AG.dropout(u, drop, snap, li, residual=h)
-            elif e_all is not None:
-                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li,
-                                 nvalid=vN, K=k1)
-            elif staged:
-                h = T.gine_layer(h, encode(enc, ea, vE), conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan,
-                                 nvalid=vN, K=k1)
-            else:
-                u = AG.gine_aggregate(h, encode(enc, ea, vE), conv.layer.eps, plan, rplan)
-                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0], v=vN)
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=h, v=vN)
-        return self._readout_grad(h, plan, status, lin_bn, vB, k1)
-
-    def _readout_grad(self, h, plan, status, lin_bn, vB, k1):
-        """Pooling, the graph-size embedding of pooling='mean', the output encoder and the status hand-over of the differentiable forward
-        (shared with pyg_gnn_types.GNN).  Padded batch: h is 0 on padding nodes, so the spare graph pools zeros; the empty graphs
-        [B, B_cap - 1) pool nothing (the mean divides by max(n, 1)); the size of an invalid graph — the spare graph may hold more nodes
-        than size_embedder has rows — is forced to 0 and its row masked."""
-        from . import autograd as AG
-        pooled = AG.segment_pool(h, plan, self.pooling)
-        if self.pooling == "mean":
-            sizes = self._valid_ids(self._graph_sizes(plan), vB)
-            pooled = AG.masked_add(pooled, AG.embedding_sum(sizes, [self.size_embedder.weight], status), vB, k1)
-        oe = self.output_encoder
-        y = lin_bn(pooled, oe.layers[0], oe.norms[0], v=vB)
-        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, vB, k1)
+        y = self._layers_grad(c, h, ea)
         self._finish_train(plan)
         return y
+
+    def _layers_grad(self, c, h, ea, size_embed=True):
+        """The differentiable forward behind its head (SignNetGNN._forward_grad, whose head differs, calls it too): the conv layers in
+        their residual-or-dropout frame, pooling, the graph-size embedding of pooling='mean' (`size_embed`: SignNetGNN adds none) and
+        the output encoder.  Padded batch: h is 0 on padding nodes, so the spare graph pools zeros; the empty graphs [B, B_cap - 1)
+        pool nothing (the mean divides by max(n, 1)); the size of an invalid graph — the spare graph may hold more nodes than
+        size_embedder has rows — is forced to 0 and its row masked."""
+        layer = self._conv_grad(c, ea)
+        drop = self.dropout
+        snap = self._dropout_begin(h.device) if drop else None
+        for li in range(len(self.convs)):
+            # (dropout sits between the ReLU and the residual: the layer runs without it and the add moves into the dropout launch, whose
+            # mask is a function of the logical element index — valid rows come first, so the padded step draws the eager masks)
+            u = layer(li, h, None if drop else h)
+            h = AG.dropout(u, drop, snap, li, residual=h) if drop else u
+        pooled = AG.segment_pool(h, c.plan, self.pooling)
+        if size_embed and self.pooling == "mean":
+            sizes = self._valid_ids(self._graph_sizes(c.plan), c.vB)
+            pooled = AG.masked_add(pooled, AG.embedding_sum(sizes, [self.size_embedder.weight], c.status), c.vB, c.k1)
+        oe = self.output_encoder
+        y = c.lin_bn(pooled, oe.layers[0], oe.norms[0], c.vB)
+        return AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, c.vB, c.k1)
+
+    def _conv_grad(self, c, ea):
+        """The conv-type hook of `_layers_grad`: runs what the conv type needs once per forward and returns the layer body
+        `layer(li, h, res) -> h` (res: the residual the layer's last link adds, None under dropout).  Here GINEConv, in three shapes:
+        the staged layer (T.gine_layer: aggregate, both links and the residual with fused adjoints; the edge embeddings of all layers
+        in one block when they are table sums), under dropout the staged link pair without a residual (T.mlp2_bn), and one launch per
+        op.  "Staged" is c.stage alone, for all layers: GINEConv builds its MLP with BatchNorm and self.norms are BatchNorm1d, so
+        asking the layers for them (SignNetGNN's copy of this loop did, layer by layer; this class's did once for all) was never false."""
+        plan, rplan, vN, k1 = c.plan, c.rplan, c.vN, c.k1
+        encs, convs, norms = list(self.edge_encoders), list(self.convs), list(self.norms)
+        e_all = None
+        if c.stage and all(isinstance(enc, DiscreteEncoder) for enc in encs) and 1 < len(encs) <= 16:
+            # every layer embeds the same edge_attr with its own tables: one [L, E, C] block, one adjoint launch pair for all layers
+            # (built under dropout too, where no layer reads it: that step's launches stay the ones it had)
+            e_all = AG.embedding_sum_layers(ea, [[t.weight for t in enc.embeddings] for enc in encs], c.status)
+
+        def layer(li, h, res):
+            conv, norm = convs[li], norms[li]
+            l0, n0, l1 = conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1]
+            if e_all is not None and res is not None:
+                return T.gine_layer(h, e_all, conv.layer.eps, l0, n0, l1, norm, plan, rplan, layer=li, nvalid=vN, K=k1)
+            e = c.encode(encs[li], ea, c.vE)
+            if c.stage and res is not None:
+                return T.gine_layer(h, e, conv.layer.eps, l0, n0, l1, norm, plan, rplan, nvalid=vN, K=k1)
+            u = AG.gine_aggregate(h, e, conv.layer.eps, plan, rplan)
+            if c.stage:                             # (under dropout)
+                return T.mlp2_bn(u, l0, n0, l1, norm, vN, k1)
+            return c.lin_bn(c.lin_bn(u, l0, n0, vN), l1, norm, vN, residual=res)
+        return layer
+
+
+class _ValueCtx:
+    """What the conv-type hooks of a forward without autograd share with pyg.GNN._forward_layers: the plan, the status word and the
+    links over packed weights — eval: BatchNorm folded into the GEMM epilogues, packed weights and folded BatchNorms kept in the
+    module's cache until a parameter or buffer changes; train: batch statistics and the running-statistics update."""
+
+    def __init__(self, module, data, train):
+        self.data, self.train = data, train
+        self.plan = ops.build_plan(data.batch, data.edge_index, int(data.num_graphs), 0)
+        self.status = self.plan.status[5:6]
+        self.cache = {} if train else _eval_cache(module)
+
+    def cached(self, key, make):
+        if key not in self.cache:
+            self.cache[key] = make()
+        return self.cache[key]
+
+    def pack(self, lin):
+        return self.cached(id(lin), lambda: _pack(lin))
+
+    def bn_of(self, norm):
+        return self.cached(id(norm), lambda: _BN(norm, not self.train))
+
+    def lin_bn(self, x, lin, norm, relu=True, residual=None):
+        if isinstance(norm, _Identity):
+            return ops.masked_linear(x, self.pack(lin), relu=relu, residual=residual)
+        return _lin_bn(x, self.pack(lin), self.bn_of(norm), self.train, relu=relu, residual=residual)
+
+    def bn_act(self, z, norm, residual):
+        """BatchNorm -> ReLU -> + residual on a materialised z (behind an aggregation: no GEMM epilogue to fold into)."""
+        if self.train:
+            _, _, _, sc, sh, _ = ops.bn_train_stats(z, norm)
+        else:
+            b = self.bn_of(norm)
+            sc, sh = b.scale, b.shift
+        return ops.masked_affine(z, scale=sc, shift=sh, relu=True, residual=residual)
+
+    def encode(self, enc, v):
+        if isinstance(enc, DiscreteEncoder):
+            return ops.embedding_sum(v, [e.weight.detach() for e in enc.embeddings], self.status)
+        return self.lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
+
+
+class _GradCtx:
+    """What the conv-type hooks of a differentiable forward share with pyg.GNN._layers_grad and the head in front of it: the in- and
+    out-edge plans, the status word, `stage`, the row validity of `module` (ops.bucket_validity: the model a bucketed step runs) and
+    the links built on them."""
+
+    def __init__(self, module, data, plan, rplan, stage):
+        self.data, self.plan, self.rplan, self.stage = data, plan, rplan, stage
+        self.status = plan.status[5:6]
+        self.pad = getattr(module, "_bucket", None)
+        self.vN, self.vE, self.vB, self.k1 = ops.bucket_validity(module)
+
+    def lin_bn(self, x, lin, norm, v=None, K=None, relu=True, residual=None):
+        """Linear -> [mask] -> BatchNorm -> [ReLU] [-> + residual], the one definition of the differentiable forwards: with `stage` the
+        one-pass link kernels of train_stage.py where the widths allow them, else one launch per op (autograd.py).  A row-validity
+        vector `v` comes with K = k1 (1 under a bucketed step, else 0); the slot tensors of phi and rho pass their own (nvalid, K)."""
+        if K is None:
+            K = 0 if v is None else self.k1
+        if isinstance(norm, _Identity):
+            y = AG.linear(x, lin.weight, lin.bias, v, K, relu=relu)
+            return y if residual is None else AG.masked_add(y, residual, v, K)
+        bn = norm.bn if isinstance(norm, MaskedBN) else norm
+        if self.stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
+            return T.lin_bn(x, lin, bn, v, K, relu=relu, residual=residual)
+        return AG.linear_bn_act(x, lin.weight, lin.bias, bn, v, K, relu=relu, residual=residual)
+
+    def encode(self, enc, v, valid=None):
+        if isinstance(enc, DiscreteEncoder):
+            return AG.embedding_sum(v, [e.weight for e in enc.embeddings], self.status)
+        return self.lin_bn(v.contiguous(), enc.layers[0], enc.norms[0], valid)
 
 
 # ----------------------------------------------------------------------------- prepared (packed) parameters
@@ -1004,7 +1047,6 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         buffers (ops.bucket_pack): the plan gives the padding graphs no eigenvector slot, K is the bucket's slot capacity, and every op
         over plain node / edge / graph rows that treats all rows as valid today takes the 0/1 validity vector of the bucket (K = 1), so
         padding rows enter no batch statistic and no parameter gradient.  Without it every launch and argument is as before."""
-        from . import autograd as AG
         ops.require_cuda(data.edge_index, data.batch, data.eigen_vectors)
         sn, g = self.sign_net, self.gnn
         B = int(data.num_graphs)
@@ -1016,28 +1058,17 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, self.max_k or 0)   # out-edge CSR
         if pad is None:
             K = int(self.max_k) if self.max_k else plan.check()[1]
-            vN = vE = vB = None          # node / edge / graph rows: all valid
-            k1 = 0
         else:
             K = int(pad.K)
-            vN, vE, vB, k1 = pad.node_valid, pad.edge_valid, pad.graph_valid, 1
         N, nv = plan.N, plan.nvalid
         alchemy_eig = self.variant == "alchemy" and not sn.ignore_eigval
         want_vals = alchemy_eig or self.variant != "alchemy"
         x0, s0 = ops.pack_eig(plan, data.eigen_vectors, data.eigen_values if want_vals else None, K, want_vals)
 
-        def lin_bn(x, lin, norm, nvalid=None, K_=0, relu=True, residual=None):
-            if isinstance(norm, _Identity):
-                y = AG.linear(x, lin.weight, lin.bias, nvalid, K_, relu=relu)
-                return y if residual is None else AG.masked_add(y, residual, nvalid, K_)
-            bn = norm.bn if isinstance(norm, MaskedBN) else norm
-            if stage and isinstance(bn, nn.BatchNorm1d) and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
-                return T.lin_bn(x, lin, bn, nvalid, K_, relu=relu, residual=residual)
-            return AG.linear_bn_act(x, lin.weight, lin.bias, bn, nvalid, K_, relu=relu, residual=residual)
-
-        from . import train_stage as T
         d = self.cfg["n_hid"]
         stage = self.train_stages and T.supported(d, d)
+        c = _GradCtx(self, data, plan, rplan, stage)         # (row validity of node / edge / graph rows: this model's `_bucket`)
+        lin_bn, vN, k1 = c.lin_bn, c.vN, c.k1
 
         def scalar_form(l0, l1):     # Linear(1, 1, bias=False) -> Linear(1, d): the closed-form 1 -> 1 -> d kernels apply
             return stage and l0.weight.numel() == 1 and l0.bias is None and l1.weight.shape[1] == 1
@@ -1108,41 +1139,12 @@ class SignNetGNN(ops.DropoutHolder, nn.Module):
             x = AG.masked_layernorm(z, y, f.norm.ln.weight, f.norm.ln.bias, LN_EPS, nv, K)
         s = AG.slot_sum(x, N, K, nv)
         pe = lin_bn(s, sn.rho.out[0], sn.rho.out[1], vN, k1, relu=False)
-        # ---- GINE network
-        xin = data.x.squeeze() if data.x.dim() > 1 and data.x.shape[-1] == 1 else data.x
-        if isinstance(g.input_encoder, DiscreteEncoder):
-            h = AG.embedding_sum(xin, [e.weight for e in g.input_encoder.embeddings], plan.status[5:6])
-        else:
-            h = lin_bn(xin.contiguous(), g.input_encoder.layers[0], g.input_encoder.norms[0], vN, k1)
-        # (the embedding rows of padding nodes are masked here: their gradient into the tables is exactly 0)
+        # ---- GINE network: this head (ids and edge_attr as they come, no row mask: the cat[h, pe] link masks the embedding rows of
+        # padding nodes, so their gradient into the tables is exactly 0), then the layers and the readout of the plain model — without
+        # a graph-size embedding, and with the status words left to check_train() below
+        h = c.encode(g.input_encoder, GNN._node_ids(data), vN)
         h = AG.linear(torch.cat([h, pe], dim=-1), g.linear.weight, g.linear.bias, vN, k1)
-        staged = [stage and isinstance(conv.nn.norms[0], nn.BatchNorm1d) and isinstance(norm, nn.BatchNorm1d)
-                  for conv, norm in zip(g.convs, g.norms)]
-        # every layer embeds the same edge_attr with its own tables: one [L, E, C] block, one adjoint launch pair for all layers
-        e_all = None
-        if all(staged) and all(isinstance(enc, DiscreteEncoder) for enc in g.edge_encoders) and 1 < len(g.edge_encoders) <= 16:
-            e_all = AG.embedding_sum_layers(data.edge_attr, [[t.weight for t in enc.embeddings] for enc in g.edge_encoders], plan.status[5:6])
-        for li, (enc, conv, norm) in enumerate(zip(g.edge_encoders, g.convs, g.norms)):
-            if e_all is not None:
-                h = T.gine_layer(h, e_all, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan, layer=li,
-                                 nvalid=vN, K=k1)
-                continue
-            if isinstance(enc, DiscreteEncoder):
-                e = AG.embedding_sum(data.edge_attr, [t.weight for t in enc.embeddings], plan.status[5:6])
-            else:
-                e = lin_bn(data.edge_attr.contiguous(), enc.layers[0], enc.norms[0], vE, k1)
-            if staged[li]:
-                h = T.gine_layer(h, e, conv.layer.eps, conv.nn.layers[0], conv.nn.norms[0], conv.nn.layers[1], norm, plan, rplan,
-                                 nvalid=vN, K=k1)
-            else:
-                u = AG.gine_aggregate(h, e, conv.layer.eps, plan, rplan)
-                u = lin_bn(u, conv.nn.layers[0], conv.nn.norms[0], vN, k1)
-                h = lin_bn(u, conv.nn.layers[1], norm, vN, k1, residual=h)
-        # (padded batch: h is 0 on padding nodes, so the spare graph pools zeros and the empty graphs [B, B_cap-1) pool nothing)
-        pooled = AG.segment_pool(h, plan, g.pooling)
-        oe = g.output_encoder
-        y = lin_bn(pooled, oe.layers[0], oe.norms[0], vB, k1)
-        y = AG.linear(y, oe.layers[1].weight, oe.layers[1].bias, vB, k1)
+        y = g._layers_grad(c, h, data.edge_attr, size_embed=False)
         discrete = isinstance(g.input_encoder, DiscreteEncoder) or any(isinstance(e, DiscreteEncoder) for e in g.edge_encoders)
         self._train_status = plan.status if discrete else None
         if not getattr(self, "_defer_status", False):

@@ -56,7 +56,7 @@ class Set2Set(nn.Module):
         return ops.set2set(x.contiguous(), graph_ptr, *(t.detach() for t in self._tensors()), self.processing_steps)
 
 
-class NetGINE(nn.Module):
+class NetGINE(ops.DeferredStatus, nn.Module):
     def __init__(self, dim):
         super().__init__()
         if not 1 <= dim <= 128:
@@ -116,8 +116,7 @@ class NetGINE(nn.Module):
         launch and argument is as before."""
         from . import autograd as AG
         B = int(data.num_graphs)
-        pad = getattr(self, "_bucket", None)
-        vN, vE, vB, k1 = (None, None, None, 0) if pad is None else (pad.node_valid, pad.edge_valid, pad.graph_valid, 1)
+        vN, vE, vB, k1 = ops.bucket_validity(self)
         plan = ops.build_plan(data.batch, data.edge_index, B, 0)
         rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
         x, ea = data.x.contiguous(), data.edge_attr.contiguous()
@@ -125,7 +124,7 @@ class NetGINE(nn.Module):
         def lin(x_, m, relu=False, v=None):
             return AG.linear(x_, m.weight, m.bias, v, 0 if v is None else k1, relu=relu)
 
-        if pad is not None:
+        if k1:
             x = AG.mask_rows(x, vN, k1)             # (the first aggregation reads the raw rows: eps's gradient sums x * da over all rows)
         for conv in self._convs():
             e = lin(lin(ea, conv.bond_encoder[0], relu=True, v=vE), conv.bond_encoder[2], v=vE)
@@ -133,14 +132,5 @@ class NetGINE(nn.Module):
             x = lin(lin(a, conv.mlp[0], relu=True, v=vN), conv.mlp[2], relu=True, v=vN)
         q = self.set2set(x, plan.graph_ptr)
         y = lin(lin(q, self.fc1, relu=True, v=vB), self.fc4, v=vB)
-        if getattr(self, "_defer_status", False):
-            self._train_status = plan.status        # (a captured step must not synchronise: check_train() reads it)
-        else:
-            plan.check()
+        self._finish_train(plan)                    # (a captured step must not synchronise: check_train() reads the status words)
         return y
-
-    def check_train(self):
-        """What the last differentiable forward under `_defer_status` left unread: raises what plan.check() raises in the eager step."""
-        st, self._train_status = getattr(self, "_train_status", None), None
-        if st is not None:
-            ops.check_plan_status(st)

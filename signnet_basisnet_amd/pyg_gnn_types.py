@@ -24,17 +24,25 @@ dropout > 0 (core/model.py:65): wired as in pyg.GNN (site = the layer, between t
 class; dropout_models.GNN is the subclass that takes it.
 Not built, as in pyg.GNN: res=False, bn=False, dos_bins > 0; SimplifiedPNAConv with aggregators other than ['mean'] (GNN
 cannot reach them) or nhid > 128.  Training: the eager step, or train_graph.BucketedStep (one captured step per capacity bucket;
-`_forward_grad` reads the padded batch's validity vectors under the switch `_bucket`).
+the differentiable forward reads the padded batch's validity vectors under the switch `_bucket`).
+
+Structure: the forwards are pyg.GNN's, written once per mode — input head, the residual-or-dropout frame around every layer, readout,
+status hand-over.  GNN below adds the conv wrappers and overrides pyg.GNN's two hooks, `_conv_value(c, ea)` (eval / train value
+without autograd) and `_conv_grad(c, ea)` (differentiable): each runs, per conv type, what that type needs once per forward — the
+edge-id range check of the edge-blind convs, GCN's coefficients, GAT's operator pair, PNA's degrees — and returns the per-layer body
+`layer(li, h, res) -> h` over the context `c` (plans, status word, validity vectors and the Linear/BatchNorm links of that mode:
+pyg._ValueCtx / pyg._GradCtx).  'GINEConv' goes to pyg.GNN's own hooks.  A new conv type is one branch in each of the two hooks.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
+from . import autograd as AG
 from . import ops
 from . import pyg as _pyg
 from .filter_baselines import _glorot, _operator_pair
-from .pyg import MLP, DiscreteEncoder, GINEConv, _BN, _GINEps, _Identity, _eval_cache, _lin_bn, _pack
+from .pyg import MLP, DiscreteEncoder, GINEConv, _GINEps
 
 GNN_TYPES = ("GINEConv", "GINConv", "GCNConv", "GATConv", "SimplifiedPNAConv")
 PNA_MAX_HIDDEN = ops.SPNA_MAX_CHANNELS // 3          # 128: C = 3 * nhid channels per edge row
@@ -150,7 +158,7 @@ def _gat_operator(data, N):
 class GNN(_pyg.GNN):
     """core/model.py's GNN with the reference's signature, for the five gnn_type values.  'GINEConv' is pyg.GNN itself (same launches, bit
     for bit).  Three modes: eval, the train-mode forward without autograd (batch statistics, running-statistics update) and the
-    differentiable train-mode forward."""
+    differentiable train-mode forward — pyg.GNN's forwards; this class supplies the conv modules and the two hooks below."""
 
     def __init__(self, nfeat_node, nfeat_edge, nhid, nout, nlayer, gnn_type, dropout=0, pooling="add", bn=True, dos_bins=0, res=True):
         if gnn_type not in _WRAPPERS:
@@ -175,188 +183,114 @@ class GNN(_pyg.GNN):
         deg = plan.rowptr[1:] - plan.rowptr[:-1]                  # in-degree, int32 [N]
         return deg.long(), deg.clamp(max=1).contiguous()
 
-    # ------------------------------------------------------------------ eval / train value without autograd
-    def _forward_layers(self, data, ea, additional_x, train):
-        if self.gnn_type == "GINEConv":
-            return super()._forward_layers(data, ea, additional_x, train)
-        fold = not train
+    # ------------------------------------------------------------------ the conv-type hooks of pyg.GNN's two forwards
+    def _conv_value(self, c, ea):
+        """Eval / train-mode value without autograd: per conv type what it needs once per forward, then its layer body (module docstring)."""
         kind = self.gnn_type
-        plan = ops.build_plan(data.batch, data.edge_index, int(data.num_graphs), 0)
-        status = plan.status[5:6]
-        cache = _eval_cache(self) if fold else {}
-
-        def cached(key, make):
-            if key not in cache:
-                cache[key] = make()
-            return cache[key]
-
-        def pack(lin):
-            return cached(id(lin), lambda: _pack(lin))
-
-        def bn_of(norm):
-            return cached(id(norm), lambda: _BN(norm, fold))
-
-        def lin_bn(x, lin, norm, relu=True, residual=None):
-            if isinstance(norm, _Identity):
-                return ops.masked_linear(x, pack(lin), relu=relu, residual=residual)
-            return _lin_bn(x, pack(lin), bn_of(norm), train, relu=relu, residual=residual)
-
-        def bn_act(z, norm, residual):
-            """BatchNorm -> ReLU -> + residual on a materialised z (behind an aggregation: no GEMM epilogue to fold into)."""
-            if fold:
-                b = bn_of(norm)
-                return ops.masked_affine(z, scale=b.scale, shift=b.shift, relu=True, residual=residual)
-            _, _, _, sc, sh, _ = ops.bn_train_stats(z, norm)
-            return ops.masked_affine(z, scale=sc, shift=sh, relu=True, residual=residual)
-
-        def encode(enc, v):
-            if isinstance(enc, DiscreteEncoder):
-                return ops.embedding_sum(v, [e.weight.detach() for e in enc.embeddings], status)
-            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0])
-
-        h = encode(self.input_encoder, self._node_ids(data))
-        if additional_x is not None:
-            h = ops.masked_linear(torch.cat([h, additional_x], dim=-1), pack(self.linear))
+        if kind == "GINEConv":
+            return super()._conv_value(c, ea)
+        plan, pack, lin_bn = c.plan, c.pack, c.lin_bn
+        encs, convs, norms = list(self.edge_encoders), list(self.convs), list(self.norms)
         if kind != "SimplifiedPNAConv":
-            self._check_edge_ids(ea, status)
-        if kind == "GCNConv":
-            dis = ops.gcn_pyg_coef(plan)
-        elif kind == "GATConv":
-            op = _gat_operator(data, plan.N)
-        elif kind == "SimplifiedPNAConv":
-            deg, has_in = self._degrees(plan)
-        drop = self.dropout if train else 0.0
-        snap = self._dropout_begin(h.device) if drop else None
-        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
-            res = None if drop else h                   # dropout sits between the ReLU and the residual: the add moves into its launch
-            h_in = h
-            if kind == "GINConv":
+            self._check_edge_ids(ea, c.status)
+        if kind == "GINConv":
+            def layer(li, h, res):
+                conv = convs[li]
                 u = ops.gin_aggregate(h, plan, conv.layer.eps.detach())
                 u = ops.masked_linear(u, pack(conv.nn.layers[0]), relu=True)
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=res)
-            elif kind == "GCNConv":
-                h = lin_bn(ops.gcn_pyg_propagate(h, plan, dis), conv.layer.lin, norm, residual=res)
-            elif kind == "GATConv":
-                L = conv.layer
+                return lin_bn(u, conv.nn.layers[1], norms[li], residual=res)
+        elif kind == "GCNConv":
+            dis = ops.gcn_pyg_coef(plan)
+
+            def layer(li, h, res):
+                return lin_bn(ops.gcn_pyg_propagate(h, plan, dis), convs[li].layer.lin, norms[li], residual=res)
+        elif kind == "GATConv":
+            op = _gat_operator(c.data, plan.N)
+
+            def layer(li, h, res):
+                L = convs[li].layer
                 f = ops.masked_linear(h, pack(L.lin_src))
                 z, _ = ops.gat_conv(f, L.att_src.detach(), L.att_dst.detach(), None, op, L.heads, None, L.negative_slope)
-                h = bn_act(z, norm, res)
-            else:
-                d = h.shape[1]
+                return c.bn_act(z, norms[li], res)
+        else:
+            deg, has_in = self._degrees(plan)
+
+            def layer(li, h, res):
+                conv, d = convs[li], h.shape[1]
                 W1 = conv.pre_nn.layers[0].weight.detach()
-                pab = cached(("ab", id(conv)), lambda: ops.PackedLinear(ops.pack_weight(torch.cat([W1[:, :d], W1[:, d:2 * d]], 0).contiguous()),
-                                                                        6 * d, d, None))
-                pq = cached(("q", id(conv)), lambda: ops.PackedLinear(ops.pack_weight(W1[:, 2 * d:].contiguous()), 3 * d, d, None))
+                pab = c.cached(("ab", id(conv)), lambda: ops.PackedLinear(ops.pack_weight(torch.cat([W1[:, :d], W1[:, d:2 * d]], 0).contiguous()),
+                                                                          6 * d, d, None))
+                pq = c.cached(("q", id(conv)), lambda: ops.PackedLinear(ops.pack_weight(W1[:, 2 * d:].contiguous()), 3 * d, d, None))
                 ab = ops.masked_linear(h, pab)                                        # [N, 2C]: A | B
-                q = ops.masked_linear(encode(enc, ea), pq)                            # [E, C]
+                q = ops.masked_linear(c.encode(encs[li], ea), pq)                     # [E, C]
                 a, b = ab[:, :3 * d], ab[:, 3 * d:]
                 bn0 = conv.pre_nn.norms[0]
-                if fold:
-                    f0 = bn_of(bn0)
-                    r = ops.spna_mean(a, b, q, plan, f0.scale, f0.shift)
-                else:
+                if c.train:
                     state, _ = ops.spna_stats(a, b, q, plan, bn0)
                     r = ops.spna_mean(a, b, q, plan, state[3], state[4])
+                else:
+                    f0 = c.bn_of(bn0)
+                    r = ops.spna_mean(a, b, q, plan, f0.scale, f0.shift)
                 m = ops.masked_linear(r, pack(conv.pre_nn.layers[1]), has_in, 1)      # W2 mean + b2 [deg > 0]
-                de = ops.embedding_sum(deg, [conv.deg_embedder.weight.detach()], status)
+                de = ops.embedding_sum(deg, [conv.deg_embedder.weight.detach()], c.status)
                 u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0])
-                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=res)
-            if drop:
-                h = ops.dropout(h, drop, snap, li, residual=h_in)
-        pooled = ops.segment_pool(h, plan, self.pooling)
-        if self.pooling == "mean":
-            size = ops.embedding_sum(self._graph_sizes(plan), [self.size_embedder.weight.detach()], status)
-            pooled = ops.masked_affine(pooled, residual=size)
-        oe = self.output_encoder
-        y = ops.masked_linear(lin_bn(pooled, oe.layers[0], oe.norms[0]), pack(oe.layers[1]))
-        plan.check()
-        return y
+                return lin_bn(u, conv.post_nn.layers[1], norms[li], residual=res)
+        return layer
 
-    # ------------------------------------------------------------------ differentiable train mode
-    def _forward_grad(self, data, ea, additional_x):
-        """Under the switch `_bucket` (train_graph.BucketedStep) `data` is a padded batch, as in pyg.GNN._forward_grad: validity vectors
-        on every op over node / edge / graph rows, ids and degrees of invalid rows forced to 0.  Per conv type:
+    def _conv_grad(self, c, ea):
+        """Differentiable train mode.  Under a bucketed step (c.pad: the padded batch of train_graph.BucketedStep) per conv type:
           GINConv   the padding self loops feed padding nodes only, whose rows are zeros; the Linears mask them.
           GCNConv   needs no kernel of its own: sn_gcn_pyg_coef_f32 / _propagate_f32 skip self loops, and padding edges are self loops
                     on padding nodes, so the degree of every valid node and every term of its sum are the eager step's.
           GATConv   the operator pair comes from ops.csr_drop_loops (fixed shapes, no host read) in place of _gat_operator.
-          SimplifiedPNAConv   the edge-row BatchNorm runs its masked launches (statistics and adjoint sums over counts[1] rows)."""
-        if self.gnn_type == "GINEConv":
-            return super()._forward_grad(data, ea, additional_x)
-        from . import autograd as AG
-        from . import train_stage as T
+          SimplifiedPNAConv   the edge-row BatchNorm runs its masked launches (statistics and adjoint sums over counts[1] rows); degrees
+                    of invalid rows are forced to 0."""
         kind = self.gnn_type
-        B = int(data.num_graphs)
-        pad = getattr(self, "_bucket", None)
-        vN, vE, vB, k1 = self._bucket_validity(pad)
-        plan = ops.build_plan(data.batch, data.edge_index, B, 0)
-        rplan = ops.build_plan(data.batch, data.edge_index.flip(0).contiguous(), B, 0)      # out-edge CSR
-        status = plan.status[5:6]
-        d = self.linear.weight.shape[0]
-        stage = T.supported(d, d)
-        ea = self._valid_ids(ea, vE) if not ea.dtype.is_floating_point else ea
-
-        def lin_bn(x, lin, norm, relu=True, residual=None, v=None):
-            kv = 0 if v is None else k1
-            if isinstance(norm, _Identity):
-                y = AG.linear(x, lin.weight, lin.bias, v, kv, relu=relu)
-                return y if residual is None else AG.masked_add(y, residual, v, kv)
-            if stage and T.supported(lin.weight.shape[1], lin.weight.shape[0]):
-                return T.lin_bn(x, lin, norm, v, kv, relu=relu, residual=residual)
-            return AG.linear_bn_act(x, lin.weight, lin.bias, norm, v, kv, relu=relu, residual=residual)
-
-        def encode(enc, v, valid=None):
-            if isinstance(enc, DiscreteEncoder):
-                return AG.embedding_sum(v, [e.weight for e in enc.embeddings], status)
-            return lin_bn(v.contiguous(), enc.layers[0], enc.norms[0], v=valid)
-
-        ids = self._node_ids(data)
-        h = encode(self.input_encoder, ids if ids.dtype.is_floating_point else self._valid_ids(ids, vN), vN)
-        if isinstance(self.input_encoder, DiscreteEncoder):
-            h = AG.mask_rows(h, vN, k1)             # (padded batch: the table rows of id 0 on padding nodes become zeros)
-        if additional_x is not None:
-            h = AG.linear(torch.cat([h, additional_x], dim=-1), self.linear.weight, self.linear.bias, vN, k1)
+        if kind == "GINEConv":
+            return super()._conv_grad(c, ea)
+        plan, rplan, pad, vN, vE, k1, lin_bn = c.plan, c.rplan, c.pad, c.vN, c.vE, c.k1, c.lin_bn
+        encs, convs, norms = list(self.edge_encoders), list(self.convs), list(self.norms)
         if kind != "SimplifiedPNAConv":
-            self._check_edge_ids(ea, status)
-        if kind == "GCNConv":
+            self._check_edge_ids(ea, c.status)
+        if kind == "GINConv":
+            def layer(li, h, res):
+                conv = convs[li]
+                l0 = conv.nn.layers[0]
+                u = AG.gin_aggregate(h, conv.layer.eps, plan, rplan)
+                u = AG.linear(u, l0.weight, l0.bias, vN, k1, relu=True)
+                return lin_bn(u, conv.nn.layers[1], norms[li], vN, residual=res)
+        elif kind == "GCNConv":
             dis = ops.gcn_pyg_coef(plan)
+
+            def layer(li, h, res):
+                return lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), convs[li].layer.lin, norms[li], vN, residual=res)
         elif kind == "GATConv":
-            op = _gat_operator(data, plan.N) if pad is None else ops.csr_drop_loops(plan, rplan)
-        elif kind == "SimplifiedPNAConv":
+            op = _gat_operator(c.data, plan.N) if pad is None else ops.csr_drop_loops(plan, rplan)
+
+            def layer(li, h, res):
+                L = convs[li].layer
+                f = AG.linear(h, L.lin_src.weight, None, vN, k1)
+                z = AG.gat_conv(f, L.att_src, L.att_dst, None, op, L.heads, None, L.negative_slope)
+                return AG.bn_act(z, norms[li], vN, k1, relu=True, residual=res)
+        else:
+            d = self.linear.weight.shape[0]
             deg, has_in = self._degrees(plan)
             if pad is not None:
                 # (a padding node can carry hundreds of padding edges — all of them when N_cap - N = 1 — and deg_embedder has 200 rows)
                 deg, has_in = self._valid_ids(deg, vN), self._valid_ids(has_in, vN)
-        drop = self.dropout
-        snap = self._dropout_begin(h.device) if drop else None
-        for li, (enc, conv, norm) in enumerate(zip(self.edge_encoders, self.convs, self.norms)):
-            res = None if drop else h
-            h_in = h
-            if kind == "GINConv":
-                u = AG.gin_aggregate(h, conv.layer.eps, plan, rplan)
-                u = AG.linear(u, conv.nn.layers[0].weight, conv.nn.layers[0].bias, vN, k1, relu=True)
-                h = lin_bn(u, conv.nn.layers[1], norm, residual=res, v=vN)
-            elif kind == "GCNConv":
-                h = lin_bn(AG.gcn_pyg_propagate(h, plan, rplan, dis), conv.layer.lin, norm, residual=res, v=vN)
-            elif kind == "GATConv":
-                L = conv.layer
-                f = AG.linear(h, L.lin_src.weight, None, vN, k1)
-                z = AG.gat_conv(f, L.att_src, L.att_dst, None, op, L.heads, None, L.negative_slope)
-                h = AG.bn_act(z, norm, vN, k1, relu=True, residual=res)
-            else:
+
+            def layer(li, h, res):
+                conv = convs[li]
                 W1 = conv.pre_nn.layers[0].weight
                 ab = AG.linear(h, torch.cat([W1[:, :d], W1[:, d:2 * d]], 0), None, vN, k1)
-                q = AG.linear(encode(enc, ea, vE), W1[:, 2 * d:], None, vE, k1)
+                q = AG.linear(c.encode(encs[li], ea, vE), W1[:, 2 * d:], None, vE, k1)
                 if pad is None:
                     r = AG.spna_mean(ab, q, conv.pre_nn.norms[0], plan, rplan)
                 else:
                     r = AG.spna_mean(ab, q, conv.pre_nn.norms[0], plan, rplan, vN, pad.counts)
                 l1 = conv.pre_nn.layers[1]
                 m = AG.linear(r, l1.weight, l1.bias, has_in, 1)
-                de = AG.embedding_sum(deg, [conv.deg_embedder.weight], status)
-                u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0], v=vN)
-                h = lin_bn(u, conv.post_nn.layers[1], norm, residual=res, v=vN)
-            if drop:
-                # (the mask is a function of the logical element index and valid rows come first: the padded step draws the eager masks)
-                h = AG.dropout(h, drop, snap, li, residual=h_in)
-        return self._readout_grad(h, plan, status, lin_bn, vB, k1)
+                de = AG.embedding_sum(deg, [conv.deg_embedder.weight], c.status)
+                u = lin_bn(torch.cat([h, m, de], dim=-1), conv.post_nn.layers[0], conv.post_nn.norms[0], vN)
+                return lin_bn(u, conv.post_nn.layers[1], norms[li], vN, residual=res)
+        return layer
