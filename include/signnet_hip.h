@@ -443,6 +443,21 @@ int sn_embedding_sum_f32(const int64_t* idx, int ldi, int nf, int64_t R, const f
 int sn_segment_pool_f32(const float* x, int64_t B, int C, const int32_t* graph_ptr, int mode,
                         float* out, void* stream);
 
+/* The read-out modes of the DGL tree's nets (dgl.sum_nodes / mean_nodes / max_nodes): the value of `pool_mean` of
+ * sn_gin_net_fused_f32 / sn_transformer_net_fused_f32 and of sn_gatedgcn_params.readout_mean. */
+#define SN_READOUT_SUM 0
+#define SN_READOUT_MEAN 1
+#define SN_READOUT_MAX 2
+
+/* Graph max pooling (dgl.max_nodes): out[g, c] = max over the rows graph_ptr[g] .. graph_ptr[g+1]-1 of x[row, c]; arg[g, c] (int32,
+ * may be NULL: not written) is the row that attains it.  Of equal values the lowest row wins; a NaN among the rows gives NaN and the
+ * first NaN row; a graph without rows gives 0 and arg -1.  128-bit loads where C % 4 == 0 and x is 16-byte aligned.  No atomics. */
+int sn_segment_max_f32(const float* x, int64_t B, int C, const int32_t* graph_ptr, float* out, int32_t* arg, void* stream);
+
+/* Its adjoint: dx[row, c] = dy[g, c] where arg[g, c] == row, else 0, for every row of [graph_ptr[0], graph_ptr[B]) — all of them are
+ * written here (no memset in front), one winner per (graph, channel), no atomics. */
+int sn_segment_max_bwd_f32(const float* dy, const int32_t* arg, int64_t B, int C, const int32_t* graph_ptr, float* dx, void* stream);
+
 /* BasisNet: the five equivariant 2->1 contractions of a stack of n x n matrices (eigenspace projectors).
  * Replaces contractions_2_to_1 (LearningFilters/ign.py:344-374, normalization 'inf'), called from
  * layer_2_to_1.forward (ign.py:117-128):  ops[b, i, :] = [X_ii, tr(X)/n, rowsum_i/n, colsum_i/n, sum(X)/n^2],
@@ -649,7 +664,8 @@ int sn_gat_aggregate_bwd_f32(const float* feat, const float* attn_l, const float
  *   wc:    [dp, dp] = C, (e0, e1, e2) = (bias, folded bn_node_e scale, shift)
  *   h_scale / h_shift: [dp] folded bn_node_h;  residual: 1 when the layer adds its input (gatedgcn_layer.py:29-31,70-72)
  * h [N, d]: embedded node features (read only); e [E, d]: embedded edge features, UPDATED IN PLACE layer by layer (edge-id order);
- * readout: mean (readout_mean = 1) or sum over the nodes, then Linear(d_out, ro_d1) ReLU Linear(ro_d1, ro_d2) ReLU Linear(ro_d2, 1)
+ * readout: readout_mean = SN_READOUT_SUM (0), SN_READOUT_MEAN (1) or SN_READOUT_MAX (2: the channel maximum over the graph's nodes, a NaN
+ * among them kept) over the nodes, then Linear(d_out, ro_d1) ReLU Linear(ro_d1, ro_d2) ReLU Linear(ro_d2, 1)
  * with plain row-major fp32 weights (layers/mlp_readout_layer.py).  y: [B]. */
 typedef struct {
   const void* wabde;
@@ -938,14 +954,15 @@ int sn_gnn_fused_front_f32(const sn_gnn_params* params, const void* x, int ldx, 
 
 /* The DGL tree's GIN base net, eval mode, one launch on the same per-graph stage kernel (GraphPrediction/nets/ZINC_graph_regression/
  * gin_net.py:83-126 with layers/gin_layer.py and layers/mlp.py:37-56, layers/mlp_readout_layer.py):
- *   h = embedding_h[atom] + embedding_p(p);  L x  h = MLP((1 + eps) h_i + sum_{j -> i} h_j);  readout sum / mean;  MLPReadout.
+ *   h = embedding_h[atom] + embedding_p(p);  L x  h = MLP((1 + eps) h_i + sum_{j -> i} h_j);  readout sum / mean / max;  MLPReadout.
  * params (all widths zero-padded to d = 64, 96 or 128 by the caller; the same struct as sn_gnn_fused_f32):
  *   node_discrete = 1, node_nf = 1, ntab[0] = embedding_h.weight [node_vocab, d]; edge_nf = 0; rho_out_w = NULL;
  *   lin_a = split-packed identity, lin_b = split-packed embedding_p.weight ([d, d], columns >= kp zero) with e0 = its bias;
  *   layers[l]: w1s = MLP.lins.0 with (e0, e1) = (1, bias), w2s = MLP.lins.1 with the MLP's eval BatchNorm (which follows the ReLU) folded
  *              in and (e0, e1) = (1, bias'); eps = the layer's eps scalar; nothing follows the second Linear;
  *   head_w1, head_mid: MLPReadout.FC_layers.0 / .1 with (e0, e1) = (1, bias); head_w2 = FC_layers.2 with e0 = bias; n_out = 1.
- * atom: int64 [N]; p: [N, ldp] positional encoding, kp columns used; pool_mean: readout 'mean' (else 'sum').  Graphs of more than 64 nodes
+ * atom: int64 [N]; p: [N, ldp] positional encoding, kp columns used; pool_mean: the readout, SN_READOUT_SUM (0), SN_READOUT_MEAN (1) or
+ * SN_READOUT_MAX (2: dgl.max_nodes).  Graphs of more than 64 nodes
  * or 192 in-edges, or an atom type outside the table: NaN row + status[3] bits, as sn_gnn_fused_f32. */
 int sn_gin_net_fused_f32(const sn_gnn_params* params, const void* head_mid, int pool_mean, const int64_t* atom, const float* p, int ldp,
                          int kp, const int32_t* graph_ptr, int64_t B, const int32_t* rowptr, const int32_t* col, const int32_t* eperm,
@@ -955,7 +972,7 @@ int sn_gin_net_fused_f32(const sn_gnn_params* params, const void* head_mid, int 
  * ZINC_graph_regression/transformer_net.py:88-140 with layers/transformer.py:150-312; the shipped shape: hidden 64, 8 heads, residual,
  * BatchNorm):
  *   h = embedding_h[atom] + embedding_p(p)  (or pe_proj(cat[.,.]): lin_a = pe_proj.weight[:, :64], lin_b = the two maps behind p folded);  L x [ Q, K, V -> edge attention with E_ij -> x1 = BatchNorm(h + O_h(a)) ->
- *   h = BatchNorm(x1 + FFN2(relu(FFN1(x1)))) ];  readout sum / mean;  MLPReadout.
+ *   h = BatchNorm(x1 + FFN2(relu(FFN1(x1)))) ];  readout sum / mean / max (pool_mean = SN_READOUT_*);  MLPReadout.
  * params: as sn_gin_net_fused_f32 with d = 64 (input stage, head, node table); layers[l].etab[0..7] = the layer's eight [64, 64] stage
  * matrices, split-packed: Q, K, V (no epilogue vectors), O_h with (e0, e1, e2) = (bias, BatchNorm1 scale, shift), FFN_h_layer1 rows
  * [0, 64) and [64, 128) with e0 = their bias halves, FFN_h_layer2 columns [0, 64) (no vectors) and [64, 128) with (e0, e1, e2) = (bias,

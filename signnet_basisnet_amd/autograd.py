@@ -470,6 +470,31 @@ def segment_pool(h, plan, mode="add"):
     return _SegmentPool.apply(h, plan, mode)
 
 
+class _SegmentMax(Function):
+    """dgl.max_nodes as an autograd node: the forward keeps the winning rows (arg), not h; the gradient goes to that one row per
+    (graph, channel) — DGL's segment reduce, not the even split among ties of scatter_reduce('amax')."""
+
+    @staticmethod
+    def forward(ctx, h, plan):
+        out, arg = ops.segment_max(_c(h), plan, want_arg=True)
+        ctx.meta = (plan, arg, h.shape)
+        ctx.mark_non_differentiable(arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        plan, arg, shape = ctx.meta
+        g = _c(g)
+        dx = torch.empty(shape, dtype=torch.float32, device=g.device)
+        check(lib().sn_segment_max_bwd_f32(ptr(g), ptr(arg), plan.B, g.shape[-1], ptr(plan.graph_ptr), ptr(dx), stream()),
+              "sn_segment_max_bwd_f32")
+        return dx, None
+
+
+def segment_max(h, plan):
+    return _SegmentMax.apply(h, plan)
+
+
 class _SegmentBcastAdd(Function):
     """y = act(x1 + x2[graph(row)]): the `x1 + x2` of the DeepSets / IGN layers (x2 = a per-graph row broadcast over the graph's
     nodes; LearningFilters/models.py:74-77, ign.py:330-335).  d x1 = dy', d x2 = segment sum of dy' (dy' = dy masked by the ReLU)."""

@@ -31,6 +31,11 @@ __device__ __forceinline__ void lds_st4(float* p, f32x4 v) {
 __device__ __forceinline__ f32x4 relu4(f32x4 v) {
   return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
 }
+// the larger of two values, a NaN in either kept (torch.amax; fmaxf would drop it): the 'max' readout of the DGL nets' one-launch kernels
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 b) {
+  return f32x4{nan_max(a[0], b[0]), nan_max(a[1], b[1]), nan_max(a[2], b[2]), nan_max(a[3], b[3])};
+}
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 

@@ -233,8 +233,22 @@ __global__ __launch_bounds__(GG_ROWS * 4, 1) void k_gatedgcn_net(GatedStruct S, 
       SN_ACCUM(5, pt);
     }
     SN_STAMP(9);
-    // ------------------------------------------------------------------ readout: mean / sum over the nodes, MLPReadout
+    // ------------------------------------------------------------------ readout: mean / sum / max over the nodes, MLPReadout
     {
+      const bool rmax = P.readout_mean == SN_READOUT_MAX;       // (uniform over the launch)
+      if (rmax) {
+        // rows outside the graph contribute -inf; a NaN among the graph's rows is kept, as sn_segment_max_f32 keeps it
+#pragma unroll
+        for (int kk = 0; kk < NT; ++kk) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            float v = valid ? h[kk][t] : -INFINITY;
+            v = nan_max(v, __shfl_xor(v, 1, 64)); v = nan_max(v, __shfl_xor(v, 2, 64));
+            v = nan_max(v, __shfl_xor(v, 4, 64)); v = nan_max(v, __shfl_xor(v, 8, 64));
+            if (li == 0) red[wave * D + 16 * kk + 4 * g + t] = v;
+          }
+        }
+      } else {
 #pragma unroll
       for (int kk = 0; kk < NT; ++kk) {
 #pragma unroll
@@ -244,13 +258,20 @@ __global__ __launch_bounds__(GG_ROWS * 4, 1) void k_gatedgcn_net(GatedStruct S, 
           if (li == 0) red[wave * D + 16 * kk + 4 * g + t] = v;
         }
       }
+      }
       __syncthreads();
       float* v0 = red + 4 * D;          // [<= 128] pooled / hidden vectors of the readout MLP
       float* v1 = v0 + 128;
       if (threadIdx.x < D) {
         const int c = threadIdx.x;
-        float s = (red[c] + red[D + c]) + (red[2 * D + c] + red[3 * D + c]);
-        if (P.readout_mean) s = s / (float)(n > 0 ? n : 1);
+        float s;
+        if (rmax) {
+          s = nan_max(nan_max(red[c], red[D + c]), nan_max(red[2 * D + c], red[3 * D + c]));
+          if (n <= 0) s = 0.f;          // a graph without nodes reads 0, as sum and mean do
+        } else {
+          s = (red[c] + red[D + c]) + (red[2 * D + c] + red[3 * D + c]);
+          if (P.readout_mean) s = s / (float)(n > 0 ? n : 1);
+        }
         v0[c] = s;
       }
       __syncthreads();

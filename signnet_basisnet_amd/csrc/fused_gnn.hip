@@ -59,7 +59,7 @@ struct GnnStruct {
   int32_t* flags_host;
   int rho_ld, rho_w;      // row stride / width of rho_sum (the GINE net: both d; the DGL GIN net: the positional encoding [N, k])
   const void* head_mid;   // DGL GIN net: the middle Linear of MLPReadout (split-packed, (e0, e1) = (1, bias))
-  int pool_mean;          // DGL GIN net: readout 'mean' instead of 'sum'
+  int pool_mean;          // DGL nets: the readout, SN_READOUT_SUM / _MEAN / _MAX
   const unsigned char* front;   // front records of the batch (gnn_front.hpp), written by the plan launch; NULL: none
   long long front_stride;
 };

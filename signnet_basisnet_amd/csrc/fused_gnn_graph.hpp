@@ -778,18 +778,34 @@ __device__ __forceinline__ void gnn_graph(const GnnStruct& S, const sn_gnn_param
   float* PS = reinterpret_cast<float*>(SA + 16 * SP_STRIDE);
   {
     const int pj = threadIdx.x / (D / 4), pc4 = threadIdx.x % (D / 4);
+    // the DGL nets' readout 'max' (S.pool_mean == SN_READOUT_MAX): the same sixteen partials with max and -inf — a NaN among the rows
+    // is kept, a graph without nodes reads 0
+    bool pmax = false;
+    if constexpr (DGL) pmax = S.pool_mean == SN_READOUT_MAX;
     if (pj < 16) {
       f32x4 s = zero4;
-      for (int r = pj; r < n; r += 16) s += lds_ld4(X1 + r * LD + 4 * pc4);
+      if (pmax) {
+        s = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        for (int r = pj; r < n; r += 16) s = nan_max4(s, lds_ld4(X1 + r * LD + 4 * pc4));
+      } else {
+        for (int r = pj; r < n; r += 16) s += lds_ld4(X1 + r * LD + 4 * pc4);
+      }
       lds_st4(PS + pj * D + 4 * pc4, s);
     }
     lds_barrier();
     if (pj < 16) {
       f32x4 s = zero4;
       if (pj == 0) {
+        if (pmax) {
+          s = lds_ld4(PS + 4 * pc4);
+#pragma unroll
+          for (int j = 1; j < 16; ++j) s = nan_max4(s, lds_ld4(PS + j * D + 4 * pc4));
+          if (n <= 0) s = zero4;
+        } else {
 #pragma unroll
         for (int j = 0; j < 16; ++j) s += lds_ld4(PS + j * D + 4 * pc4);
         if (DGL && S.pool_mean) s = s / (float)n;
+        }
       }
       sp_store4(SA, pj, pc4 >> 2, pc4 & 3, s);
     }

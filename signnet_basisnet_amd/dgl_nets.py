@@ -59,6 +59,9 @@ def handle_lap(model, batch_pos_enc, batch_graphs, device=None, *, u=None):
     return ops.lap_pe_transform(p, "canonical", graph_ptr=cached_plan(batch_graphs, p.shape[0]).graph_ptr)
 
 
+_READOUT_MODE = {"sum": 0, "mean": 1, "max": 2}       # SN_READOUT_* of signnet_hip.h; any other name pools as mean, as before
+
+
 def _check_pe_init(name, pe_init, lap_lspe, use_lapeig_loss):
     """What every net here covers of the PE switches: pe_init 'lap_pe' (the LapPE rows: sign_inv, sign_flip, abs_val, canonical, none)
     or 'no_pe' (the NoPE rows), without LSPE and without the eigenvector loss."""
@@ -142,6 +145,7 @@ class _DGLNet(ops.DropoutHolder, _PackCache, nn.Module):
     """What GINNet, GatedGCNNet, PNANet, TransformerNet and GATNet share.  A net's __init__ is `_init_common`, its own layers,
     `_init_tail`; its forward is `_prologue`, then `_encode` / its layer loop / `_readout` (or their `_grad` forms)."""
 
+    _max_readout = False     # readout 'max' is refused, as before; readout_models.py's subclasses set True
     _feature_dropout = False # dropout / in_feat_dropout > 0 are refused, as before; dropout_models.py's subclasses set True
     _sign_inv_factory = staticmethod(get_sign_inv_net)     # builds `sign_inv_net`; dropout_signinv.py's subclasses hand in their own
     _stage_cls = None        # the packer of the net's one-launch eval kernel (_FusedGin, _FusedGated, _FusedTransformer), if it has one
@@ -245,15 +249,21 @@ class _DGLNet(ops.DropoutHolder, _PackCache, nn.Module):
         return AG.masked_add(pp, x, vN, k1)
 
     def _readout(self, x, plan, first=None):
-        """mean / sum pooling over each graph's nodes, then MLPReadout.  `first`: the first Linear packed for padded channels of x."""
-        hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
+        """mean / sum / max pooling over each graph's nodes, then MLPReadout.  `first`: the first Linear packed for padded channels of x."""
+        if self.readout == "max":
+            hg = ops.segment_max(x, plan)
+        else:
+            hg = ops.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
             hg = ops.masked_linear(hg, first if i == 0 and first is not None else self._pk(fc), relu=i < len(fcs) - 1)
         return hg
 
     def _readout_grad(self, x, plan, vB, k1):
-        hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
+        if self.readout == "max":
+            hg = AG.segment_max(x, plan)
+        else:
+            hg = AG.segment_pool(x, plan, "mean" if self.readout != "sum" else "add")
         fcs = self.MLP_layer.FC_layers
         for i, fc in enumerate(fcs):
             hg = AG.linear(hg, fc.weight, fc.bias, vB, k1, relu=i < len(fcs) - 1)
@@ -357,7 +367,7 @@ class _FusedGin:
         P.head_w1 = hold(ops.pack_split(_pad_mat(fcs[0].weight, dp), ones, ops.pad_vec(fcs[0].bias, dp)))
         self.head_mid = hold(ops.pack_split(_pad_mat(fcs[1].weight, dp), ones, ops.pad_vec(fcs[1].bias, dp)))
         P.head_w2 = hold(ops.pack_split(_pad_mat(fcs[2].weight, dp), ops.pad_vec(fcs[2].bias, dp)))
-        self.params, self.kp, self.pool_mean = P, kp, 0 if net.readout == "sum" else 1
+        self.params, self.kp, self.pool_mean = P, kp, _READOUT_MODE.get(net.readout, 1)
         self.ok = True
 
     def run(self, plan, hidx, p):
@@ -382,7 +392,7 @@ class GINNet(_DGLNet):
         super().__init__()
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
-        self._init_common(p, "GINNet", [(p["readout"] == "max", "readout 'sum' or 'mean'")], in_feat_dropout="after_e")      # (embedding_e: unused by GIN)
+        self._init_common(p, "GINNet", [(p["readout"] == "max" and not self._max_readout, "readout 'sum' or 'mean'")], in_feat_dropout="after_e")      # (embedding_e: unused by GIN)
         self.layers = nn.ModuleList(
             [_GINConv(MLP(hidden, hidden, hidden, 2, use_bn=self.batch_norm, dropout=self.p_drop, activation="relu")) for _ in range(self.n_layers - 1)] +
             [_GINConv(MLP(hidden, hidden, out_dim, 2, use_bn=self.batch_norm, dropout=self.p_drop, activation="relu"))])
@@ -561,7 +571,7 @@ class _FusedGated:
 
         dev = Ls[0].A.weight.device
         P = _GatedParamsC()
-        P.d, P.d_out, P.n_layers, P.readout_mean = d, Ls[-1].out_channels, len(Ls), 0 if net.readout == "sum" else 1
+        P.d, P.d_out, P.n_layers, P.readout_mean = d, Ls[-1].out_channels, len(Ls), _READOUT_MODE.get(net.readout, 1)
         P.ro_d1, P.ro_d2 = fcs[0].weight.shape[0], fcs[1].weight.shape[0]
         for i, fc in enumerate(fcs):
             setattr(P, f"ro_w{i}", hold(fc.weight.detach().float().contiguous()))
@@ -612,7 +622,7 @@ class GatedGCNNet(_DGLNet):
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
         self.pe_aggregate = p["pe_aggregate"]
-        self._init_common(p, "GatedGCNNet", [(p["readout"] == "max" or not p["edge_feat"] or not p["batch_norm"],
+        self._init_common(p, "GatedGCNNet", [((p["readout"] == "max" and not self._max_readout) or not p["edge_feat"] or not p["batch_norm"],
                                               "readout sum/mean, edge_feat=True, batch_norm=True")], in_feat_dropout="after_e")
         self.layers = nn.ModuleList([GatedGCNLayer(hidden, hidden, self.p_drop, True, residual=self.residual, graph_norm=False,
                                                    feature_dropout=self._feature_dropout)
@@ -786,7 +796,7 @@ class PNANet(_DGLNet):
         self._init_common(p, "PNANet", [
             (self.aggregators.split() != ["mean", "max", "min", "std"] or self.scalers.split() != ["identity", "amplification", "attenuation"],
              "aggregators 'mean max min std', scalers 'identity amplification attenuation'"),
-            (not (self.graph_norm and p["batch_norm"] and p["edge_feat"]) or p["gru"] or p["readout"] == "max",
+            (not (self.graph_norm and p["batch_norm"] and p["edge_feat"]) or p["gru"] or (p["readout"] == "max" and not self._max_readout),
              "graph_norm, batch_norm, edge_feat True; gru False; readout sum / mean"),
             (not (p["divide_input_first"] and p["divide_input_last"]), "divide_input_first / _last True (the shipped configs)")],
             edge_dim=edge_dim, in_feat_dropout="before_h")
@@ -1081,7 +1091,7 @@ class _FusedTransformer:
         P.head_w1 = hold(ops.pack_split(_pad_mat(fcs[0].weight, 64), ones, ops.pad_vec(fcs[0].bias, 64)))
         self.head_mid = hold(ops.pack_split(_pad_mat(fcs[1].weight, 64), ones, ops.pad_vec(fcs[1].bias, 64)))
         P.head_w2 = hold(ops.pack_split(_pad_mat(fcs[2].weight, 64), ops.pad_vec(fcs[2].bias, 64)))
-        self.params, self.kp, self.pool_mean = P, kp, 0 if net.readout == "sum" else 1
+        self.params, self.kp, self.pool_mean = P, kp, _READOUT_MODE.get(net.readout, 1)
         self.ok = True
 
     def run(self, plan, hidx, p, e_proj):
@@ -1118,7 +1128,7 @@ class TransformerNet(_DGLNet):
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
         self.layer_norm, self.pe_aggregate = p["layer_norm"], p["pe_aggregate"]
-        self._init_common(p, "TransformerNet", [(p["readout"] == "max" or not p["edge_feat"], "readout sum / mean, edge_feat True")],
+        self._init_common(p, "TransformerNet", [((p["readout"] == "max" and not self._max_readout) or not p["edge_feat"], "readout sum / mean, edge_feat True")],
                           in_feat_dropout="after_e")
         self.layers = nn.ModuleList([BatchedTransformerLayer(hidden, hidden, p["n_heads"], p["full_graph"], use_edge=True)
                                      for _ in range(self.n_layers - 1)] +
@@ -1434,7 +1444,7 @@ class GATNet(_DGLNet):
         p = net_params
         hidden, out_dim = p["hidden_dim"], p["out_dim"]
         H = self.n_heads = p["n_heads"]
-        self._init_common(p, "GATNet", [(p["readout"] == "max", "readout sum / mean")], in_feat_dropout="after_e")
+        self._init_common(p, "GATNet", [(p["readout"] == "max" and not self._max_readout, "readout sum / mean")], in_feat_dropout="after_e")
         #                     (batch_norm, residual: read and ignored by the reference too)
         if self.n_layers < 2:
             raise ValueError("GATNet: L >= 2 (gat_net.py:62-66 always builds a first and a last layer)")

@@ -101,8 +101,17 @@ SIGN_INV_DROPOUT_OVERRIDES = {
 }
 
 
-def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False, sign_inv_dropout=False) -> dict:
-    """What `baselines` (False, True or "all"), `gnn_types`, `feature_dropout` and `sign_inv_dropout` add to ALIASES[tree]."""
+# Opt-in with `max_readout=True` (the runner's `--max-readout`; implies sign_inv_dropout), on top of the flags above: the five base nets
+# from readout_models.py, which take `--readout max` next to `sum` / `mean`.  Without the flag every name resolves exactly as before and
+# `max` is refused as before.
+MAX_READOUT_OVERRIDES = {
+    "graphprediction": {"nets.ZINC_graph_regression." + m: _PKG + ".max_readout_nets"
+                        for m in ("gin_net", "gatedgcn_net", "pna_net", "transformer_net", "gat_net")},
+}
+
+
+def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False) -> dict:
+    """What `baselines` (False, True or "all"), `gnn_types`, `feature_dropout`, `sign_inv_dropout` and `max_readout` add to ALIASES[tree]."""
     if baselines not in (False, True, "all"):
         raise ValueError(f"baselines must be False, True or 'all', got {baselines!r}")
     table = {}
@@ -113,10 +122,12 @@ def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False
         table.update(ALL_BASELINE_OVERRIDES.get(tree, {}))
     if gnn_types:
         table.update(GNN_TYPE_OVERRIDES.get(tree, {}))
-    if feature_dropout or sign_inv_dropout:
+    if feature_dropout or sign_inv_dropout or max_readout:
         table.update(FEATURE_DROPOUT_OVERRIDES.get(tree, {}))
-    if sign_inv_dropout:
+    if sign_inv_dropout or max_readout:
         table.update(SIGN_INV_DROPOUT_OVERRIDES.get(tree, {}))
+    if max_readout:
+        table.update(MAX_READOUT_OVERRIDES.get(tree, {}))
     return table
 
 
@@ -155,10 +166,10 @@ class _AliasLoader(importlib.abc.Loader):
 class AliasFinder(importlib.abc.MetaPathFinder):
     """Answers the names of `ALIASES[tree]` and nothing else; every other import goes on to the normal finders."""
 
-    def __init__(self, tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False):
+    def __init__(self, tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False):
         self.tree = tree
         self.table = dict(ALIASES[tree])
-        self.table.update(_baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout))
+        self.table.update(_baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -167,17 +178,18 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         return importlib.machinery.ModuleSpec(fullname, _AliasLoader(impl), origin=impl)
 
 
-def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False) -> AliasFinder:
+def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False) -> AliasFinder:
     """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
     `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN) and rebinds those of `BASELINE_OVERRIDES[tree]` (LearningFilters' `models`, with
     the four polynomial-filter baselines); baselines="all" rebinds those of `ALL_BASELINE_OVERRIDES[tree]` on top (LearningFilters'
     `models` with GatNet and ARMANet too); gnn_types=True rebinds those of `GNN_TYPE_OVERRIDES[tree]` (GINESignNetPyG's `core.model` with
     the plain GNN for every model.gnn_type); feature_dropout=True rebinds those of `FEATURE_DROPOUT_OVERRIDES[tree]` (the models that take
     train-mode dropout); sign_inv_dropout=True implies feature_dropout and rebinds those of `SIGN_INV_DROPOUT_OVERRIDES[tree]` on top
-    (GraphPrediction's base nets and `sign_inv_net` with dropout in the sign-invariant encoder too); a finder installed with less is
-    extended in place."""
+    (GraphPrediction's base nets and `sign_inv_net` with dropout in the sign-invariant encoder too); max_readout=True implies
+    sign_inv_dropout and rebinds those of `MAX_READOUT_OVERRIDES[tree]` on top (GraphPrediction's base nets with `--readout max`); a finder
+    installed with less is extended in place."""
     shim_dir(tree)
-    extra = _baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout)
+    extra = _baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
             for name, impl in extra.items():
@@ -189,15 +201,18 @@ def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, 
                     continue                    # already bound for gnn_types: a later call without the flag takes nothing away
                 bound_for_dropout = FEATURE_DROPOUT_OVERRIDES.get(tree, {}).get(name)
                 bound_for_signinv = SIGN_INV_DROPOUT_OVERRIDES.get(tree, {}).get(name)
-                if bound_for_signinv is not None and f.table.get(name) == bound_for_signinv:
-                    continue                    # already bound for sign_inv_dropout: a later call with less takes nothing away
-                if bound_for_dropout is not None and f.table.get(name) == bound_for_dropout and impl != bound_for_signinv:
+                bound_for_max = MAX_READOUT_OVERRIDES.get(tree, {}).get(name)
+                if bound_for_max is not None and f.table.get(name) == bound_for_max:
+                    continue                    # already bound for max_readout: a later call with less takes nothing away
+                if bound_for_signinv is not None and f.table.get(name) == bound_for_signinv and impl != bound_for_max:
+                    continue                    # likewise for sign_inv_dropout
+                if bound_for_dropout is not None and f.table.get(name) == bound_for_dropout and impl not in (bound_for_signinv, bound_for_max):
                     continue                    # likewise for feature_dropout
                 if f.table.get(name) != impl:
                     f.table[name] = impl
                     sys.modules.pop(name, None)
             return f
-    finder = AliasFinder(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout)
+    finder = AliasFinder(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout)
     sys.meta_path.insert(0, finder)
     for name in finder.table:           # a module imported before install() would otherwise stay bound to the tree's file
         sys.modules.pop(name, None)

@@ -34,6 +34,11 @@ base nets and `nets.ZINC_graph_regression.sign_inv_net` from `dropout_signinv.py
 
     cd <reference>/GraphPrediction  && python -m signnet_basisnet_amd.dropin.run --sign-inv-dropout main_ZINC_graph_regression.py --config configs/gatedgcn/GatedGCN_ZINC_LapPE_signinv_GIN.json --dropout 0.1
 
+`--max-readout` (implies `--sign-inv-dropout`) rebinds the names of `dropin.MAX_READOUT_OVERRIDES` on top: GraphPrediction's five base nets
+from `readout_models.py`, which take `--readout max` (dgl.max_nodes) next to `sum` / `mean`; without it `max` is refused as before:
+
+    cd <reference>/GraphPrediction  && python -m signnet_basisnet_amd.dropin.run --max-readout main_ZINC_graph_regression.py --config configs/gatedgcn/GatedGCN_ZINC_NoPE.json --readout max
+
 `--attn-dropout=counter` makes "counter" the `attn_dropout_source` of every `pyg.SignNetGNN` the run constructs (Alchemy, GINESignNetPyG):
 the train-mode attention-dropout masks are evaluated inside the attention kernels from (seed, step) — seed torch.initial_seed() unless
 the script calls `seed_dropout` — instead of drawn with torch's device generator.
@@ -49,7 +54,7 @@ from . import ALIASES, SCRIPTS, install
 
 def main(argv=None) -> None:
     argv = list(sys.argv[1:] if argv is None else argv)
-    tree, baselines, gnn_types, feature_dropout, sign_inv_dropout = None, False, False, False, False
+    tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout = None, False, False, False, False, False
     while argv and argv[0].startswith("--"):        # the runner's own options come before the script
         if argv[0] == "--baselines":
             baselines, argv = True, argv[1:]
@@ -59,6 +64,8 @@ def main(argv=None) -> None:
             feature_dropout, argv = True, argv[1:]
         elif argv[0] == "--sign-inv-dropout":
             feature_dropout, sign_inv_dropout, argv = True, True, argv[1:]
+        elif argv[0] == "--max-readout":
+            feature_dropout, sign_inv_dropout, max_readout, argv = True, True, True, argv[1:]
         elif argv[0].startswith("--attn-dropout="):
             from ..pyg import SignNetGNN
             try:
@@ -80,7 +87,7 @@ def main(argv=None) -> None:
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] [--sign-inv-dropout] [--attn-dropout=counter] <entry script> "
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] [--sign-inv-dropout] [--max-readout] [--attn-dropout=counter] <entry script> "
                          "[script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
     if argv[0] == "-m":
@@ -93,7 +100,8 @@ def main(argv=None) -> None:
             tree = SCRIPTS.get(module.rsplit(".", 1)[-1] + ".py")
             if tree is None:
                 raise SystemExit(f"cannot tell the reference tree from the module {module!r}; pass --tree " + "|".join(sorted(ALIASES)))
-        install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout, sign_inv_dropout=sign_inv_dropout)
+        install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout, sign_inv_dropout=sign_inv_dropout,
+                max_readout=max_readout)
         if os.getcwd() in sys.path:
             sys.path.remove(os.getcwd())
         sys.path.insert(0, os.getcwd())
@@ -107,7 +115,8 @@ def main(argv=None) -> None:
         tree = SCRIPTS.get(os.path.basename(script))
         if tree is None:
             raise SystemExit(f"cannot tell the reference tree from {os.path.basename(script)!r}; pass --tree " + "|".join(sorted(ALIASES)))
-    install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout, sign_inv_dropout=sign_inv_dropout)
+    install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout, sign_inv_dropout=sign_inv_dropout,
+                max_readout=max_readout)
     script_dir = os.path.dirname(os.path.abspath(script))
     for p in (os.getcwd(), script_dir):          # script_dir ends up first, as under `python script.py`
         if p in sys.path:

@@ -18,7 +18,7 @@ from ._lib import (EPI_AFFINE, EPI_BIAS, EPI_LEAKY, EPI_RELU, EPI_RELU_PRE, EPI_
 
 __all__ = ["KernelTimer", "KERNEL_ROOFLINE", "GraphPlan", "PlanBins", "build_plan", "pack_eig", "pack_weight", "gin_aggregate", "gine_aggregate",
            "masked_linear", "masked_colstats", "masked_affine", "masked_layernorm", "set_attention",
-           "slot_sum", "embedding_sum", "segment_pool", "PackedLinear",
+           "slot_sum", "embedding_sum", "segment_pool", "segment_max", "PackedLinear",
            "EPI_BIAS", "EPI_RELU_PRE", "EPI_AFFINE", "EPI_RELU", "EPI_RESIDUAL"]
 
 
@@ -893,6 +893,19 @@ def segment_pool(x, plan: GraphPlan, mode="add"):
         check(lib().sn_segment_pool_f32(ptr(x), plan.B, x.shape[1], ptr(plan.graph_ptr), 1 if mode == "mean" else 0,
                                         ptr(out), stream()), "sn_segment_pool_f32")
     return out
+
+
+def segment_max(x, plan: GraphPlan, want_arg=False):
+    """dgl.max_nodes: out[g, :] = the channel maximum over graph g's rows of x (sn_segment_max_f32: of equal values the lowest row, a NaN
+    kept, an empty graph 0).  want_arg: -> (out, arg), arg [B, C] int32 the row that attains it (-1: empty graph)."""
+    require_cuda(x)
+    x = _f32c(x, "x")
+    out = torch.empty(plan.B, x.shape[1], dtype=torch.float32, device=x.device)
+    arg = torch.empty(plan.B, x.shape[1], dtype=torch.int32, device=x.device) if want_arg else None
+    with _span("sn_segment_max_f32"):
+        check(lib().sn_segment_max_f32(ptr(x), plan.B, x.shape[1], ptr(plan.graph_ptr), ptr(out), ptr(arg), stream()),
+              "sn_segment_max_f32")
+    return (out, arg) if want_arg else out
 
 
 def ign_contract_2to1(X):
