@@ -19,19 +19,15 @@ from . import dgl_deepsigns as OD
 
 def gin_net(sd, src, dst, batch_num_nodes, h_idx, p, n_layers, readout="mean", training=False):
     """GINNet.forward (gin_net.py:80-139) for pe_init='lap_pe', lap_lspe=False.  p [N, pos_enc_dim] is the (already sign-invariant)
-    positional encoding; returns scores [B, 1]."""
-    h = sd["embedding_h.weight"][h_idx] + F.linear(p, sd["embedding_p.weight"], sd["embedding_p.bias"])
+    positional encoding (None: pe_init='no_pe'); readout 'sum' / 'mean' / 'max' (dgl.sum_nodes / mean_nodes / max_nodes); returns
+    scores [B, 1]."""
+    h = sd["embedding_h.weight"][h_idx]
+    if p is not None:                                                                   # (pe_init 'no_pe': h = embedding_h(h) alone)
+        h = h + F.linear(p, sd["embedding_p.weight"], sd["embedding_p.bias"])
     for l in range(n_layers):
         a = (1 + sd[f"layers.{l}.eps"]) * h + torch.zeros_like(h).index_add_(0, dst, h.index_select(0, src))
         h = OD.mlp(sd, f"layers.{l}.apply_func", a, 2, True, "relu", training)
-    bnn = torch.as_tensor(batch_num_nodes)
-    seg = torch.repeat_interleave(torch.arange(len(bnn)), bnn)
-    hg = torch.zeros(len(bnn), h.shape[1], dtype=h.dtype).index_add_(0, seg, h)
-    if readout != "sum":
-        hg = hg / bnn.to(h.dtype).clamp(min=1).unsqueeze(1)
-    y = torch.relu(F.linear(hg, sd["MLP_layer.FC_layers.0.weight"], sd["MLP_layer.FC_layers.0.bias"]))
-    y = torch.relu(F.linear(y, sd["MLP_layer.FC_layers.1.weight"], sd["MLP_layer.FC_layers.1.bias"]))
-    return F.linear(y, sd["MLP_layer.FC_layers.2.weight"], sd["MLP_layer.FC_layers.2.bias"])
+    return _mlp_readout(sd, _readout(h, batch_num_nodes, readout))
 
 
 def gin_net_with_sign_inv(sd, src, dst, batch_num_nodes, h_idx, pos_enc, n_layers, sign_inv_layers, k, readout="mean", training=False):
@@ -71,8 +67,9 @@ def gatedgcn_layer(sd, pfx, src, dst, h, e, batch_norm=True, residual=True, trai
 
 
 def gatedgcn_net(sd, src, dst, batch_num_nodes, h_idx, p, e_idx, n_layers, pe_aggregate="concat", readout="mean", training=False,
-                 out=None):
-    """GatedGCNNet.forward (gatedgcn_net.py:84-148) for pe_init='lap_pe', lap_lspe=False, edge_feat=True."""
+                 out=None, residual=True):
+    """GatedGCNNet.forward (gatedgcn_net.py:84-148) for pe_init='lap_pe', lap_lspe=False, edge_feat=True.  residual: net_params['residual']
+    (a layer whose widths differ has none either way, gatedgcn_layer.py:24-25)."""
     h = sd["embedding_h.weight"][h_idx]
     pp = F.linear(p, sd["embedding_p.weight"], sd["embedding_p.bias"])
     if pe_aggregate == "concat":
@@ -81,17 +78,10 @@ def gatedgcn_net(sd, src, dst, batch_num_nodes, h_idx, p, e_idx, n_layers, pe_ag
         h = h + pp
     e = sd["embedding_e.weight"][e_idx]
     for l in range(n_layers):
-        h, e = gatedgcn_layer(sd, f"layers.{l}", src, dst, h, e, True, True, training)
+        h, e = gatedgcn_layer(sd, f"layers.{l}", src, dst, h, e, True, residual, training)
     if out is not None:
         out["h_last"] = h
-    bnn = torch.as_tensor(batch_num_nodes)
-    seg = torch.repeat_interleave(torch.arange(len(bnn)), bnn)
-    hg = torch.zeros(len(bnn), h.shape[1], dtype=h.dtype).index_add_(0, seg, h)
-    if readout != "sum":
-        hg = hg / bnn.to(h.dtype).clamp(min=1).unsqueeze(1)
-    y = torch.relu(F.linear(hg, sd["MLP_layer.FC_layers.0.weight"], sd["MLP_layer.FC_layers.0.bias"]))
-    y = torch.relu(F.linear(y, sd["MLP_layer.FC_layers.1.weight"], sd["MLP_layer.FC_layers.1.bias"]))
-    return F.linear(y, sd["MLP_layer.FC_layers.2.weight"], sd["MLP_layer.FC_layers.2.bias"])
+    return _mlp_readout(sd, _readout(h, batch_num_nodes, readout))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -106,6 +96,10 @@ PNA_EPS = 1e-5        # pna_utils.py:9
 def _readout(h, batch_num_nodes, readout):
     bnn = torch.as_tensor(batch_num_nodes)
     seg = torch.repeat_interleave(torch.arange(len(bnn)), bnn)
+    if readout == "max":                                                                # dgl.max_nodes: per graph and channel
+        idx = seg.unsqueeze(1).expand(-1, h.shape[1])
+        hg = torch.full((len(bnn), h.shape[1]), float("-inf"), dtype=h.dtype).scatter_reduce(0, idx, h, reduce="amax")
+        return torch.where((bnn > 0).unsqueeze(1), hg, torch.zeros_like(hg))           # (a graph without nodes reads 0)
     hg = torch.zeros(len(bnn), h.shape[1], dtype=h.dtype).index_add_(0, seg, h)
     if readout != "sum":
         hg = hg / bnn.to(h.dtype).clamp(min=1).unsqueeze(1)
