@@ -1512,6 +1512,30 @@ int sn_bond_full_attention_bwd_f32(const float* Q, const float* K, const float* 
                                    const int32_t* graph_valid, const int32_t* edge_valid, float* dQ, float* dK, float* dV, float* dQ2,
                                    float* dK2, float* dT_real, float* dT_fake, float* dgamma, float* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * tanh / ELU of the DGL tree's sign-invariant encoders (`--sign_inv_activation`: layers/mlp.py:40-51, layers/gnns.py:23-26), with the
+ * eval-mode BatchNorm that follows the activation folded into the same launch, and their adjoint:
+ *   sn_act_affine_f32      y[r,c]  = rowvalid(r) ? fma(act(x[r,c]), scale[c], shift[c]) : 0                      x, y: [R, C]
+ *   sn_act_affine_bwd_f32  dx[r,c] = rowvalid(r) ? dy[r,c] * act'(a[r,c]) : 0,   a = act(x): the forward's output WITHOUT an affine
+ *                          tanh: act' = fma(-a, a, 1);   elu: act' = a > 0 ? 1 : a + 1
+ * (the adjoint is sn_act_affine_bwd_f32 because sn_act_bwd_f32 is the ReLU / LeakyReLU adjoint on the PRE-activation, above.)
+ * act: SN_ACT_TANH = tanhf(x); SN_ACT_ELU = x > 0 ? x : expm1f(x) (alpha = 1) — the accurate device-library functions, no fast-math
+ * intrinsic: a NaN stays a NaN, tanh(+-inf) = +-1, elu(+inf) = +inf, elu(-inf) = -1.  rowvalid is the (nvalid, K) row mask of
+ * sn_masked_affine_f32 (nvalid = NULL: every row; with nvalid, K > 0 and R < 2^31); invalid rows are written as 0 in both
+ * directions.  scale, shift: [C] each, or both NULL (y = act(x)); one of the two alone, or an act other than the two, is SN_ERR_ARG.
+ * The adjoint reads nothing but dy and the saved activation output.  x and y (dy / a and dx) must not overlap.  Three access paths
+ * with the same bits:
+ *   row-vector   C % 4 == 0, every ld % 4 == 0, every pointer (scale / shift included) 16-byte aligned: 128-bit accesses;
+ *   flat-vector  every ld == C (any C), the matrix pointers 16-byte aligned: one contiguous run moved in 128-bit accesses;
+ *   scalar       anything else: any ld >= C, 4-byte-aligned pointers.
+ * R = 0: SN_OK, no launch.  Columns C..ld of y / dx are never written.  No LDS, no atomics: repeated calls are bit-identical. */
+#define SN_ACT_TANH 1
+#define SN_ACT_ELU  2      /* alpha = 1: nn.ELU()'s default, the only one the reference builds */
+int sn_act_affine_f32(const float* x, int ldx, int64_t R, int C, const int32_t* nvalid, int K, int act, const float* scale,
+                      const float* shift, float* y, int ldy, void* stream);
+int sn_act_affine_bwd_f32(const float* dy, int lddy, const float* a, int lda, int64_t R, int C, const int32_t* nvalid, int K, int act,
+                          float* dx, int lddx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,8 @@ SIGNATURES = {
     "sn_bond_full_attention_f32": [_p, _p, _p, _p, _p, _l, _p, _p, _i, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "sn_bond_full_attention_bwd_f32": [_p, _p, _p, _p, _p, _l, _p, _p, _i, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "sn_act_affine_f32": [_p, _i, _l, _i, _p, _i, _i, _p, _p, _p, _i, _p],
+    "sn_act_affine_bwd_f32": [_p, _i, _p, _i, _l, _i, _p, _i, _i, _p, _i, _p],
 }
 _SPECIAL_RESTYPE = {"sn_last_error": C.c_char_p, "sn_packed_weight_floats": C.c_int64, "sn_evd_large_work_ints": C.c_int64,
                     "sn_gnn_front_bytes": C.c_int64, "sn_full_attention_bwd_scratch_floats": C.c_int64,

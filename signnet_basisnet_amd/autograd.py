@@ -1197,3 +1197,26 @@ def dropout(x, p, snap, site, residual=None):
     if p == 0.0:
         return x if residual is None else act_residual(x, residual)
     return _Dropout.apply(x, residual, p, snap, site)
+
+
+# ----------------------------------------------------------------------------- tanh / ELU (csrc/activation.hip)
+class _Activation(Function):
+    """act(x) on valid rows, 0 elsewhere.  Only the OUTPUT is saved: tanh' = 1 - a^2 and elu' = a > 0 ? 1 : a + 1 are functions of it."""
+
+    @staticmethod
+    def forward(ctx, x, act, nvalid, K):
+        a = ops.act_affine(_c(x), act, nvalid, K)
+        ctx.save_for_backward(a)
+        ctx.meta = (act, nvalid, K)
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        a, = ctx.saved_tensors
+        act, nvalid, K = ctx.meta
+        return ops.act_bwd(_c(g), a, act, nvalid, K), None, None, None
+
+
+def activation(x, act, nvalid=None, K=0):
+    """'tanh' | 'elu' (alpha 1) of the row matrix x on valid rows (sn_act_affine_f32 without an affine); one launch per direction."""
+    return _Activation.apply(x, act, nvalid, K)

@@ -64,10 +64,13 @@ class MLP(nn.Module):
     """Linear -> activation -> BatchNorm per hidden layer, final Linear (mlp.py:5-56); all Linears have bias."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, use_bn=False, use_ln=False, dropout=0.5,
-                 activation="relu", residual=False):
+                 activation="relu", residual=False, _activations=("relu",)):
         super().__init__()
-        if use_ln or residual or activation != "relu":
+        if use_ln or residual or (activation != "relu" and tuple(_activations) == ("relu",)):
             raise ValueError("HIP path: only relu / no LayerNorm / no residual (what every shipped config uses)")
+        if activation not in ("relu", "elu", "tanh"):
+            raise ValueError("Invalid activation")                    # mlp.py:23-30
+        self.activation = activation
         self.lins = nn.ModuleList()
         if use_bn:
             self.bns = nn.ModuleList()
@@ -94,22 +97,28 @@ class _GINConv(nn.Module):
         self.register_buffer("eps", torch.zeros(1))
 
 
+_GNN_ACTIVATIONS = {"relu": "relu", "tanh": "tanh"}        # gnns.py:13: what GCN / GIN look the name up in (anything else: KeyError)
+
+
 class GIN(nn.Module):
-    def __init__(self, in_channels, hidden_channels, out_channels, n_layers, use_bn=True, dropout=0.5, activation="relu"):
+    def __init__(self, in_channels, hidden_channels, out_channels, n_layers, use_bn=True, dropout=0.5, activation="relu",
+                 _activations=("relu",)):
         super().__init__()
+        if tuple(_activations) != ("relu",):
+            _GNN_ACTIVATIONS[activation]                               # gnns.py:87, in front of the first MLP
         self.layers = nn.ModuleList()
         if use_bn:
             self.bns = nn.ModuleList()
         self.use_bn = use_bn
         self.layers.append(_GINConv(MLP(in_channels, hidden_channels, hidden_channels, 2, use_bn=use_bn, dropout=dropout,
-                                        activation=activation)))
+                                        activation=activation, _activations=_activations)))
         for _ in range(n_layers - 2):
             self.layers.append(_GINConv(MLP(hidden_channels, hidden_channels, hidden_channels, 2, use_bn=use_bn,
-                                            dropout=dropout, activation=activation)))
+                                            dropout=dropout, activation=activation, _activations=_activations)))
             if use_bn:
                 self.bns.append(nn.BatchNorm1d(hidden_channels))
         self.layers.append(_GINConv(MLP(hidden_channels, hidden_channels, out_channels, 2, use_bn=use_bn, dropout=dropout,
-                                        activation=activation)))
+                                        activation=activation, _activations=_activations)))
         if use_bn:
             self.bns.append(nn.BatchNorm1d(hidden_channels))
 
@@ -148,7 +157,7 @@ def _prep_mlp(mlp: MLP, train=False):
     return out
 
 
-def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None, tail_drop=None, fuse_drop=False):
+def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None, tail_drop=None, fuse_drop=False, act=None):
     """mlp.py:37-56: hidden layers = bias -> relu -> BN [-> dropout]; the final Linear optionally followed by the
     BatchNorm that GIN.forward applies before the NEXT GINConv (gnns.py:105-112; in eval folded into the GEMM epilogue).
     train: BatchNorm over ALL rows of the layer (the reference normalises [N, C, K] tensors, padded slots included).
@@ -156,15 +165,23 @@ def _run_mlp(prep, x, nvalid=None, K=0, tail_bn=None, train=False, drop=None, ta
     rows node * K + slot with the channels contiguous, the reference's row-major [N, k, C], for the sign-invariant encoders.
     fuse_drop (the encoders of dropout_signinv.py): where a BatchNorm precedes the site, its apply pass and the mask are ONE launch
     (ops.affine_dropout) instead of masked_affine + dropout — the same bits.  tail_drop: the site of GIN.forward's inter-layer dropout
-    (gnns.py:105), applied to the final Linear's output in front of `tail_bn`."""
+    (gnns.py:105), applied to the final Linear's output in front of `tail_bn`.
+    act = 'tanh' | 'elu' (activation_signinv.py; None: ReLU, the GEMM's own epilogue): a hidden layer is the Linear with its bias, then
+    ONE ops.act_affine launch — in eval with the folded BatchNorm, in train mode bare, the batch statistics taken on its output."""
     for i, (pl, bn) in enumerate(prep):
         last = i == len(prep) - 1
         site = tail_bn if last else bn
+        relu = not last and act is None
         if not train:
             sc, sh = (None, None) if site is None else (site.scale, site.shift)
-            x = ops.masked_linear(x, pl, nvalid, K, relu_pre=not last, scale=sc, shift=sh)
+            if last or act is None:
+                x = ops.masked_linear(x, pl, nvalid, K, relu_pre=relu, scale=sc, shift=sh)
+            else:
+                x = ops.act_affine(ops.masked_linear(x, pl, nvalid, K), act, nvalid, K, scale=sc, shift=sh)
         else:
-            x = ops.masked_linear(x, pl, nvalid, K, relu=not last)
+            x = ops.masked_linear(x, pl, nvalid, K, relu=relu)
+            if not last and act is not None:
+                x = ops.act_affine(x, act, nvalid, K)
             dropped = drop is not None and not last and drop[0]
             if last and tail_drop is not None and drop is not None and drop[0]:
                 x = ops.dropout(x, drop[0], drop[1], tail_drop)
@@ -195,6 +212,13 @@ class _EncoderDropout(ops.DropoutHolder):
     forward with p > 0 is not sign-invariant, there as here; eval draws nothing and stays invariant bit for bit."""
 
     _signinv_dropout = False
+    _signinv_activations = ("relu",)     # what `activation=` may name; the subclasses of activation_signinv.py widen it (DESIGN.md §4.5k)
+
+    @property
+    def _act(self):
+        """None for ReLU (the epilogue of the layer-path GEMM), else 'tanh' | 'elu': an ops.act_affine launch per activation site."""
+        a = getattr(self.rho, "activation", "relu")
+        return None if a == "relu" else a
 
     def _init_dropout(self, dropout, who):
         if not self._signinv_dropout:
@@ -239,6 +263,8 @@ class _FusedDeepSigns:
         import ctypes as C
         enc, rho, K = mod.enc, mod.rho, mod.k
         self.ok = False
+        if mod._act is not None:          # the stage kernels' arithmetic is ReLU: a tanh / elu encoder runs the layer path
+            return
         L = len(enc.layers)
         mlps = [c.apply_func for c in enc.layers]
         if any(len(m.lins) != 2 for m in mlps) or mlps[0].lins[0].weight.shape[1] != 1:
@@ -442,6 +468,9 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
     @matmul_precision.setter
     def matmul_precision(self, name):
         from . import fused
+        if self._act is not None and name != "highest":
+            raise ValueError(f"{type(self).__name__}: matmul_precision {name!r} is not built for a {self._act} encoder (it runs the "
+                             "layer path, not the stage kernels); only 'highest'")
         hidden = self.enc.layers[0].apply_func.lins[0].weight.shape[0]
         out = self.enc.layers[-1].apply_func.lins[-1].weight.shape[0]
         dp = max(48, 16 * ((max(hidden, out) + 15) // 16))          # the stage kernel's padded width (_FusedDeepSigns)
@@ -503,7 +532,7 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
                 a = ops.gin_aggregate(h.reshape(N, -1), plan, Lp["eps"], negate=(sign == 1 and l == 0))
                 d = None if drop is None else (drop[0], drop[1], s0 + 2 * l)
                 h = _run_mlp(Lp["mlp"], a.view(N * K, -1), tail_bn=Lp["next_bn"], train=train, drop=d,
-                             tail_drop=s0 + 2 * l + 1 if l < L - 1 else None, fuse_drop=True)
+                             tail_drop=s0 + 2 * l + 1 if l < L - 1 else None, fuse_drop=True, act=self._act)
             outs.append(h)
         return outs
 
@@ -529,12 +558,15 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         sv, sk = (None, 0) if pad is None else (pad.node_slots, K)               # the N*K slot rows
         vN, _, _, k1 = _bucket_rows(self)                                        # the N rows of rho
         drop = self._drop_begin(True, x.device)
+        act = self._act
 
         def run_mlp(mlp, h, tail_bn=None, nv=None, kv=0, site0=0, tail_site=None):
             n = len(mlp.lins)
             for i, lin in enumerate(mlp.lins):
                 last = i == n - 1
-                h = AG.linear(h, lin.weight, lin.bias, nv, kv, relu=not last)     # mlp.py:40-46: bias -> relu -> BN
+                h = AG.linear(h, lin.weight, lin.bias, nv, kv, relu=not last and act is None)     # mlp.py:40-46: bias -> act -> BN
+                if not last and act is not None:
+                    h = AG.activation(h, act, nv, kv)
                 bn = tail_bn if last else (mlp.bns[i] if mlp.use_bn else None)
                 if drop is not None and last and tail_site is not None:
                     h = AG.dropout(h, drop[0], drop[1], tail_site)                # gnns.py:105: in front of the next layer's BatchNorm
@@ -575,7 +607,7 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         h = torch.stack([x, xm], dim=1).contiguous()                                                        # [N, 2, K, 1]
         for Lp in P["gin"]:
             a = ops.gin_aggregate(h.reshape(N, -1), plan, Lp["eps"])
-            h = _run_mlp(Lp["mlp"], a.view(N * 2 * K, -1), tail_bn=Lp["next_bn"])
+            h = _run_mlp(Lp["mlp"], a.view(N * 2 * K, -1), tail_bn=Lp["next_bn"], act=self._act)
         return ops.slot_sum(h.view(N * 2, -1), N, 2).view(N * K, -1)                                         # sum over the sign axis
 
     def _forward_side(self, g, xin, N, K):
@@ -640,9 +672,9 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
         if self.masked:
             # sum over K ; rho(c -> hidden -> K)                              (deepsigns.py:81-84)
-            y = _run_mlp(P["rho"], ops.slot_sum(z, N, K), train=train, drop=rd, fuse_drop=True)
+            y = _run_mlp(P["rho"], ops.slot_sum(z, N, K), train=train, drop=rd, fuse_drop=True, act=self._act)
         else:
-            y = _run_mlp(P["rho"], z.view(N, -1), train=train, drop=rd, fuse_drop=True)     # deepsigns.py:47-49
+            y = _run_mlp(P["rho"], z.view(N, -1), train=train, drop=rd, fuse_drop=True, act=self._act)     # deepsigns.py:47-49
         return y.view(N, K, 1)
 
 
@@ -651,8 +683,10 @@ class GINDeepSigns(_DeepSignsBase):
                  activation="relu"):
         super().__init__()
         self._init_dropout(dropout, "GINDeepSigns")
-        self.enc = GIN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
-        self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.enc = GIN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
+        self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
         self.k = k
         self._prep = None
 
@@ -665,8 +699,10 @@ class MaskedGINDeepSigns(_DeepSignsBase):
         super().__init__()
         self._init_dropout(dropout, "MaskedGINDeepSigns")
         self.device = device
-        self.enc = GIN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
-        self.rho = MLP(out_channels, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.enc = GIN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
+        self.rho = MLP(out_channels, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
         self.k = k
         self._prep = None
 
@@ -702,17 +738,22 @@ class _GraphConv(nn.Module):
         self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
         self.bias = nn.Parameter(torch.zeros(out_feats))
         nn.init.xavier_uniform_(self.weight)
-        self.relu = activation is not None
+        self.relu = activation == "relu"
+        self.act = None if activation in (None, "relu") else activation      # 'tanh': an ops.act_affine launch behind the bias
 
 
 class GCN(nn.Module):
     """layers/gnns.py:15-45: GraphConv(in, hidden, act), n_layers - 2 x GraphConv(hidden, hidden, act), GraphConv(hidden, out); before every
     layer i >= 1 the BatchNorm1d bns[i-1] over all N*K rows.  Parameters only: GCNDeepSigns runs it."""
 
-    def __init__(self, in_channels, hidden_channels, out_channels, n_layers, use_bn=True, dropout=0.5, activation="relu"):
+    def __init__(self, in_channels, hidden_channels, out_channels, n_layers, use_bn=True, dropout=0.5, activation="relu",
+                 _activations=("relu",)):
         super().__init__()
-        if activation != "relu":
-            raise ValueError("HIP path: only relu (what every shipped config uses)")
+        if tuple(_activations) == ("relu",):
+            if activation != "relu":
+                raise ValueError("HIP path: only relu (what every shipped config uses)")
+        else:
+            _GNN_ACTIVATIONS[activation]                               # gnns.py:21
         self.layers = nn.ModuleList()
         if use_bn:
             self.bns = nn.ModuleList()
@@ -825,8 +866,11 @@ class _SignInvBase(_EncoderDropout, nn.Module):
         vN, _, _, k1 = _bucket_rows(self)
         mlp, n = self.rho, len(self.rho.lins)
         r0 = self._rho_site0()
+        act = self._act
         for i, lin in enumerate(mlp.lins):
-            z = AG.linear(z, lin.weight, lin.bias, vN, k1, relu=i < n - 1)
+            z = AG.linear(z, lin.weight, lin.bias, vN, k1, relu=i < n - 1 and act is None)
+            if i < n - 1 and act is not None:
+                z = AG.activation(z, act, vN, k1)
             bn = mlp.bns[i] if (mlp.use_bn and i < n - 1) else None
             if drop is not None and i < n - 1:
                 z = AG.bn_drop(z, bn, drop[0], drop[1], r0 + i, vN, k1) if bn is not None else AG.dropout(z, drop[0], drop[1], r0 + i)
@@ -836,7 +880,7 @@ class _SignInvBase(_EncoderDropout, nn.Module):
 
     def _rho_value(self, P, z, train, drop):
         rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
-        return _run_mlp(P["rho"], z, train=train, drop=rd, fuse_drop=True)
+        return _run_mlp(P["rho"], z, train=train, drop=rd, fuse_drop=True, act=self._act)
 
     def forward(self, g, x):
         train = self.training     # train: batch statistics + running-statistics update, dropout where `p_drop` > 0
@@ -872,8 +916,10 @@ class GCNDeepSigns(_SignInvBase):
         self._init_dropout(dropout, "GCNDeepSigns")
         if use_ln:
             raise ValueError("HIP path: only relu / no LayerNorm / no residual (what every shipped config uses)")
-        self.enc = GCN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
-        self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.enc = GCN(in_channels, hidden_channels, out_channels, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
+        self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
         self.k = k
 
     def _enc_sites(self):
@@ -890,7 +936,7 @@ class GCNDeepSigns(_SignInvBase):
             b = conv.bias.detach().contiguous()
             pl = ops.PackedLinear(ops.pack_weight_t(W), d_out, d_in, None if first else b)         # weight [in, out] = Linear weight^T
             nxt = _BNSite(enc.bns[l], train) if (enc.use_bn and l < L - 1) else None               # applied before layer l + 1 (gnns.py:37-43)
-            layers.append(dict(pl=pl, first=first, bias=b, width=d_out, relu=conv.relu, next_bn=nxt))
+            layers.append(dict(pl=pl, first=first, bias=b, width=d_out, relu=conv.relu, act=conv.act, next_bn=nxt))
         return dict(layers=layers, rho=_prep_mlp(self.rho, train))
 
     def _zero_in_degree(self, plan, valid=None):
@@ -917,11 +963,16 @@ class GCNDeepSigns(_SignInvBase):
                 if train:
                     if Lp["relu"]:
                         h = ops.masked_affine(h, relu=True)
+                    elif Lp["act"]:
+                        h = ops.act_affine(h, Lp["act"])
                     if dsite is not None:
                         h = ops.dropout(h, drop[0], drop[1], dsite)
                     if site is not None:
                         sc, sh = site.affine(h, True)
                         h = ops.masked_affine(h, scale=sc, shift=sh)
+                elif Lp["act"]:
+                    sc, sh = (None, None) if site is None else (site.scale, site.shift)
+                    h = ops.act_affine(h, Lp["act"], scale=sc, shift=sh)
                 elif Lp["relu"] or site is not None:
                     sc, sh = (None, None) if site is None else (site.scale, site.shift)
                     h = ops.masked_affine(h, relu_pre=Lp["relu"], scale=sc, shift=sh)
@@ -929,9 +980,14 @@ class GCNDeepSigns(_SignInvBase):
             a = ops.gcn_propagate(h.view(N, -1), plan, rplan).view(N * S, -1)
             if not train:
                 sc, sh = (None, None) if site is None else (site.scale, site.shift)
-                h = ops.masked_linear(a, Lp["pl"], relu_pre=Lp["relu"], scale=sc, shift=sh)
+                if Lp["act"]:
+                    h = ops.act_affine(ops.masked_linear(a, Lp["pl"]), Lp["act"], scale=sc, shift=sh)
+                else:
+                    h = ops.masked_linear(a, Lp["pl"], relu_pre=Lp["relu"], scale=sc, shift=sh)
             else:
                 h = ops.masked_linear(a, Lp["pl"], relu=Lp["relu"])
+                if Lp["act"]:
+                    h = ops.act_affine(h, Lp["act"])
                 if dsite is not None:
                     h = ops.dropout(h, drop[0], drop[1], dsite)
                 if site is not None:
@@ -985,9 +1041,13 @@ class GCNDeepSigns(_SignInvBase):
                     h = AG.gcn_propagate(z.view(N, -1), plan, rplan, conv.bias, d_out).view(N * K, -1)
                     if conv.relu:
                         h = AG.act_residual(h, act="relu")
+                    elif conv.act:
+                        h = AG.activation(h, conv.act, sv, sk)
                 else:
                     a = AG.gcn_propagate(h.view(N, -1), plan, rplan).view(N * K, -1)
                     h = AG.linear(a, Wt, conv.bias, sv, sk, relu=conv.relu)
+                    if conv.act:
+                        h = AG.activation(h, conv.act, sv, sk)
                 if drop is not None and l < L - 1:
                     h = AG.dropout(h, drop[0], drop[1], s0 + l)                    # gnns.py:36, in front of the BatchNorm
                 if bn is not None:
@@ -1017,7 +1077,8 @@ class TransformerDeepSigns(_SignInvBase):
             raise ValueError(f"TransformerDeepSigns: head width {d_head} outside 1..{ops.GRAPH_ATTENTION_MAX_HEAD} (sn_graph_attention_f32)")
         self.enc = SetTransformerEncoder(d_model=hidden_channels, n_heads=heads, d_head=d_head, d_ff=heads * d_head, n_layers=num_layers)
         self.embed = nn.Linear(1, hidden_channels)
-        self.rho = MLP(hidden_channels * k, hidden_channels, k, 4, use_bn=use_bn, dropout=dropout, activation=activation)
+        self.rho = MLP(hidden_channels * k, hidden_channels, k, 4, use_bn=use_bn, dropout=dropout, activation=activation,
+                       _activations=self._signinv_activations)
         self.k = k
 
     def _enc_sites(self):

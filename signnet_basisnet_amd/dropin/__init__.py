@@ -110,8 +110,22 @@ MAX_READOUT_OVERRIDES = {
 }
 
 
-def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False) -> dict:
-    """What `baselines` (False, True or "all"), `gnn_types`, `feature_dropout`, `sign_inv_dropout` and `max_readout` add to ALIASES[tree]."""
+# Opt-in with `sign_inv_activation=True` (the runner's `--sign-inv-activation`; implies max_readout), on top of the flags above: the five
+# base nets, `nets.ZINC_graph_regression.sign_inv_net` and `layers.deepsigns` from activation_signinv.py, whose sign-invariant encoders
+# take `--sign_inv_activation tanh` (and `elu` where the reference's own classes do).  Without the flag every name resolves exactly as
+# before and anything but `relu` is refused as before.
+SIGN_INV_ACTIVATION_OVERRIDES = {
+    "graphprediction": {**{"nets.ZINC_graph_regression." + m: _PKG + ".signinv_activation_nets"
+                           for m in ("gin_net", "gatedgcn_net", "pna_net", "transformer_net", "gat_net", "sign_inv_net")},
+                        "layers.deepsigns": _PKG + ".signinv_activation_layers"},
+}
+
+
+def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False,
+                    sign_inv_activation=False) -> dict:
+    """What `baselines` (False, True or "all"), `gnn_types`, `feature_dropout`, `sign_inv_dropout`, `max_readout` and
+    `sign_inv_activation` add to ALIASES[tree]."""
+    max_readout = max_readout or sign_inv_activation
     if baselines not in (False, True, "all"):
         raise ValueError(f"baselines must be False, True or 'all', got {baselines!r}")
     table = {}
@@ -128,6 +142,8 @@ def _baseline_table(tree: str, baselines, gnn_types=False, feature_dropout=False
         table.update(SIGN_INV_DROPOUT_OVERRIDES.get(tree, {}))
     if max_readout:
         table.update(MAX_READOUT_OVERRIDES.get(tree, {}))
+    if sign_inv_activation:
+        table.update(SIGN_INV_ACTIVATION_OVERRIDES.get(tree, {}))
     return table
 
 
@@ -166,10 +182,11 @@ class _AliasLoader(importlib.abc.Loader):
 class AliasFinder(importlib.abc.MetaPathFinder):
     """Answers the names of `ALIASES[tree]` and nothing else; every other import goes on to the normal finders."""
 
-    def __init__(self, tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False):
+    def __init__(self, tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False,
+                 sign_inv_activation=False):
         self.tree = tree
         self.table = dict(ALIASES[tree])
-        self.table.update(_baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout))
+        self.table.update(_baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout, sign_inv_activation))
 
     def find_spec(self, fullname, path=None, target=None):
         impl = self.table.get(fullname)
@@ -178,7 +195,8 @@ class AliasFinder(importlib.abc.MetaPathFinder):
         return importlib.machinery.ModuleSpec(fullname, _AliasLoader(impl), origin=impl)
 
 
-def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False) -> AliasFinder:
+def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, sign_inv_dropout=False, max_readout=False,
+            sign_inv_activation=False) -> AliasFinder:
     """Route the reference's module names of `tree` to the HIP modules.  Idempotent per tree.  baselines=True also routes the names of
     `BASELINE_ALIASES[tree]` (NetGINE / the plain GINE GNN) and rebinds those of `BASELINE_OVERRIDES[tree]` (LearningFilters' `models`, with
     the four polynomial-filter baselines); baselines="all" rebinds those of `ALL_BASELINE_OVERRIDES[tree]` on top (LearningFilters'
@@ -186,10 +204,11 @@ def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, 
     the plain GNN for every model.gnn_type); feature_dropout=True rebinds those of `FEATURE_DROPOUT_OVERRIDES[tree]` (the models that take
     train-mode dropout); sign_inv_dropout=True implies feature_dropout and rebinds those of `SIGN_INV_DROPOUT_OVERRIDES[tree]` on top
     (GraphPrediction's base nets and `sign_inv_net` with dropout in the sign-invariant encoder too); max_readout=True implies
-    sign_inv_dropout and rebinds those of `MAX_READOUT_OVERRIDES[tree]` on top (GraphPrediction's base nets with `--readout max`); a finder
-    installed with less is extended in place."""
+    sign_inv_dropout and rebinds those of `MAX_READOUT_OVERRIDES[tree]` on top (GraphPrediction's base nets with `--readout max`);
+    sign_inv_activation=True implies max_readout and rebinds those of `SIGN_INV_ACTIVATION_OVERRIDES[tree]` on top (GraphPrediction's base
+    nets, `sign_inv_net` and `layers.deepsigns` with `--sign_inv_activation tanh | elu`); a finder installed with less is extended in place."""
     shim_dir(tree)
-    extra = _baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout)
+    extra = _baseline_table(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout, sign_inv_activation)
     for f in sys.meta_path:
         if isinstance(f, AliasFinder) and f.tree == tree:
             for name, impl in extra.items():
@@ -202,17 +221,21 @@ def install(tree: str, baselines=False, gnn_types=False, feature_dropout=False, 
                 bound_for_dropout = FEATURE_DROPOUT_OVERRIDES.get(tree, {}).get(name)
                 bound_for_signinv = SIGN_INV_DROPOUT_OVERRIDES.get(tree, {}).get(name)
                 bound_for_max = MAX_READOUT_OVERRIDES.get(tree, {}).get(name)
-                if bound_for_max is not None and f.table.get(name) == bound_for_max:
-                    continue                    # already bound for max_readout: a later call with less takes nothing away
-                if bound_for_signinv is not None and f.table.get(name) == bound_for_signinv and impl != bound_for_max:
+                bound_for_act = SIGN_INV_ACTIVATION_OVERRIDES.get(tree, {}).get(name)
+                if bound_for_act is not None and f.table.get(name) == bound_for_act:
+                    continue                    # already bound for sign_inv_activation: a later call with less takes nothing away
+                if bound_for_max is not None and f.table.get(name) == bound_for_max and impl != bound_for_act:
+                    continue                    # likewise for max_readout
+                if bound_for_signinv is not None and f.table.get(name) == bound_for_signinv and impl not in (bound_for_max, bound_for_act):
                     continue                    # likewise for sign_inv_dropout
-                if bound_for_dropout is not None and f.table.get(name) == bound_for_dropout and impl not in (bound_for_signinv, bound_for_max):
+                if bound_for_dropout is not None and f.table.get(name) == bound_for_dropout and \
+                        impl not in (bound_for_signinv, bound_for_max, bound_for_act):
                     continue                    # likewise for feature_dropout
                 if f.table.get(name) != impl:
                     f.table[name] = impl
                     sys.modules.pop(name, None)
             return f
-    finder = AliasFinder(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout)
+    finder = AliasFinder(tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout, sign_inv_activation)
     sys.meta_path.insert(0, finder)
     for name in finder.table:           # a module imported before install() would otherwise stay bound to the tree's file
         sys.modules.pop(name, None)

@@ -39,6 +39,13 @@ from `readout_models.py`, which take `--readout max` (dgl.max_nodes) next to `su
 
     cd <reference>/GraphPrediction  && python -m signnet_basisnet_amd.dropin.run --max-readout main_ZINC_graph_regression.py --config configs/gatedgcn/GatedGCN_ZINC_NoPE.json --readout max
 
+`--sign-inv-activation` (implies `--max-readout`) rebinds the names of `dropin.SIGN_INV_ACTIVATION_OVERRIDES` on top: GraphPrediction's five
+base nets, `nets.ZINC_graph_regression.sign_inv_net` and `layers.deepsigns` from `activation_signinv.py`, whose sign-invariant encoders take
+`--sign_inv_activation tanh` (and `elu` where the reference's own classes take it: the Transformer encoder); without it anything but `relu`
+is refused as before:
+
+    cd <reference>/GraphPrediction  && python -m signnet_basisnet_amd.dropin.run --sign-inv-activation main_ZINC_graph_regression.py --config configs/gatedgcn/GatedGCN_ZINC_LapPE_signinv_GIN.json --sign_inv_activation tanh
+
 `--attn-dropout=counter` makes "counter" the `attn_dropout_source` of every `pyg.SignNetGNN` the run constructs (Alchemy, GINESignNetPyG):
 the train-mode attention-dropout masks are evaluated inside the attention kernels from (seed, step) — seed torch.initial_seed() unless
 the script calls `seed_dropout` — instead of drawn with torch's device generator.
@@ -55,6 +62,7 @@ from . import ALIASES, SCRIPTS, install
 def main(argv=None) -> None:
     argv = list(sys.argv[1:] if argv is None else argv)
     tree, baselines, gnn_types, feature_dropout, sign_inv_dropout, max_readout = None, False, False, False, False, False
+    more = {}                                       # keywords of install() that are handed on only when their flag is given
     while argv and argv[0].startswith("--"):        # the runner's own options come before the script
         if argv[0] == "--baselines":
             baselines, argv = True, argv[1:]
@@ -66,6 +74,9 @@ def main(argv=None) -> None:
             feature_dropout, sign_inv_dropout, argv = True, True, argv[1:]
         elif argv[0] == "--max-readout":
             feature_dropout, sign_inv_dropout, max_readout, argv = True, True, True, argv[1:]
+        elif argv[0] == "--sign-inv-activation":
+            feature_dropout, sign_inv_dropout, max_readout, argv = True, True, True, argv[1:]
+            more["sign_inv_activation"] = True
         elif argv[0].startswith("--attn-dropout="):
             from ..pyg import SignNetGNN
             try:
@@ -87,7 +98,7 @@ def main(argv=None) -> None:
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] [--sign-inv-dropout] [--max-readout] [--attn-dropout=counter] <entry script> "
+        raise SystemExit("usage: python -m signnet_basisnet_amd.dropin.run [--tree T] [--baselines[=all]] [--gnn-types] [--feature-dropout] [--sign-inv-dropout] [--max-readout] [--sign-inv-activation] [--attn-dropout=counter] <entry script> "
                          "[script arguments ...]\n"
                          "trees: " + ", ".join(f"{t} ({s})" for s, t in SCRIPTS.items()))
     if argv[0] == "-m":
@@ -101,7 +112,7 @@ def main(argv=None) -> None:
             if tree is None:
                 raise SystemExit(f"cannot tell the reference tree from the module {module!r}; pass --tree " + "|".join(sorted(ALIASES)))
         install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout, sign_inv_dropout=sign_inv_dropout,
-                max_readout=max_readout)
+                max_readout=max_readout, **more)
         if os.getcwd() in sys.path:
             sys.path.remove(os.getcwd())
         sys.path.insert(0, os.getcwd())
@@ -116,7 +127,7 @@ def main(argv=None) -> None:
         if tree is None:
             raise SystemExit(f"cannot tell the reference tree from {os.path.basename(script)!r}; pass --tree " + "|".join(sorted(ALIASES)))
     install(tree, baselines=baselines, gnn_types=gnn_types, feature_dropout=feature_dropout, sign_inv_dropout=sign_inv_dropout,
-                max_readout=max_readout)
+                max_readout=max_readout, **more)
     script_dir = os.path.dirname(os.path.abspath(script))
     for p in (os.getcwd(), script_dir):          # script_dir ends up first, as under `python script.py`
         if p in sys.path:

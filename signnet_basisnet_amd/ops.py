@@ -2353,3 +2353,52 @@ def check_dropout_p(p, who):
     if p < 0.0 or p > 1.0:
         raise ValueError(f"{who}: dropout probability has to be between 0 and 1, but got {p}")
     return p
+
+
+# ----------------------------------------------------------------------------- tanh / ELU of the sign-invariant encoders (csrc/activation.hip)
+ACT_TANH, ACT_ELU = 1, 2                       # SN_ACT_* of signnet_hip.h
+ACTIVATIONS = {"tanh": ACT_TANH, "elu": ACT_ELU}
+
+
+def _act_code(act, who):
+    if act not in ACTIVATIONS:
+        raise ValueError(f"{who}: activation must be one of {sorted(ACTIVATIONS)}, got {act!r} (relu is the epilogue of masked_linear)")
+    return ACTIVATIONS[act]
+
+
+def act_affine(x, act, nvalid=None, K=0, scale=None, shift=None):
+    """y = rowvalid ? fma(act(x), scale, shift) : 0 on the row matrix x [..., C] in ONE launch (sn_act_affine_f32): act 'tanh' | 'elu'
+    (alpha 1), then the folded BatchNorm that follows the activation in the reference's MLP (mlp.py:40-51).  scale = shift = None:
+    y = act(x) on valid rows."""
+    code = _act_code(act, "act_affine")
+    if (scale is None) != (shift is None):
+        raise ValueError("act_affine: scale and shift go together")
+    require_cuda(x)
+    x = _f32c(x, "x")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    Cc = x.shape[-1]
+    if scale is not None and (scale.numel() != Cc or shift.numel() != Cc):
+        raise ValueError(f"act_affine: scale / shift must have {Cc} elements")
+    with _span("sn_act_affine_f32"):
+        check(lib().sn_act_affine_f32(ptr(x), Cc, x.numel() // Cc, Cc, ptr(nvalid), int(K), code, ptr(scale), ptr(shift), ptr(out), Cc,
+                                      stream()), "sn_act_affine_f32")
+    return out
+
+
+def act_bwd(dy, a, act, nvalid=None, K=0):
+    """dx = rowvalid ? dy * act'(a) : 0 with a = act(x), the saved output of act_affine WITHOUT an affine (sn_act_affine_bwd_f32)."""
+    code = _act_code(act, "act_bwd")
+    require_cuda(dy, a)
+    dy, a = _f32c(dy, "dy"), _f32c(a, "a")
+    if dy.shape != a.shape:
+        raise ValueError("act_bwd: dy and a must have the same shape")
+    dx = torch.empty_like(a)
+    if a.numel() == 0:
+        return dx
+    Cc = a.shape[-1]
+    with _span("sn_act_affine_bwd_f32"):
+        check(lib().sn_act_affine_bwd_f32(ptr(dy), Cc, ptr(a), Cc, a.numel() // Cc, Cc, ptr(nvalid), int(K), code, ptr(dx), Cc, stream()),
+              "sn_act_affine_bwd_f32")
+    return dx
