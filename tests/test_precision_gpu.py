@@ -18,7 +18,7 @@ REDUCED = ("high", "medium")
 
 
 # ------------------------------------------------------------------------------------------------ 1. GEMM level
-@pytest.mark.parametrize("K", [64, 112, 128])
+@pytest.mark.parametrize("K", [48, 64, 80, 96, 112, 128])          # every dispatch_mlp<PREC> tile count: 3 .. 8
 def test_a_mode_computes_exactly_its_product_set(K):
     """One Linear + bias, [4096, K] x [K, K], through ops.mlp_chain (sn_mlp_chain_prec_f32, one layer).  With
     d = ((y_gpu - b) - emu_mm(mode)) / mag elementwise:  (i) |d| <= K * 2^-23 — twice the worst case of a round-to-nearest fp32
