@@ -19,7 +19,7 @@ batch statistics are taken on the activated tensor) — one launch more than ReL
 autograd.activation, whose adjoint reads only the saved output.  Such an encoder has no stage kernels: the GIN encoders take the layer
 path (`fused_stages` has no effect) and `matmul_precision` accepts "highest" only.
 """
-from . import dropout_signinv, readout_models
+from . import dgl_deepsigns, dropout_signinv, readout_models
 
 
 class GINDeepSigns(dropout_signinv.GINDeepSigns):
@@ -44,15 +44,7 @@ ENCODERS = {"gcn": GCNDeepSigns, "gin": GINDeepSigns, "masked_gin": MaskedGINDee
 def get_sign_inv_net(net_params):
     """dropout_signinv.get_sign_inv_net with the classes of this module: `net_params['sign_inv_activation']` reaches the encoder, as in
     nets/ZINC_graph_regression/sign_inv_net.py:7-13."""
-    assert net_params["sign_inv_net"] is not None, "did not specify sign inv net"
-    kind = net_params["sign_inv_net"]
-    if kind not in ENCODERS:
-        raise ValueError("Invalid sign inv net")
-    args = (1, net_params["hidden_dim"], net_params["phi_out_dim"], net_params["sign_inv_layers"], net_params["pos_enc_dim"])
-    kw = dict(use_bn=True, dropout=net_params["dropout"], activation=net_params["sign_inv_activation"])
-    if kind == "masked_gin":
-        return MaskedGINDeepSigns(*args, net_params["device"], **kw)
-    return ENCODERS[kind](*args, **kw)
+    return dgl_deepsigns.sign_inv_net_from(net_params, ENCODERS)
 
 
 class _ActivationEncoder:

@@ -14,9 +14,16 @@ entirely in the HIP kernels of libsignnet_hip.so; there is no CPU path.  Train m
 batch-statistic BatchNorm (and updates the running statistics); under autograd `_forward_grad` records the same launches as
 torch.autograd.Function nodes whose backward are the hand-written adjoints.
 
-The GIN encoders have one-launch stage kernels (`fused_stages`, `matmul_precision`, `overlap`); the GCN and Transformer encoders run
-layer by layer — one sn_gcn_propagate_f32 / sn_graph_attention_f32 launch per layer for both signs and every slot, everything else
-on the layer-path ops — and offer neither switch (`matmul_precision` accepts "highest" only).
+All four encoders derive from `_SignInvEncoder`, which holds what does not look into `enc`: the one `forward` (contract checks, the
+dispatch to `_forward_grad`, the cache of prepared parameters and its invalidation, the dropout snapshot, the hook `_forward_stages`,
+then `_forward_value`), rho on the value path and under autograd (`_mlp_grad`, the one MLP runner of the autograd paths), the -x
+constants and the per-call plans of the autograd paths.  Every plan is built from `_plan_inputs` (graph object -> batch vector,
+edge index, graph count, with the node-total check) and, for the flipped graph, `_flipped`: `cached_plan` / `_cached_rplan` keep
+theirs on the graph object, `_grad_plans` builds per call.  `sign_inv_net_from` is the factory body over a table of the four classes.
+
+The GIN encoders (`_DeepSignsBase`) have one-launch stage kernels (`fused_stages`, `matmul_precision`, `overlap`), tried through the
+hook; the GCN and Transformer encoders run layer by layer — one sn_gcn_propagate_f32 / sn_graph_attention_f32 launch per layer for both
+signs and every slot, everything else on the layer-path ops — and offer neither switch (`matmul_precision` accepts "highest" only).
 """
 from __future__ import annotations
 
@@ -323,32 +330,18 @@ class _FusedDeepSigns:
         import ctypes as C
         from ._lib import check, lib, ptr, stream
         K, out = self.K, self.out
+        # the reduced modes are entry points of their own, with the mode in front of the stream (both record under the default's name)
+        phi, chain, tail = ("sn_deepsigns_phi_prec_f32", "sn_mlp_chain_prec_f32", (int(precision), stream())) if precision else \
+                           ("sn_deepsigns_phi_f32", "sn_mlp_chain_f32", (stream(),))
         z = torch.empty(N * K, out, dtype=torch.float32, device=x.device)
-        if precision:
-            with ops._span("sn_deepsigns_phi_f32"):
-                check(lib().sn_deepsigns_phi_prec_f32(C.byref(self.phi), ptr(x), K, ptr(plan.graph_ptr), ptr(plan.rowptr), ptr(plan.col),
-                                                      C.byref(plan.bins.cstruct), K, ptr(z), int(precision), stream()),
-                      "sn_deepsigns_phi_prec_f32")
-            y = torch.empty(N, K, dtype=torch.float32, device=x.device)
-            with ops._span("sn_mlp_chain_f32"):
-                if self.masked:
-                    check(lib().sn_mlp_chain_prec_f32(ptr(z), out, N, out, ptr(plan.nvalid), K, self.rho_w, self.n_rho, self.rp, ptr(y), K, K,
-                                                      int(precision), stream()), "sn_mlp_chain_prec_f32")
-                else:
-                    check(lib().sn_mlp_chain_prec_f32(ptr(z), K * out, N, K * out, None, 0, self.rho_w, self.n_rho, self.rp, ptr(y), K, K,
-                                                      int(precision), stream()), "sn_mlp_chain_prec_f32")
-            return y, z
         with ops._span("sn_deepsigns_phi_f32"):
-            check(lib().sn_deepsigns_phi_f32(C.byref(self.phi), ptr(x), K, ptr(plan.graph_ptr), ptr(plan.rowptr), ptr(plan.col),
-                                             C.byref(plan.bins.cstruct), K, ptr(z), stream()), "sn_deepsigns_phi_f32")
+            check(getattr(lib(), phi)(C.byref(self.phi), ptr(x), K, ptr(plan.graph_ptr), ptr(plan.rowptr), ptr(plan.col),
+                                      C.byref(plan.bins.cstruct), K, ptr(z), *tail), phi)
         y = torch.empty(N, K, dtype=torch.float32, device=x.device)
+        # masked: the slot sum over the valid slots in front of rho [N, out]; else rho reads the K * out columns of a node as they lie
+        width, nvalid, kv = (out, ptr(plan.nvalid), K) if self.masked else (K * out, None, 0)
         with ops._span("sn_mlp_chain_f32"):
-            if self.masked:
-                check(lib().sn_mlp_chain_f32(ptr(z), out, N, out, ptr(plan.nvalid), K, self.rho_w, self.n_rho, self.rp, ptr(y), K, K,
-                                             stream()), "sn_mlp_chain_f32")
-            else:
-                check(lib().sn_mlp_chain_f32(ptr(z), K * out, N, K * out, None, 0, self.rho_w, self.n_rho, self.rp, ptr(y), K, K,
-                                             stream()), "sn_mlp_chain_f32")
+            check(getattr(lib(), chain)(ptr(z), width, N, width, nvalid, kv, self.rho_w, self.n_rho, self.rp, ptr(y), K, K, *tail), chain)
         return y, z
 
 
@@ -410,6 +403,30 @@ def _await_side(g, plan=None):
     g._sn_side = None
 
 
+def _plan_inputs(g, N, error=ops.NODE_COUNT_ERROR):
+    """(batch [N], edge index [2, E], B) of a batched graph: what ops.build_plan reads.  Index plumbing only.  The node total comes from
+    the graph object's cached host counts — repeat_interleave without output_size would read the sum back from the device, a host
+    wait per batch and not recordable in a HIP graph — and output_size=N trusts N: a mismatch would be an uninitialised tail or a
+    write past it, so it raises `error` (may name {total} and {N})."""
+    src, dst = g.edges()
+    bnn = g.batch_num_nodes().to(src.device)
+    B = int(bnn.numel())
+    total = _node_counts(g)[1]
+    if total != N:
+        raise ValueError(error.format(total=total, N=N))
+    batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)
+    return batch.long(), torch.stack([src.long(), dst.long()]), B
+
+
+_CACHED_PLAN_ERROR = "batch_num_nodes() sums to {total} but the feature matrix has {N} rows"       # cached_plan's own wording
+
+
+def _flipped(ei):
+    """The edge index of the FLIPPED graph (rows = source nodes: the out-degrees of GraphConv's norm, the CSR of an aggregation's
+    adjoint); its batch vector and graph count are the graph's own."""
+    return ei.flip(0).contiguous()
+
+
 def cached_plan(g, N, k=None):
     """The CSR / graph_ptr plan of a batched graph (sn_batch_plan), built once per graph OBJECT and kept on it — as DGL keeps a
     graph's sparse formats on the graph.  k: also lay out the stage kernels' work bins over all k eigenvector slots (kmax = -k);
@@ -427,33 +444,149 @@ def cached_plan(g, N, k=None):
         plan = cache[key] if key in cache else next(iter(cache.values()))
         _await_side(g, plan)
         return plan
-    src, dst = g.edges()
-    bnn = g.batch_num_nodes().to(src.device)
-    B = int(bnn.numel())
-    total = _node_counts(g)[1]
-    if total != N:            # repeat_interleave(output_size=N) trusts N: a mismatch would be an uninitialised tail or a write past it
-        raise ValueError(f"batch_num_nodes() sums to {total} but the feature matrix has {N} rows")
-    batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)
-    ei = torch.stack([src.long(), dst.long()])
-    plan = ops.build_plan(batch.long(), ei, B, -int(k), bins=True) if k else ops.build_plan(batch.long(), ei, B, 0)
+    batch, ei, B = _plan_inputs(g, N, _CACHED_PLAN_ERROR)
+    plan = ops.build_plan(batch, ei, B, -int(k), bins=True) if k else ops.build_plan(batch, ei, B, 0)
     cache[key] = plan
     return plan
 
 
-class _DeepSignsBase(_EncoderDropout, nn.Module):
+def _cached_rplan(g, N):
+    """The plan of the FLIPPED edge list, kept on the graph object next to its plans and dropped with them (serving.GraphedDGLForward
+    resets `_sn_plans` inside the recorded step: the flipped plan is then rebuilt there too).  Call after cached_plan(g, N)."""
+    cache = getattr(g, "_sn_plans", None)
+    held = getattr(g, "_sn_rplan", None)
+    if held is not None and held[0] is cache:
+        return held[1]
+    batch, ei, B = _plan_inputs(g, N, _CACHED_PLAN_ERROR)
+    rplan = ops.build_plan(batch, _flipped(ei), B, 0)
+    try:
+        g._sn_rplan = (cache, rplan)
+    except Exception:
+        pass
+    return rplan
+
+
+def _mlp_grad(mlp, h, act, drop, nv=None, kv=0, site0=0, tail_bn=None, tail_site=None):
+    """An MLP under autograd (mlp.py:37-56: bias -> act -> BN [-> dropout] per hidden layer): rows outside (nv, kv) — the padding of a
+    bucketed batch — enter no statistic and no gradient, the statistics run over ALL other rows, as in the reference.  drop = (p, snap):
+    hidden layer i is followed by site `site0 + i`, one launch with the BatchNorm apply where there is one.  tail_bn / tail_site: the
+    BatchNorm GIN.forward applies in front of the NEXT GINConv and the dropout site in front of it (gnns.py:105-110)."""
+    from . import autograd as AG
+    n = len(mlp.lins)
+    for i, lin in enumerate(mlp.lins):
+        last = i == n - 1
+        h = AG.linear(h, lin.weight, lin.bias, nv, kv, relu=not last and act is None)
+        if not last and act is not None:
+            h = AG.activation(h, act, nv, kv)
+        bn = tail_bn if last else (mlp.bns[i] if mlp.use_bn else None)
+        if drop is not None and last and tail_site is not None:
+            h = AG.dropout(h, drop[0], drop[1], tail_site)
+        if drop is not None and not last:
+            h = AG.bn_drop(h, bn, drop[0], drop[1], site0 + i, nv, kv) if bn is not None else AG.dropout(h, drop[0], drop[1], site0 + i)
+        elif bn is not None:
+            h = AG.bn_act(h, bn, nv, kv, relu=False)
+    return h
+
+
+class _SignInvEncoder(_EncoderDropout, nn.Module):
+    """What the four sign-invariant nets share (nothing here looks into `enc`): the forward contract and its dispatch to the three
+    forward paths — eval and the train-mode value (`_forward_value`), train under autograd (`_forward_grad`) — the cache of prepared
+    parameters and its invalidation, rho on either path, and the per-call plans of the autograd path.  A subclass provides
+    `_prepare(train) -> P` (with P["rho"]), `_enc_sites()`, `_forward_value(P, g, x, train, drop)` and `_forward_grad(g, x, drop)`."""
     masked = False
+
+    def __init__(self):
+        super().__init__()
+        # fires also when a PARENT module's load_state_dict recurses into this one (its own override below does not)
+        self.register_load_state_dict_post_hook(lambda m, keys=None: m._invalidate())
+        self._prep = None
+
+    @property
+    def matmul_precision(self):
+        """"highest" only: an encoder without stage kernels runs every Linear as the fp32 layer-path GEMM.  Assigning "high" or "medium"
+        raises ValueError — a mode is never replaced by another."""
+        return "highest"
+
+    @matmul_precision.setter
+    def matmul_precision(self, name):
+        if name != "highest":
+            raise ValueError(f"{type(self).__name__}: matmul_precision {name!r} is not built for this encoder (it has no stage kernels); "
+                             "only 'highest'")
+
+    def _invalidate(self):
+        self._prep = None
+
+    def train(self, mode=True):
+        self._invalidate()
+        return super().train(mode)
+
+    def _apply(self, fn, *a, **k):
+        self._invalidate()
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self._invalidate()
+        return super().load_state_dict(*a, **k)
+
+    def _neg(self, x2):
+        """-x of a row matrix (one launch; the constants are kept with the prepared parameters' device)."""
+        c = getattr(self, "_neg1", None)
+        if c is None or c[0].device != x2.device:
+            c = self._neg1 = (torch.full((1,), -1.0, device=x2.device), torch.zeros(1, device=x2.device))
+        return ops.masked_affine(x2, scale=c[0], shift=c[1])
+
+    def _grad_plans(self, g, N, kmax=0, counts=None):
+        """(plan, plan of the flipped edge list), built per call: under train_graph.DGLBucketedStep the graph object is a static buffer
+        whose contents change between replays, so nothing is cached on it.  counts: the device count block of such a padded batch —
+        its padding graphs get no slot."""
+        batch, ei, B = _plan_inputs(g, N)
+        return ops.build_plan(batch, ei, B, kmax, counts=counts), ops.build_plan(batch, _flipped(ei), B, kmax)
+
+    def _rho_grad(self, z, drop=None):
+        """rho under autograd: padded rows of a bucketed batch enter no statistic and no gradient; its sites start at `_rho_site0()`."""
+        vN, _, _, k1 = _bucket_rows(self)
+        return _mlp_grad(self.rho, z, self._act, drop, vN, k1, self._rho_site0())
+
+    def _rho_value(self, P, z, train, drop):
+        rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
+        return _run_mlp(P["rho"], z, train=train, drop=rd, fuse_drop=True, act=self._act)
+
+    def _forward_stages(self, g, x, copied):
+        """Hook of an encoder with stage kernels: the eval output where they serve this call, else None (the layer path follows).
+        copied: x is a converted copy (dtype / layout) queued on the caller's stream a moment ago."""
+        return None
+
+    def forward(self, g, x):
+        train = self.training     # train: batch statistics + running-statistics update, dropout where `p_drop` > 0
+        ops.require_cuda(x)
+        if x.dim() != 3 or x.shape[1] != self.k or x.shape[2] != 1:
+            raise ValueError(f"expected x of shape [N, {self.k}, 1]")
+        xin = x.contiguous().float()
+        drop = self._drop_begin(train, x.device)      # the dropout step advances here: once per train-mode forward, never in eval
+        if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._forward_grad(g, xin, drop)
+        if train:
+            P = self._prepare(True)          # parameters may change between training-mode calls: nothing is cached
+        else:
+            if self._prep is None:
+                self._prep = self._prepare(False)
+            P = self._prep
+            y = self._forward_stages(g, xin, xin.data_ptr() != x.data_ptr())
+            if y is not None:
+                return y
+        return self._forward_value(P, g, xin, train, drop)
+
+
+class _DeepSignsBase(_SignInvEncoder):
+    """The GIN pair: the layer path of the base class and, in eval, the two stage kernels in front of it."""
 
     def _enc_sites(self):
         """Dropout sites of ONE enc call: a hidden site per GIN MLP (mlp.py:51) and one in front of every layer but the first
         (gnns.py:105), in the order m0, d1, m1, d2, m2, ..."""
         return 2 * len(self.enc.layers) - 1
 
-    def __init__(self):
-        super().__init__()
-        # fires also when a PARENT module's load_state_dict recurses into this one (its own override below does not)
-        self.register_load_state_dict_post_hook(lambda m, keys=None: m._invalidate())
-
     fused_stages = True      # eval: the two stage kernels (3 launches); False forces the layer-at-a-time path
+    _fused = None            # _FusedDeepSigns of the current parameters, packed by the first eval forward that may use it
 
     @property
     def matmul_precision(self):
@@ -483,20 +616,8 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         return fused.PRECISIONS[self.matmul_precision]
 
     def _invalidate(self):
-        self._prep = None
+        super()._invalidate()
         self._fused = None
-
-    def train(self, mode=True):
-        self._invalidate()
-        return super().train(mode)
-
-    def _apply(self, fn, *a, **k):
-        self._invalidate()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._invalidate()
-        return super().load_state_dict(*a, **k)
 
     def _prepare(self, train=False):
         enc = self.enc
@@ -507,19 +628,11 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
             P["gin"].append(dict(eps=conv.eps, mlp=_prep_mlp(conv.apply_func, train), next_bn=nxt))
         return P
 
-    def _plan(self, g, N, fused=False, counts=None):
-        """counts: the device count block of a padded batch (train_graph.DGLBucketedStep): its padding graphs get no slot."""
-        src, dst = g.edges()
-        bnn = g.batch_num_nodes().to(src.device)
-        B = int(bnn.numel())
-        # (the node total comes from the graph object's cached host counts: repeat_interleave without output_size would read the sum
-        #  back from the device — a host wait per batch, and not recordable in a HIP graph)
-        if _node_counts(g)[1] != N:
-            raise ValueError("batch_num_nodes does not sum to the number of feature rows")
-        batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N)      # index plumbing only
-        if fused:     # kmax = -k: work bins over all k slots of every graph (zero-padded columns are evaluated like any other)
-            return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, -self.k, bins=True)
-        return ops.build_plan(batch.long(), torch.stack([src.long(), dst.long()]), B, self.k, counts=counts)
+    def _plan(self, g, N, counts=None):
+        """The k-slot plan of the layer path (kmax = k: `nvalid` is min(n, k) per node).  counts: the device count block of a padded
+        batch (train_graph.DGLBucketedStep): its padding graphs get no slot."""
+        batch, ei, B = _plan_inputs(g, N)
+        return ops.build_plan(batch, ei, B, self.k, counts=counts)
 
     def _phi(self, P, plan, x, N, K, train=False, drop=None):
         """enc(g, x) + enc(g, -x): GIN.forward, gnns.py:102-114, twice.  drop = (p, snap): the sites of _enc_sites per call."""
@@ -536,7 +649,7 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
             outs.append(h)
         return outs
 
-    def _forward_grad(self, g, x):
+    def _forward_grad(self, g, x, drop):
         """Differentiable train-mode forward: the same launches as the value path, recorded as
         torch.autograd.Function nodes whose backward are the hand-written adjoints of csrc/backward.hip, so that the
         gradient a DGL base network sends back into `p = sign_inv_net(g, pos_enc)` (train_ZINC_graph_regression.py:20-25)
@@ -549,68 +662,39 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         from . import autograd as AG
         N, K = x.shape[0], self.k
         pad = getattr(self, "_bucket", None)
-        plan = self._plan(g, N, counts=None if pad is None else pad.counts)
-        src, dst = g.edges()
-        rg = Graph(dst, src, g.batch_num_nodes())
-        rg._sn_node_counts = _node_counts(g)           # (the same batch: its node counts are not read back a second time)
-        rplan = self._plan(rg, N)                                                # out-edge CSR for the aggregation adjoint
+        # (the flipped plan: the out-edge CSR of the aggregation's adjoint)
+        plan, rplan = self._grad_plans(g, N, K, None if pad is None else pad.counts)
         enc = self.enc
         sv, sk = (None, 0) if pad is None else (pad.node_slots, K)               # the N*K slot rows
-        vN, _, _, k1 = _bucket_rows(self)                                        # the N rows of rho
-        drop = self._drop_begin(True, x.device)
         act = self._act
-
-        def run_mlp(mlp, h, tail_bn=None, nv=None, kv=0, site0=0, tail_site=None):
-            n = len(mlp.lins)
-            for i, lin in enumerate(mlp.lins):
-                last = i == n - 1
-                h = AG.linear(h, lin.weight, lin.bias, nv, kv, relu=not last and act is None)     # mlp.py:40-46: bias -> act -> BN
-                if not last and act is not None:
-                    h = AG.activation(h, act, nv, kv)
-                bn = tail_bn if last else (mlp.bns[i] if mlp.use_bn else None)
-                if drop is not None and last and tail_site is not None:
-                    h = AG.dropout(h, drop[0], drop[1], tail_site)                # gnns.py:105: in front of the next layer's BatchNorm
-                if drop is not None and not last:                                 # mlp.py:51
-                    h = AG.bn_drop(h, bn, drop[0], drop[1], site0 + i, nv, kv) if bn is not None else \
-                        AG.dropout(h, drop[0], drop[1], site0 + i)
-                elif bn is not None:
-                    h = AG.bn_act(h, bn, nv, kv, relu=False)                       # statistics over ALL rows, as the reference
-            return h
-
         outs = []
         L = len(enc.layers)
-        x = x.contiguous().float()
         for sign in (0, 1):
             h = x
             s0 = ops.SIGNINV_DROP_SITE + sign * self._enc_sites()
             for l, conv in enumerate(enc.layers):
                 a = AG.gin_aggregate(h.reshape(N, -1), conv.eps, plan, rplan, negate=(sign == 1 and l == 0))
-                h = run_mlp(conv.apply_func, a.view(N * K, -1), enc.bns[l] if (enc.use_bn and l < L - 1) else None, sv, sk,
-                            s0 + 2 * l, s0 + 2 * l + 1 if l < L - 1 else None)
+                h = _mlp_grad(conv.apply_func, a.view(N * K, -1), act, drop, sv, sk, s0 + 2 * l,
+                              enc.bns[l] if (enc.use_bn and l < L - 1) else None, s0 + 2 * l + 1 if l < L - 1 else None)
             outs.append(h)
-        r0 = self._rho_site0()
         if self.masked:
-            z = AG.masked_add(outs[0], outs[1], plan.nvalid, K)
-            y = run_mlp(self.rho, AG.slot_sum(z, N, K, plan.nvalid), nv=vN, kv=k1, site0=r0)
+            z = AG.slot_sum(AG.masked_add(outs[0], outs[1], plan.nvalid, K), N, K, plan.nvalid)
         else:
-            z = AG.masked_add(outs[0], outs[1], sv, sk)
-            y = run_mlp(self.rho, z.view(N, -1), nv=vN, kv=k1, site0=r0)
-        return y.view(N, K, 1)
+            z = AG.masked_add(outs[0], outs[1], sv, sk).view(N, -1)
+        return self._rho_grad(z, drop).view(N, K, 1)
 
     def _phi_eval_merged(self, P, plan, x, N, K):
         """Eval: enc(g, x) and enc(g, -x) in ONE pass — the two signs ride in the feature axis ([N, 2, K, C]), so a layer is one
         aggregation launch and two Linears instead of two and four (folded BatchNorm is row-wise, the signs never mix until the
         final sum).  Returns phi(x) + phi(-x) as [N*K, c]."""
-        if "neg1" not in P:
-            P["neg1"] = (torch.full((1,), -1.0, device=x.device), torch.zeros(1, device=x.device))
-        xm = ops.masked_affine(x.view(N * K, 1), scale=P["neg1"][0], shift=P["neg1"][1]).view(N, K, 1)      # -x
+        xm = self._neg(x.view(N * K, 1)).view(N, K, 1)
         h = torch.stack([x, xm], dim=1).contiguous()                                                        # [N, 2, K, 1]
         for Lp in P["gin"]:
             a = ops.gin_aggregate(h.reshape(N, -1), plan, Lp["eps"])
             h = _run_mlp(Lp["mlp"], a.view(N * 2 * K, -1), tail_bn=Lp["next_bn"], act=self._act)
         return ops.slot_sum(h.view(N * 2, -1), N, 2).view(N * K, -1)                                         # sum over the sign axis
 
-    def _forward_side(self, g, xin, N, K):
+    def _forward_side(self, g, xin, N, K, copied):
         """`overlap = True` (opt-in, eval, stage kernels): the batch plan and the two stage launches are queued on a side stream of this
         module and the result is handed over with an event kept on the graph object; the base network that consumes it (any net of
         dgl_nets: its first `cached_plan(g, ...)` waits for the event on ITS stream) then runs behind it, and the NEXT batch's
@@ -622,7 +706,7 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         if getattr(self, "_side_stream", None) is None:
             self._side_stream = torch.cuda.Stream(device=xin.device)
         side = self._side_stream
-        if getattr(self, "_side_wait", False):
+        if copied:
             # x was converted (dtype / layout) by a kernel queued on the caller's stream a moment ago: the side stream must see it
             side.wait_stream(torch.cuda.current_stream(xin.device))
         with torch.cuda.stream(side), _lib_mod.stream_scope():
@@ -636,46 +720,33 @@ class _DeepSignsBase(_EncoderDropout, nn.Module):
         g._sn_side = (ev, side, (y,))
         return y
 
-    def forward(self, g, x):
-        train = self.training     # train: batch statistics + running-statistics update, dropout where `p_drop` > 0
-        ops.require_cuda(x)
-        if x.dim() != 3 or x.shape[1] != self.k or x.shape[2] != 1:
-            raise ValueError(f"expected x of shape [N, {self.k}, 1]")
-        if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return self._forward_grad(g, x)
-        drop = self._drop_begin(train, x.device)
-        if train:
-            P = self._prepare(True)          # parameters may change between training-mode calls: nothing is cached
-        else:
-            if getattr(self, "_prep", None) is None:
-                self._prep = self._prepare()
-            P = self._prep
+    def _forward_stages(self, g, x, copied):
+        """Eval: sn_batch_plan and the two stage kernels, where the shapes are theirs (the layer path's `_prep` is packed either way)."""
         N, K = x.shape[0], self.k
-        if not train and self.fused_stages:
-            if getattr(self, "_fused", None) is None:
-                self._fused = _FusedDeepSigns(self)
-            if self._fused.ok and N > 0 and _max_nodes(g) <= ops.PHI_BIN_ROWS and int(g.batch_num_nodes().numel()) <= 6144:
-                xin = x.contiguous().float().view(N, K)
-                if getattr(self, "overlap", False):
-                    self._side_wait = xin.data_ptr() != x.data_ptr()     # a copy / cast was queued on the caller's stream
-                    return self._forward_side(g, xin, N, K)
-                y, _ = self._fused.run(cached_plan(g, N, K), xin, N, self._prec)
-                return y.view(N, K, 1)
+        if not self.fused_stages:
+            return None
+        if self._fused is None:
+            self._fused = _FusedDeepSigns(self)
+        if not (self._fused.ok and N > 0 and _max_nodes(g) <= ops.PHI_BIN_ROWS and int(g.batch_num_nodes().numel()) <= 6144):
+            return None
+        if getattr(self, "overlap", False):
+            return self._forward_side(g, x.view(N, K), N, K, copied)
+        y, _ = self._fused.run(cached_plan(g, N, K), x.view(N, K), N, self._prec)
+        return y.view(N, K, 1)
+
+    def _forward_value(self, P, g, x, train, drop=None):
+        N, K = x.shape[0], self.k
         plan = self._plan(g, N)
         if not train:
-            z = self._phi_eval_merged(P, plan, x.contiguous().float(), N, K)
+            z = self._phi_eval_merged(P, plan, x, N, K)
             if self.masked:
                 z = ops.masked_affine(z, plan.nvalid, K)                     # x[~mask] = 0       (deepsigns.py:76-80)
         else:
-            zp, zm = self._phi(P, plan, x.contiguous().float(), N, K, train, drop)
+            zp, zm = self._phi(P, plan, x, N, K, train, drop)
             z = ops.masked_affine(zp, plan.nvalid, K, residual=zm) if self.masked else ops.masked_affine(zp, residual=zm)
-        rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
-        if self.masked:
-            # sum over K ; rho(c -> hidden -> K)                              (deepsigns.py:81-84)
-            y = _run_mlp(P["rho"], ops.slot_sum(z, N, K), train=train, drop=rd, fuse_drop=True, act=self._act)
-        else:
-            y = _run_mlp(P["rho"], z.view(N, -1), train=train, drop=rd, fuse_drop=True, act=self._act)     # deepsigns.py:47-49
-        return y.view(N, K, 1)
+        # masked: sum over K ; rho(c -> hidden -> K) (deepsigns.py:81-84); else rho over the K * c columns of a node (deepsigns.py:47-49)
+        z = ops.slot_sum(z, N, K) if self.masked else z.view(N, -1)
+        return self._rho_value(P, z, train, drop).view(N, K, 1)
 
 
 class GINDeepSigns(_DeepSignsBase):
@@ -688,7 +759,6 @@ class GINDeepSigns(_DeepSignsBase):
         self.rho = MLP(out_channels * k, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
                        _activations=self._signinv_activations)
         self.k = k
-        self._prep = None
 
 
 class MaskedGINDeepSigns(_DeepSignsBase):
@@ -704,29 +774,9 @@ class MaskedGINDeepSigns(_DeepSignsBase):
         self.rho = MLP(out_channels, hidden_channels, k, num_layers, use_bn=use_bn, dropout=dropout, activation=activation,
                        _activations=self._signinv_activations)
         self.k = k
-        self._prep = None
 
 
 # ----------------------------------------------------------------------------- the 'gcn' and 'transformer' encoders
-def _cached_rplan(g, N):
-    """The plan of the FLIPPED edge list (rows = source nodes: the out-degrees of GraphConv's norm, the CSR of the aggregation's adjoint),
-    kept on the graph object next to its plans and dropped with them (serving.GraphedDGLForward resets `_sn_plans` inside the recorded
-    step: the flipped plan is then rebuilt there too).  Call after cached_plan(g, N)."""
-    cache = getattr(g, "_sn_plans", None)
-    held = getattr(g, "_sn_rplan", None)
-    if held is not None and held[0] is cache:
-        return held[1]
-    src, dst = g.edges()
-    rg = Graph(dst, src, g.batch_num_nodes())
-    rg._sn_node_counts = _node_counts(g)           # (the same batch: its node counts are not read back a second time)
-    rplan = cached_plan(rg, N)
-    try:
-        g._sn_rplan = (cache, rplan)
-    except Exception:
-        pass
-    return rplan
-
-
 class _GraphConv(nn.Module):
     """dgl.nn.pytorch.GraphConv(in_feats, out_feats, norm='both', weight=True, bias=True, activation=...), restated from DGL's published
     definition (DGL is not pinned by the reference): parameters `weight` [in, out] (Glorot uniform) and `bias` [out] (zeros);
@@ -804,106 +854,11 @@ class SetTransformerEncoder(nn.Module):
         self.layers = nn.ModuleList([_SetAttentionBlock(d_model, n_heads, d_head, d_ff) for _ in range(n_layers)])
 
 
-class _SignInvBase(_EncoderDropout, nn.Module):
-    """What the sign-invariant nets WITHOUT stage kernels share (nothing here looks into `enc`): the forward contract, the three forward
-    paths (eval / train value / train under autograd), and the cache invalidation of _DeepSignsBase."""
-
-    def __init__(self):
-        super().__init__()
-        self.register_load_state_dict_post_hook(lambda m, keys=None: m._invalidate())
-        self._prep = None
-
-    @property
-    def matmul_precision(self):
-        """"highest" only: these encoders have no stage kernels, every Linear is the fp32 layer-path GEMM.  Assigning "high" or "medium"
-        raises ValueError — a mode is never replaced by another."""
-        return "highest"
-
-    @matmul_precision.setter
-    def matmul_precision(self, name):
-        if name != "highest":
-            raise ValueError(f"{type(self).__name__}: matmul_precision {name!r} is not built for this encoder (it has no stage kernels); "
-                             "only 'highest'")
-
-    def _invalidate(self):
-        self._prep = None
-
-    def train(self, mode=True):
-        self._invalidate()
-        return super().train(mode)
-
-    def _apply(self, fn, *a, **k):
-        self._invalidate()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._invalidate()
-        return super().load_state_dict(*a, **k)
-
-    def _neg(self, x2):
-        """-x of a row matrix (one launch; the constants are kept with the prepared parameters' device)."""
-        c = getattr(self, "_neg1", None)
-        if c is None or c[0].device != x2.device:
-            c = self._neg1 = (torch.full((1,), -1.0, device=x2.device), torch.zeros(1, device=x2.device))
-        return ops.masked_affine(x2, scale=c[0], shift=c[1])
-
-    def _grad_plans(self, g, N):
-        """(plan, plan of the flipped edge list), built per call: under train_graph.DGLBucketedStep the graph object is a static buffer
-        whose contents change between replays, so nothing is cached on it."""
-        src, dst = g.edges()
-        bnn = g.batch_num_nodes().to(src.device)
-        B = int(bnn.numel())
-        if _node_counts(g)[1] != N:
-            raise ValueError(ops.NODE_COUNT_ERROR)
-        batch = torch.repeat_interleave(torch.arange(B, device=src.device), bnn, output_size=N).long()      # index plumbing only
-        ei = torch.stack([src.long(), dst.long()])
-        return ops.build_plan(batch, ei, B, 0), ops.build_plan(batch, ei.flip(0).contiguous(), B, 0)
-
-    def _rho_grad(self, z, drop=None):
-        """rho under autograd (mlp.py:37-56): padded rows of a bucketed batch enter no statistic and no gradient.  drop = (p, snap):
-        hidden layer i is followed by site `_rho_site0() + i` — one launch with the BatchNorm apply where there is one."""
-        from . import autograd as AG
-        vN, _, _, k1 = _bucket_rows(self)
-        mlp, n = self.rho, len(self.rho.lins)
-        r0 = self._rho_site0()
-        act = self._act
-        for i, lin in enumerate(mlp.lins):
-            z = AG.linear(z, lin.weight, lin.bias, vN, k1, relu=i < n - 1 and act is None)
-            if i < n - 1 and act is not None:
-                z = AG.activation(z, act, vN, k1)
-            bn = mlp.bns[i] if (mlp.use_bn and i < n - 1) else None
-            if drop is not None and i < n - 1:
-                z = AG.bn_drop(z, bn, drop[0], drop[1], r0 + i, vN, k1) if bn is not None else AG.dropout(z, drop[0], drop[1], r0 + i)
-            elif bn is not None:
-                z = AG.bn_act(z, bn, vN, k1, relu=False)
-        return z
-
-    def _rho_value(self, P, z, train, drop):
-        rd = None if drop is None else (drop[0], drop[1], self._rho_site0())
-        return _run_mlp(P["rho"], z, train=train, drop=rd, fuse_drop=True, act=self._act)
-
-    def forward(self, g, x):
-        train = self.training     # train: batch statistics + running-statistics update, dropout where `p_drop` > 0
-        ops.require_cuda(x)
-        if x.dim() != 3 or x.shape[1] != self.k or x.shape[2] != 1:
-            raise ValueError(f"expected x of shape [N, {self.k}, 1]")
-        x = x.contiguous().float()
-        if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return self._forward_grad(g, x)
-        if train:
-            P = self._prepare(True)          # parameters may change between training-mode calls: nothing is cached
-        else:
-            if self._prep is None:
-                self._prep = self._prepare(False)
-            P = self._prep
-        return self._forward_value(P, g, x, train, self._drop_begin(train, x.device))
-
-
 _ZERO_IN_DEGREE = ("There are 0-in-degree nodes in the graph: GraphConv's normalised sum is undefined for them (DGL raises DGLError here "
                    "unless allow_zero_in_degree is set, which layers/gnns.py:23-29 leaves at False)")
 
 
-class GCNDeepSigns(_SignInvBase):
+class GCNDeepSigns(_SignInvEncoder):
     """layers/deepsigns.py:13-31: rho(enc(g, x) + enc(g, -x)) with enc = GCN (layers/gnns.py:15-45) over [N, k, c] features and
     rho = MLP(out * k, hidden, k, num_layers).  state_dict keys `enc.layers.{l}.weight` / `.bias`, `enc.bns.{l}.*`, `rho.lins.{i}.*`,
     `rho.bns.{i}.*`.  The propagation D_in^-1/2 A D_out^-1/2 h is ONE launch per layer (sn_gcn_propagate_f32; eval: both signs in the
@@ -957,37 +912,28 @@ class GCNDeepSigns(_SignInvBase):
         for l, Lp in enumerate(P["layers"]):
             site = Lp["next_bn"]
             dsite = drop[2] + l if (drop is not None and l < n_layers - 1) else None
-            if Lp["first"]:
+            relu, act = Lp["relu"], Lp["act"]
+            # eval: the folded BatchNorm rides with the activation; train: its batch statistics are taken behind it (the tail below)
+            sc, sh = (None, None) if (train or site is None) else (site.scale, site.shift)
+            if Lp["first"]:       # the weight in front: nothing follows the propagation but its bias, so the activation is a launch of its own
                 z = ops.masked_linear(h, Lp["pl"])
                 h = ops.gcn_propagate(z.view(N, -1), plan, rplan, Lp["bias"], Lp["width"]).view(N * S, -1)
-                if train:
-                    if Lp["relu"]:
+                if act:
+                    h = ops.act_affine(h, act, scale=sc, shift=sh)
+                elif train:
+                    if relu:
                         h = ops.masked_affine(h, relu=True)
-                    elif Lp["act"]:
-                        h = ops.act_affine(h, Lp["act"])
-                    if dsite is not None:
-                        h = ops.dropout(h, drop[0], drop[1], dsite)
-                    if site is not None:
-                        sc, sh = site.affine(h, True)
-                        h = ops.masked_affine(h, scale=sc, shift=sh)
-                elif Lp["act"]:
-                    sc, sh = (None, None) if site is None else (site.scale, site.shift)
-                    h = ops.act_affine(h, Lp["act"], scale=sc, shift=sh)
-                elif Lp["relu"] or site is not None:
-                    sc, sh = (None, None) if site is None else (site.scale, site.shift)
-                    h = ops.masked_affine(h, relu_pre=Lp["relu"], scale=sc, shift=sh)
-                continue
-            a = ops.gcn_propagate(h.view(N, -1), plan, rplan).view(N * S, -1)
-            if not train:
-                sc, sh = (None, None) if site is None else (site.scale, site.shift)
-                if Lp["act"]:
-                    h = ops.act_affine(ops.masked_linear(a, Lp["pl"]), Lp["act"], scale=sc, shift=sh)
+                elif relu or site is not None:
+                    h = ops.masked_affine(h, relu_pre=relu, scale=sc, shift=sh)
+            else:                 # the weight behind: ReLU (and in eval the folded BatchNorm) in the GEMM's epilogue
+                a = ops.gcn_propagate(h.view(N, -1), plan, rplan).view(N * S, -1)
+                if act:
+                    h = ops.act_affine(ops.masked_linear(a, Lp["pl"]), act, scale=sc, shift=sh)
+                elif train:
+                    h = ops.masked_linear(a, Lp["pl"], relu=relu)
                 else:
-                    h = ops.masked_linear(a, Lp["pl"], relu_pre=Lp["relu"], scale=sc, shift=sh)
-            else:
-                h = ops.masked_linear(a, Lp["pl"], relu=Lp["relu"])
-                if Lp["act"]:
-                    h = ops.act_affine(h, Lp["act"])
+                    h = ops.masked_linear(a, Lp["pl"], relu_pre=relu, scale=sc, shift=sh)
+            if train:
                 if dsite is not None:
                     h = ops.dropout(h, drop[0], drop[1], dsite)
                 if site is not None:
@@ -1014,7 +960,7 @@ class GCNDeepSigns(_SignInvBase):
             z = ops.masked_affine(zp, residual=zm).view(N, -1)
         return self._rho_value(P, z, train, drop).view(N, K, 1)                        # deepsigns.py:27-30
 
-    def _forward_grad(self, g, x):
+    def _forward_grad(self, g, x, drop):
         """Differentiable train-mode forward: the launches of the value path as autograd nodes (the propagation's adjoint is the same
         kernel on the flipped plan).  Under the switch `_bucket` (train_graph.DGLBucketedStep) `g` is a PADDED batch: the ops over the
         N*K slot rows take the node-slot vector, those over the N rows of rho the node validity, as _DeepSignsBase._forward_grad."""
@@ -1026,7 +972,6 @@ class GCNDeepSigns(_SignInvBase):
         enc, L = self.enc, len(self.enc.layers)
         sv, sk = (None, 0) if pad is None else (pad.node_slots, K)
         x2 = x.view(N * K, 1)
-        drop = self._drop_begin(True, x.device)
         outs = []
         for sign in (0, 1):
             h = x2 if sign == 0 else self._neg(x2)
@@ -1057,7 +1002,7 @@ class GCNDeepSigns(_SignInvBase):
         return self._rho_grad(z.view(N, -1), drop).view(N, K, 1)
 
 
-class TransformerDeepSigns(_SignInvBase):
+class TransformerDeepSigns(_SignInvEncoder):
     """layers/deepsigns.py:89-119: embed = Linear(1, hidden); enc = SetTransformerEncoder(hidden, 2 heads of hidden // 2, d_ff =
     2 * (hidden // 2), num_layers blocks); rho = MLP(hidden * k, hidden, k, 4); forward = rho(cat_i [enc(g, embed(x)[:, i]) +
     enc(g, embed(-x)[:, i])]).  `out_channels` is unused, as in the reference.  state_dict keys `embed.*`,
@@ -1114,7 +1059,7 @@ class TransformerDeepSigns(_SignInvBase):
         z = ops.slot_sum(h.view(N * 2, -1), N, 2)                                      # sum over the sign axis -> [N, K * hidden]
         return self._rho_value(P, z, train, drop).view(N, K, 1)                        # deepsigns.py:116-118
 
-    def _forward_grad(self, g, x):
+    def _forward_grad(self, g, x, drop):
         """Differentiable train-mode forward: one attention launch per block forward, one backward.  Under `_bucket` the padding nodes
         form the batch's spare graph: attention never mixes them with valid nodes, and their rows are masked out of every Linear."""
         from . import autograd as AG
@@ -1136,23 +1081,27 @@ class TransformerDeepSigns(_SignInvBase):
             f = AG.linear(AG.linear(h, m.ffn[0].weight, m.ffn[0].bias, sv, sk, relu=True), m.ffn[3].weight, m.ffn[3].bias, sv, sk)
             h = AG.masked_layernorm(f, h, m.norm_inter.weight, m.norm_inter.bias, m.norm_inter.eps, sv, sk)
         z = AG.slot_sum(h.view(N * 2, -1), N, 2)
-        return self._rho_grad(z, self._drop_begin(True, x.device)).view(N, K, 1)
+        return self._rho_grad(z, drop).view(N, K, 1)
 
 
-def get_sign_inv_net(net_params):
-    """nets/ZINC_graph_regression/sign_inv_net.py:3-17: 'gcn', 'gin', 'masked_gin' and 'transformer' with the reference's argument lists
+ENCODERS = {"gcn": GCNDeepSigns, "gin": GINDeepSigns, "masked_gin": MaskedGINDeepSigns, "transformer": TransformerDeepSigns}
+
+
+def sign_inv_net_from(net_params, encoders):
+    """nets/ZINC_graph_regression/sign_inv_net.py:3-17 over a table of the four classes (this module's, or the opt-in subclasses of
+    dropout_signinv.py / activation_signinv.py): 'gcn', 'gin', 'masked_gin' and 'transformer' with the reference's argument lists
     (a shipped config selects 'gin' or 'masked_gin'; the main script's --sign_inv_net takes all four); anything
     else raises ValueError('Invalid sign inv net')."""
     assert net_params["sign_inv_net"] is not None, "did not specify sign inv net"
     kind = net_params["sign_inv_net"]
+    if kind not in encoders:
+        raise ValueError("Invalid sign inv net")
     args = (1, net_params["hidden_dim"], net_params["phi_out_dim"], net_params["sign_inv_layers"], net_params["pos_enc_dim"])
-    kw = dict(use_bn=True, dropout=net_params["dropout"], activation=net_params["sign_inv_activation"])
-    if kind == "gcn":
-        return GCNDeepSigns(*args, **kw)
-    if kind == "gin":
-        return GINDeepSigns(*args, **kw)
     if kind == "masked_gin":
-        return MaskedGINDeepSigns(*args, net_params["device"], **kw)
-    if kind == "transformer":
-        return TransformerDeepSigns(*args, **kw)
-    raise ValueError("Invalid sign inv net")
+        args += (net_params["device"],)
+    return encoders[kind](*args, use_bn=True, dropout=net_params["dropout"], activation=net_params["sign_inv_activation"])
+
+
+def get_sign_inv_net(net_params):
+    """The reference's factory over the classes of this module (dropout 0 and ReLU only: see ENCODERS of the opt-in modules)."""
+    return sign_inv_net_from(net_params, ENCODERS)

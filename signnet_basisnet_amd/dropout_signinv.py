@@ -39,15 +39,7 @@ ENCODERS = {"gcn": GCNDeepSigns, "gin": GINDeepSigns, "masked_gin": MaskedGINDee
 def get_sign_inv_net(net_params):
     """dgl_deepsigns.get_sign_inv_net with the classes of this module: `net_params['dropout']` reaches the encoder, as in
     nets/ZINC_graph_regression/sign_inv_net.py:7-13."""
-    assert net_params["sign_inv_net"] is not None, "did not specify sign inv net"
-    kind = net_params["sign_inv_net"]
-    if kind not in ENCODERS:
-        raise ValueError("Invalid sign inv net")
-    args = (1, net_params["hidden_dim"], net_params["phi_out_dim"], net_params["sign_inv_layers"], net_params["pos_enc_dim"])
-    kw = dict(use_bn=True, dropout=net_params["dropout"], activation=net_params["sign_inv_activation"])
-    if kind == "masked_gin":
-        return MaskedGINDeepSigns(*args, net_params["device"], **kw)
-    return ENCODERS[kind](*args, **kw)
+    return dgl_deepsigns.sign_inv_net_from(net_params, ENCODERS)
 
 
 class _SeedsEncoder:
